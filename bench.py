@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- VP8 decode pixel path on MI355X: Mpix/s on a 1080p all-key-frame stream.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--workload 1080p|4k]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--workload 1080p|4k] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` and `ms_per_step` of the timed launch, its
+HIP-event kernel times and the roofline derived from them.  `--full` adds everything else the line has carried: the MD5 gates
+against the reference listings (1 GPU: a sample of the launch's frames; N > 1: the sharded listing), the consumer probes, the
+raster form, single-frame latencies, the HBM copy probe, the 4K stream, the batch curve and dense content, the inter-frame probes,
+the end-to-end pipelines and the CPU baseline (the `--no-*` options leave single probes of a full run out).  `--dump-outputs DIR`
+writes, after the timed steps, what the last step decoded: a fixed sample of its frames as packed I420 pixels in float32
+(DIR/frames.npy, one row a frame, at most 64 MB) and their indices in the launch (DIR/frame_index.npy); with N > 1 every rank
+writes its own pair, prefixed rank<r>_.
 
 One "step" = one pass of the whole pixel path (dequant + IDCT / WHT, intra reconstruction, in-loop deblocking filter: the
 kernels behind include/vp8hip.h) over a batch of F independent key frames.  What is resident in HBM when the timed region starts
@@ -14,8 +23,8 @@ once on the host, outside the timed region) looped F/10 times -- legal because e
 (macroblock-window tiles, include/vp8hip.h "two forms"), which the consumers of such a pipeline read without a further pass --
 the device's MD5 kernel (vpxdec --md5 / decode_to_md5), a batch download into page-locked memory (the tiled -> raster pass IS
 the download), the border-extended raster form for inter prediction on demand.  `config.consumers` times the step with each of
-them behind it; `config.with_raster_form` is round 3's step (decode, then the raster form of every frame in HBM).  Before
-timing, decoded frames are checked bit-exactly against the reference decoder's per-frame MD5s (tests/golden/*.md5).
+them behind it; `config.with_raster_form` is round 3's step (decode, then the raster form of every frame in HBM).  With --full,
+decoded frames are checked bit-exactly against the reference decoder's per-frame MD5s (tests/golden/*.md5) before timing.
 
 N > 1: one rank per GPU -- under torch.distributed.run, or spawned by bench.py itself when no launcher set
 WORLD_SIZE -- decoding ONE looped stream of N * F frames in contiguous blocks of F (rank r: frames [r*F, (r+1)*F),
@@ -438,6 +447,33 @@ def load_stream(P, ctx, fixture, F, lo):
     return nsrc, feed_s
 
 
+def frame_pixels(P, ctx, i, W):
+    """Frame buffer i of `ctx` as its planes back to back (Y, U, V: the bytes decode_to_md5 hashes), uint8, packed on the device
+    from whichever form the launch left (vp8hip_frames_fetch_i420_async) where the width allows, else downloaded plane by plane."""
+    import numpy as np
+    if W % 8 == 0:
+        return ctx.frames_i420(i, 1)[0]
+    return np.concatenate([p.ravel() for p in ctx.download_planes(i)])
+
+
+def dump_outputs(P, ctx, F, W, H, out_dir, prefix="", budget=64_000_000 - 4096):
+    """What the last timed step decoded, for comparing two builds output for output: a fixed sample of the launch's frames (seeded,
+    the first and the last always among them, as many whole frames as fit in `budget` bytes of float32) as packed I420 pixels,
+    one row a frame (<prefix>frames.npy), and their indices in the launch (<prefix>frame_index.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame_bytes = W * H + 2 * ((W + 1) // 2) * ((H + 1) // 2)
+    k = max(1, min(F, budget // (4 * frame_bytes + 8)))
+    rng = np.random.default_rng(20240)
+    pick = {0, F - 1}
+    while len(pick) < k:
+        pick.add(int(rng.integers(0, F)))
+    idx = np.array(sorted(pick)[:k], np.int64)
+    frames = np.stack([frame_pixels(P, ctx, int(i), W) for i in idx]).astype(np.float32)
+    np.save(os.path.join(out_dir, prefix + "frames.npy"), frames)
+    np.save(os.path.join(out_dir, prefix + "frame_index.npy"), idx.astype(np.float64))
+
+
 def timed_steps(P, ctx, jobs, F, steps, warmup, barrier):
     for _ in range(warmup):
         ctx.decode_array(jobs, F, P.STAGE_ALL)
@@ -531,7 +567,14 @@ def main():
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--no-4k-probe", action="store_true")
     ap.add_argument("--no-curve", action="store_true", help="skip config.batch_curve and config.dense_content")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: MD5 gates, consumer / raster / latency / copy probes, 4K, batch curve, dense content, "
+                         "inter-frame probes, end-to-end pipelines, CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the frames the last step decoded to DIR/*.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)
@@ -604,7 +647,7 @@ def main():
     # ---- correctness gate 1 (multi-GPU): a 16-frames-per-rank prefix stream decoded the sharded way -- every rank its block,
     # MD5 of every frame, digests all-gathered over RCCL -- must give the 1-GPU decode_to_md5 listing
     listing_ok = None
-    if dist is not None:
+    if dist is not None and args.full:
         nv = 16 * world
 
         def decode_block(vlo, vhi):
@@ -623,30 +666,32 @@ def main():
 
         listing = sharding.sharded_listing(dist, nv, decode_block, device=coll_dev)
         listing_ok = listing == [gold[i % nsrc] for i in range(nv)]
-    # ---- correctness gate 2: one untimed pass of the timed launch, >= 64 frames spread over strands, waves and the whole
+    # ---- correctness gate 2 (--full): one untimed pass of the timed launch, >= 64 frames spread over strands, waves and the whole
     # shard checked against the reference MD5s
-    ctx.decode_array(jobs, F, P.STAGE_ALL)
-    ctx.sync()
-    import random
-    rnd = random.Random(1234 + rank)
-    sample = sorted(set([0, 1, 7, 8, 9, 63, 64, 65, F // 2, F - 2, F - 1] + [rnd.randrange(F) for _ in range(64)]))
-    sample = [i for i in sample if 0 <= i < F]
-    ok = 1
-    for i in sample:
-        # (hashed on the HOST: the frame packed on the device from the tiles the launch left, vp8hip_frames_fetch_i420_async -- the
-        # raster pool of all F frame buffers, 56 GB at 16,384 1080p frames, is not allocated for the sake of 75 of them)
-        if (hashlib.md5(ctx.frames_i420(i, 1)[0].tobytes()).hexdigest() if W % 8 == 0 else P.planes_md5(*ctx.download_planes(i))) != gold[(lo + i) % nsrc]:
+    sample = []
+    if args.full:
+        ctx.decode_array(jobs, F, P.STAGE_ALL)
+        ctx.sync()
+        import random
+        rnd = random.Random(1234 + rank)
+        sample = sorted(set([0, 1, 7, 8, 9, 63, 64, 65, F // 2, F - 2, F - 1] + [rnd.randrange(F) for _ in range(64)]))
+        sample = [i for i in sample if 0 <= i < F]
+        ok = 1
+        for i in sample:
+            # (hashed on the HOST: the frame packed on the device from the tiles the launch left, vp8hip_frames_fetch_i420_async -- the
+            # raster pool of all F frame buffers, 56 GB at 16,384 1080p frames, is not allocated for the sake of 75 of them)
+            if hashlib.md5(frame_pixels(P, ctx, i, W).tobytes()).hexdigest() != gold[(lo + i) % nsrc]:
+                ok = 0
+                sys.stderr.write(f"[bench] rank {rank}: frame {lo + i} MD5 mismatch\n")
+        if listing_ok is False:
             ok = 0
-            sys.stderr.write(f"[bench] rank {rank}: frame {lo + i} MD5 mismatch\n")
-    if listing_ok is False:
-        ok = 0
-        sys.stderr.write(f"[bench] rank {rank}: the gathered sharded listing differs from the 1-GPU listing\n")
-    if dist is not None:
-        t = torch.tensor([ok], device=coll_dev, dtype=torch.int32)
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        ok = int(t.item())
-    if not ok:
-        raise SystemExit("decode_to_md5 precondition failed: GPU output differs from the reference")
+            sys.stderr.write(f"[bench] rank {rank}: the gathered sharded listing differs from the 1-GPU listing\n")
+        if dist is not None:
+            t = torch.tensor([ok], device=coll_dev, dtype=torch.int32)
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            ok = int(t.item())
+        if not ok:
+            raise SystemExit("decode_to_md5 precondition failed: GPU output differs from the reference")
 
     def barrier():
         if dist is not None:
@@ -655,6 +700,8 @@ def main():
         ctx.sync()
 
     elapsed_local, ms, st = timed_steps(P, ctx, jobs, F, args.steps, args.warmup, barrier)
+    if args.dump_outputs:
+        dump_outputs(P, ctx, F, W, H, args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "")
     mem_gb = {k: round(v / 1e9, 2) for k, v in ctx.memory_usage().items() if v}      # (what the timed step had resident on this rank)
     elapsed = elapsed_local
     per_rank = [elapsed_local]
@@ -670,7 +717,7 @@ def main():
         elapsed = max(per_rank)
     # ---- the step with a consumer behind it (rank 0, N = 1; never `value`): what reads the frames a step leaves
     consumers = with_raster = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         def timed(fn, reps=3):
             fn(); ctx.sync()
             t0 = time.perf_counter()
@@ -745,7 +792,7 @@ def main():
     # single-frame latency: one frame per launch (what a single-stream decoder sees), kernels only
     latency_ms = None
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         one = (P.Job * 1)()
         one[0].ir_slot, one[0].dst_fb = 0, 0
         for k in range(4):
@@ -758,12 +805,12 @@ def main():
         latency_ms = (time.perf_counter() - tl) / 20 * 1e3
     ctx.close()
     inter_latency = None
-    if rank == 0 and world == 1 and args.workload == "1080p":
+    if rank == 0 and world == 1 and args.workload == "1080p" and args.full:
         try:
             inter_latency = single_inter_latency(P, local_rank)
         except Exception as ex:      # noqa: BLE001 - a probe, not the benchmark
             inter_latency = {"error": repr(ex)}
-    if rank == 0:
+    if rank == 0 and args.full:
         # what the HBM system delivers to a plain device-to-device copy on this box (SURVEY.md 8d asks for the probe)
         a = torch.empty(2 << 30, dtype=torch.uint8, device="cuda")
         b = torch.empty_like(a)
@@ -832,7 +879,7 @@ def main():
                 "host_feeder_s_for_source_frames": round(feed_s, 4),
                 "rank_startup_s": {"host_feeder_source_frames": round(feed_s, 3), "slot_copies_device_to_device": round(copy_s, 3),
                                    "note": f"rank 0, outside the timed region: {F} slots filled from {nsrc} source frames (vp8hip_ir_copy)"},
-                "single_frame_launch_ms": round(latency_ms, 3),
+                "single_frame_launch_ms": round(latency_ms, 3) if latency_ms is not None else None,
                 "single_frame_launch_inter": inter_latency,
                 "consumers": consumers,
                 "with_raster_form": with_raster,
@@ -871,7 +918,7 @@ def main():
                 "device_copy_probe_GBps": round(copy_gbps, 1) if copy_gbps else None,
             },
         }
-        if world == 1 and args.workload == "1080p" and not args.no_4k_probe:
+        if args.full and world == 1 and args.workload == "1080p" and not args.no_4k_probe:
             # BASELINE configs[4]'s stream on one GPU: 3840x2160 all-key-frame, same path, measured the same way
             try:
                 fx4, W4, H4 = WORKLOADS["4k"]
@@ -902,7 +949,7 @@ def main():
                 c4.close()
             except Exception as ex:      # a probe, not the benchmark: report, do not fail the line
                 out["config"]["workload_4k"] = {"error": repr(ex)}
-        if world == 1 and args.workload == "1080p" and not args.no_curve:
+        if args.full and world == 1 and args.workload == "1080p" and not args.no_curve:
             # throughput against frames per launch (the lane-per-row kernels want every SIMD's two wave slots full: 16,384 1080p
             # frames; up to 512 frames the wave-per-row kernels run), each point a context of its own with just that many frames
             # resident, every frame's MD5 checked; the last point is the headline launch itself
@@ -933,7 +980,7 @@ def main():
                     out["config"][key] = d
                 except Exception as ex:          # noqa: BLE001
                     out["config"][key] = {"error": repr(ex)}
-        if world == 1 and args.workload == "1080p" and not args.no_inter_probe:
+        if args.full and world == 1 and args.workload == "1080p" and not args.no_inter_probe:
             try:
                 out["config"]["inter_frames"] = inter_frame_probe(P, local_rank)
             except Exception as ex:      # a probe, not the benchmark: report, do not fail the line
@@ -943,7 +990,7 @@ def main():
                 out["config"]["inter_frames_typical"] = inter_frame_probe(P, local_rank, name="p_1920x1080", k=5)
             except Exception as ex:      # noqa: BLE001
                 out["config"]["inter_frames_typical"] = {"error": repr(ex)}
-        if world == 1 and args.workload == "1080p" and not args.no_end_to_end:
+        if args.full and world == 1 and args.workload == "1080p" and not args.no_end_to_end:
             # host-inclusive rates (never `value`): compressed frames in host memory -> per-frame MD5.  Every probe on its own: one
             # that fails reports its error and leaves the others' results alone
             e2 = out["config"]["end_to_end"] = {}
@@ -968,7 +1015,7 @@ def main():
             probe("device_entropy_frames_stay", lambda: batch_md5_probe(
                 fixture, local_rank, 147456, ("--device-entropy", "--no-download", "--batch", "8192", "--entropy-batch", "24576")))
             probe("inter_streams_device_entropy", lambda: streams_probe(local_rank))
-        if not args.no_cpu_baseline and world == 1:      # the contract: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the contract: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(fixture)
         print(json.dumps(out))
         sys.stdout.flush()

@@ -20,7 +20,7 @@ def test_bench_two_ranks_one_device(workload, frames):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", workload, "--frames", str(frames),
-                        "--steps", "1", "--warmup", "1", "--no-inter-probe", "--no-4k-probe", "--no-end-to-end", "--no-cpu-baseline"],
+                        "--steps", "1", "--warmup", "1", "--full", "--no-inter-probe", "--no-4k-probe", "--no-end-to-end", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -1,19 +1,50 @@
 """CPU: the key-frame stream writer (tests/vp8_writer.py) against the two decoders that matter:
  * the host feeder must read back exactly the IR the stream was written from (modes, segments, sub-block modes, eobs,
    coefficients) -- a round trip through bool coder, mode trees, token trees and contexts;
- * the REAL reference decoder (oracle/_ref, built from /root/reference) must decode the stream to the frames the
-   oracle produces from that IR.  This pins feeder AND oracle on content no encoder would choose: every mode
-   everywhere, all segment / delta features, 1..8 token partitions, coefficients up to +-2047, odd sizes."""
+ * the REAL reference decoder must decode the stream to the frames the oracle produces from that IR: oracle/_ref/ref_md5
+   where the reference is built here (oracle/Makefile), else its listing recorded for the same stream bytes
+   (tests/golden/writer_ref_md5.json; VP8_RECORD_REF_DIGESTS=1 with the reference built rewrites it).  This pins feeder
+   AND oracle on content no encoder would choose: every mode everywhere, all segment / delta features, 1..8 token
+   partitions, coefficients up to +-2047, odd sizes."""
+import hashlib
+import json
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from vp8_testlib import ROOT, load_package, oracle_decode, synth_ir
+from vp8_testlib import GOLDEN, ROOT, load_package, oracle_decode, synth_ir
 from vp8_writer import write_inter_frame, write_ivf, write_key_frame
 
 REF_MD5 = os.path.join(ROOT, "oracle", "_ref", "ref_md5")
+LISTINGS = os.path.join(GOLDEN, "writer_ref_md5.json")
+RECORD = os.environ.get("VP8_RECORD_REF_DIGESTS") == "1"
+
+
+def reference_listing(key, ivf):
+    """The reference decoder's per-frame MD5s of the stream in `ivf`: printed by oracle/_ref/ref_md5 where it is built (and then
+    equal to the recorded listing), else the listing recorded from it for a stream with the same SHA-256."""
+    sha = hashlib.sha256(open(ivf, "rb").read()).hexdigest()
+    table = json.load(open(LISTINGS)) if os.path.exists(LISTINGS) else {}
+    live = None
+    if os.path.exists(REF_MD5):
+        out = str(ivf) + ".md5"
+        r = subprocess.run([REF_MD5, str(ivf), out], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        live = [l.split()[0] for l in open(out)]
+    if RECORD:
+        assert live is not None, "VP8_RECORD_REF_DIGESTS=1 needs the reference build (make -C oracle ref)"
+        table[key] = {"stream_sha256": sha, "md5": live}
+        with open(LISTINGS, "w") as f:
+            json.dump(table, f, indent=1, sort_keys=True)
+            f.write("\n")
+    rec = table.get(key)
+    assert rec is not None, f"{key}: no reference listing recorded in {LISTINGS}"
+    assert rec["stream_sha256"] == sha, f"{key}: the written stream is not the one the reference listing was recorded from"
+    if live is not None:
+        assert live == rec["md5"], key
+    return rec["md5"]
 
 CASES = [  # width, height, seed, log2 partitions, filter_type, dense, big coefficients, segmented
     (16, 16, 1, 0, 0, 0.5, False, True), (48, 32, 2, 1, 1, 0.4, False, True), (176, 144, 3, 2, 0, 0.3, True, True),
@@ -54,15 +85,12 @@ def test_feeder_reads_back_the_ir(pkg, case):
     assert np.array_equal(c2[live], coef[live])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MD5), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("case", CASES)
-def test_reference_decodes_written_streams_like_the_oracle(pkg, case, tmp_path):
+def test_reference_decodes_written_streams_like_the_oracle(pkg, case, tmp_path, request):
     hdr, mbs, coef, mvs, data = _stream(case)
-    ivf, out = tmp_path / "s.ivf", tmp_path / "s.md5"
+    ivf = tmp_path / "s.ivf"
     write_ivf(ivf, hdr.width, hdr.height, [data, data])
-    r = subprocess.run([REF_MD5, str(ivf), str(out)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    ref = [l.split()[0] for l in open(out)]
+    ref = reference_listing(request.node.name, ivf)
     g = pkg.geom(hdr.width, hdr.height)
     buf = np.zeros(g.frame_size, np.uint8)
     oracle_decode(hdr, mbs, coef, mvs, buf, (None, None, None))
@@ -164,16 +192,13 @@ def test_feeder_reads_back_inter_frames(pkg, case):
         assert np.array_equal(m2[live, 8:33], mbs[live, 8:33]) and np.array_equal(c2[live], coef[live]), k
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MD5), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("case", INTER_CASES)
-def test_reference_decodes_written_inter_streams_like_the_oracle(pkg, case, tmp_path):
+def test_reference_decodes_written_inter_streams_like_the_oracle(pkg, case, tmp_path, request):
     w, h, seed, plan, lp, big = case
     frames, _ = inter_sequence(w, h, seed, plan, lp, big=big)
-    ivf, out = tmp_path / "s.ivf", tmp_path / "s.md5"
+    ivf = tmp_path / "s.ivf"
     write_ivf(ivf, w, h, frames)
-    r = subprocess.run([REF_MD5, str(ivf), str(out)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    ref = [l.split()[0] for l in open(out)]
+    ref = reference_listing(request.node.name, ivf)
     g = pkg.geom(w, h)
     bufs = [np.zeros(g.frame_size, np.uint8) for _ in range(4)]
     mine = []
@@ -196,10 +221,9 @@ def fuzz_case(seed):
 FUZZ_SEEDS = list(range(100, 124))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MD5), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("seed", FUZZ_SEEDS)
-def test_reference_decodes_fuzzed_inter_streams_like_the_oracle(pkg, seed, tmp_path):
-    test_reference_decodes_written_inter_streams_like_the_oracle(pkg, fuzz_case(seed), tmp_path)
+def test_reference_decodes_fuzzed_inter_streams_like_the_oracle(pkg, seed, tmp_path, request):
+    test_reference_decodes_written_inter_streams_like_the_oracle(pkg, fuzz_case(seed), tmp_path, request)
 
 
 @pytest.mark.parametrize("seed", FUZZ_SEEDS[:8])

@@ -12,11 +12,11 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=${1:-r04_a}; NF=${2:-4096}; O=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $O/for_profiles
 R=$GRAFT_REPO_ROOT
 cd /tmp; export TMPDIR=/tmp
-B="--steps 10 --warmup 2 --no-inter-probe --no-4k-probe --no-end-to-end --no-cpu-baseline"
+B="--steps 10 --warmup 2 --full --no-inter-probe --no-4k-probe --no-end-to-end --no-cpu-baseline"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_bench -- python3 $R/bench.py $B > $O/kt_bench.json 2> $O/kt_bench.err; echo "kt_bench rc=$?" >> $O/summary.txt
 timeout 600 python3 $R/bench.py $B > $O/unprofiled_bench.json 2> $O/unprofiled.err; echo "unprofiled rc=$?" >> $O/summary.txt
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_batch_md5 -- $R/libvpx.opencl_amd/bin/batch_md5 --device-entropy --no-download --batch 8192 --entropy-batch 24576 --loop 12288 $R/tests/golden/kf_1920x1080.ivf /tmp/o.md5 > $O/kt_batch_md5.log 2>&1; echo "kt_batch_md5 rc=$?" >> $O/summary.txt
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_inter -- python3 $R/bench.py --steps 2 --warmup 1 --no-4k-probe --no-end-to-end --no-cpu-baseline > $O/kt_inter.json 2> $O/kt_inter.err; echo "kt_inter rc=$?" >> $O/summary.txt
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_inter -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-4k-probe --no-end-to-end --no-cpu-baseline > $O/kt_inter.json 2> $O/kt_inter.err; echo "kt_inter rc=$?" >> $O/summary.txt
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_streams -- $R/libvpx.opencl_amd/bin/batch_md5 --streams 4096 $R/tests/golden/p_1920x1080.ivf /tmp/o.md5 > $O/kt_streams.log 2>&1; echo "kt_streams rc=$?" >> $O/summary.txt
 for n in kt_bench kt_batch_md5 kt_inter kt_streams; do f=$(find $O/$n -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/for_profiles/${TAG}_${n}_kernel_stats.csv; done
 cp $O/kt_bench.json $O/for_profiles/${TAG}_kt_bench.json; cp $O/unprofiled_bench.json $O/for_profiles/${TAG}_unprofiled_bench.json

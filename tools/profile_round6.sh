@@ -34,7 +34,7 @@ kt_chain)
     f=$(find $O/kt_chain -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/for_profiles/${TAG}_kt_chain${NJ}_kernel_stats.csv
     cp $O/kt_chain.log $O/for_profiles/${TAG}_kt_chain${NJ}.log; cat $O/kt_chain.log; head -8 $f | cut -c1-160 ;;
 kt_bench)
-    B="--steps 10 --warmup 2 --no-inter-probe --no-4k-probe --no-end-to-end --no-cpu-baseline --no-curve"
+    B="--steps 10 --warmup 2 --full --no-inter-probe --no-4k-probe --no-end-to-end --no-cpu-baseline --no-curve"
     timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_bench -- python3 $R/bench.py $B > $O/kt_bench.json 2> $O/kt_bench.err; echo "kt_bench rc=$?" >> $O/summary.txt
     timeout 600 python3 $R/bench.py $B > $O/unprofiled_bench.json 2> $O/unprofiled.err; echo "unprofiled rc=$?" >> $O/summary.txt
     f=$(find $O/kt_bench -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/for_profiles/${TAG}_kt_bench_kernel_stats.csv
