@@ -318,6 +318,18 @@ int  vp8hip_join(vp8hip_ctx *ctx);
 /* in / out: n x 400 bytes = rows and columns -4..15 of a luma macroblock (20 x 20); par: n x 8 bytes = mblim, blim, lim, hev_thr,
  * left edge filtered, inner edges filtered, top edge filtered, filter type (0 normal, 1 simple) */
 int  vp8hip_lane_loop_filter_mbs(const uint8_t *in, uint8_t *out, const uint8_t *par, int n);
+/* the chroma role of the same: in / out: n x 144 bytes = rows and columns -4..7 of a chroma macroblock (12 x 12); par: as above.
+ * Two block rows, the first with the macroblock's top edge; simple-filter macroblocks are left alone (loopfilter.c:283-299). */
+int  vp8hip_lane_loop_filter_chroma_mbs(const uint8_t *in, uint8_t *out, const uint8_t *par, int n);
+/* one edge across each line: lines / out: n x 8 bytes = p3 p2 p1 p0 q0 q1 q2 q3, n even, lines 2i and 2i+1 share lane i;
+ * par: n/2 x 8 bytes = sharpness (0..7), filter level (0..63), frame type (0 key, 1 inter), kind (0 macroblock edge, 1 inner
+ * edge, 2 simple filter on the macroblock-edge limit, 3 simple filter on the inner-edge limit), edge filtered (0 no), 3 unused.
+ * The limits are derived on the device (vp8_loop_filter_update_sharpness, loopfilter.c:66-96, and the hev threshold table). */
+int  vp8hip_lane_loop_filter_lines(const uint8_t *lines, uint8_t *out, const uint8_t *par, int n);
+/* the loop filter's clamp(f + 3 w) on 16-bit pairs against its exact value and its stepwise form, for all 2^32 pairs (f, w):
+ * *mismatches = pairs where they differ; first_bad: nbad (<= 4096) records of 4 words = the low half's pair f << 16 | w, the
+ * high half's, the one-instruction result, the stepwise result */
+int  vp8hip_lane_add3w_sweep(uint64_t *mismatches, uint32_t *first_bad, int nbad);
 /* mode: n B_PREDICTION_MODEs; ctx: n x 16 bytes = above[0..7], left[0..3], top_left, 3 bytes of padding; out: n x 16 bytes, row-major */
 int  vp8hip_lane_intra4x4(const uint8_t *mode, const uint8_t *ctx, uint8_t *out, int n);
 /* coef: n x 16 in IR order (column-major, vp8_ir.h); dq: n x (dc, ac); pred / out: n x 16 bytes, row-major */

@@ -304,18 +304,25 @@ __device__ __forceinline__ v2s lf_keep(v2s f, v2u mask)
 
 // filter_value = clamp(filter_value + 3 * (qs0 - ps0)) (loopfilter_filters.c:66, 176): three saturating adds of
 // the saturated difference give the same result as one clamp of the exact sum (same-signed increments)
-__device__ __forceinline__ v2s add3w(v2s f, v2s qs0, v2s ps0)
+__device__ __forceinline__ v2s add3w_stepwise(v2s f, v2s qs0, v2s ps0)
 {
     const v2s w = subs(qs0, ps0);
-#ifdef LF_ADD3_STEPWISE      // (through round 5: three saturating adds)
     return adds(adds(adds(f, w), w), w);
-#else
+}
+// the same in one instruction on gfx950; LF_ADD3_STEPWISE (through round 5) and any other target take the stepwise form
+__device__ __forceinline__ v2s add3w(v2s f, v2s qs0, v2s ps0)
+{
+#if defined(__gfx950__) && !defined(LF_ADD3_STEPWISE)
+    const v2s w = subs(qs0, ps0);
     // ONE saturation of the exact sum f + 3 w (v_pk_mad_i16 ... clamp: the multiply-add is exact, the clamp works on its result): where
     // w itself was saturated 3 w lies beyond the range by more than any f brings back, so the result is the clamp of the exact sum
-    // either way -- which is what the reference computes (loopfilter_filters.c:66, 176)
+    // either way -- which is what the reference computes (loopfilter_filters.c:66, 176).  vp8hip_lane_add3w_sweep checks both
+    // forms against that clamp for every pair (f, w).
     u32 d;
     asm("v_pk_mad_i16 %0, %1, %2, %3 op_sel_hi:[1,0,1] clamp" : "=v"(d) : "v"(as_u32(w)), "s"(3u), "v"(as_u32(f)));
     return as_v2s(d);
+#else
+    return add3w_stepwise(f, qs0, ps0);
 #endif
 }
 
