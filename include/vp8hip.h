@@ -183,6 +183,30 @@ int  vp8hip_postproc(vp8hip_ctx *ctx, int src_fb, int dst_fb, int tmp_fb, const 
  * its output: vp8hip_postproc(dst_fb -> prev_fb), or with src_fb == dst_fb for the noise alone).  qprev <= qcurr <= 127.
  * Asynchronous on the context's stream; mb_class may be reused when the call returns. */
 int  vp8hip_mfqe(vp8hip_ctx *ctx, int show_fb, int prev_fb, int dst_fb, const uint8_t *mb_class, int qcurr, int qprev);
+/* The decoder's debug overlays (vp8/common/postproc.c:1007-1362, CONFIG_POSTPROC_VISUALIZER) drawn into frame buffer fb in place,
+ * from the macroblocks of IR slot ir_slot (modes, reference frames, sub-block modes, skip flags; the vectors of an inter frame),
+ * in the reference's order: the text the VP8HIP_VIS_TXT_* flags ask for (7x5 characters of 0 / 255 addressed linearly from the
+ * luma origin: a long string runs on into the rows below), the motion vectors of the modes in mv_mask as inverted Bresenham
+ * lines, the block-mode colours (mb_modes_mask: macroblock modes, where the VALUE 4 also selects B_PRED's sub-blocks; b_modes_mask:
+ * sub-blocks of B_PRED macroblocks when it has bit B_PRED), the reference-frame colours of the frames in ref_frame_mask.  The
+ * flags are the VP8D_DEBUG_* bits of vp8/common/ppflags.h; a phase runs when its flag and its mask are set, the masks are the
+ * values of the VP8_SET_DBG_* controls.  The strings are formatted by the caller (NULL: not drawn), at most 511 characters.
+ * Writes that would leave the frame buffer are dropped.  Asynchronous on the context's stream; the strings may be reused when the
+ * call returns. */
+#define VP8HIP_VIS_TXT_FRAME_INFO     (1u << 3)
+#define VP8HIP_VIS_TXT_MBLK_MODES     (1u << 4)
+#define VP8HIP_VIS_TXT_DC_DIFF        (1u << 5)
+#define VP8HIP_VIS_TXT_RATE_INFO      (1u << 6)
+#define VP8HIP_VIS_DRAW_MV            (1u << 7)
+#define VP8HIP_VIS_CLR_BLK_MODES      (1u << 8)
+#define VP8HIP_VIS_CLR_FRM_REF_BLKS   (1u << 9)
+typedef struct vp8hip_vis {
+    unsigned flags;           /* VP8HIP_VIS_* (VP8D_DEBUG_*) bits; others are ignored */
+    int ref_frame_mask, mb_modes_mask, b_modes_mask, mv_mask;   /* the four VP8_SET_DBG_* values */
+    const char *frame_info;   /* host-formatted, or NULL */
+    const char *rate_info;    /* host-formatted, or NULL */
+} vp8hip_vis;
+int  vp8hip_visualize(vp8hip_ctx *ctx, int fb, int ir_slot, const vp8hip_vis *v);
 
 /* Entropy decoding on the device (key frames).  What it replaces: the per-macroblock half of the host feeder -- the reference's
  * vp8_kfread_modes (vp8/decoder/decodemv.c:50-173) and vp8_decode_mb_tokens (vp8/decoder/detokenize.c:183-405) driven by

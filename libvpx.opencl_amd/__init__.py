@@ -360,6 +360,11 @@ class PostprocParams(ctypes.Structure):     # vp8hip_pp, include/vp8hip.h
 PP_DEBLOCK, PP_DEMACROBLOCK, PP_ADDNOISE = 1, 2, 4
 
 
+class VisParams(ctypes.Structure):          # vp8hip_vis, include/vp8hip.h
+    _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
+                ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
+
+
 def load_hip():
     global _hip
     if _hip is None:
@@ -393,6 +398,7 @@ def load_hip():
         L.vp8hip_stream.restype = c_void_p
         L.vp8hip_postproc.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.POINTER(PostprocParams)]
         L.vp8hip_mfqe.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int]
+        L.vp8hip_visualize.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(VisParams)]
         L.vp8hip_entropy_decode.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t]
         L.vp8hip_entropy_status.argtypes = [c_void_p, c_int, c_void_p]
         L.vp8hip_ir_fetch.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
@@ -648,6 +654,15 @@ class Vp8Hip:
         mb_class = np.ascontiguousarray(mb_class, np.uint8)
         assert mb_class.size == self.g_mbs()
         self._chk(self.L.vp8hip_mfqe(self.h, show_fb, prev_fb, dst_fb, mb_class.ctypes.data, qcurr, qprev), "mfqe")
+
+    def visualize(self, fb, slot, flags, ref_frame_mask=0, mb_modes_mask=0, b_modes_mask=0, mv_mask=0, frame_info=None,
+                  rate_info=None):
+        """The decoder's debug overlays (VP8D_DEBUG_* flags, the four VP8_SET_DBG_* masks) drawn into frame buffer fb in place from
+        the macroblocks of IR slot `slot` (include/vp8hip.h); the strings are str or None."""
+        v = VisParams(flags, ref_frame_mask, mb_modes_mask, b_modes_mask, mv_mask,
+                      frame_info.encode("latin-1") if frame_info is not None else None,
+                      rate_info.encode("latin-1") if rate_info is not None else None)
+        self._chk(self.L.vp8hip_visualize(self.h, fb, slot, ctypes.byref(v)), "visualize")
 
     def g_mbs(self):
         return (self.g.aligned_w // 16) * (self.g.aligned_h // 16)

@@ -201,6 +201,9 @@ extern "C" void vp8hip_destroy(vp8hip_ctx *c)
     if (c->d_mfqe) (void)hipFree(c->d_mfqe);
     if (c->h_mfqe) (void)hipHostFree(c->h_mfqe);
     if (c->ev_mfqe) (void)hipEventDestroy(c->ev_mfqe);
+    if (c->d_vis) (void)hipFree(c->d_vis);
+    if (c->h_vis) (void)hipHostFree(c->h_vis);
+    if (c->ev_vis) (void)hipEventDestroy(c->ev_vis);
     destroy_events(c);
     if (c->stream_d2h) { (void)hipStreamSynchronize(c->stream_d2h); (void)hipStreamDestroy(c->stream_d2h); }
     if (c->ev_d2h_from) (void)hipEventDestroy(c->ev_d2h_from);

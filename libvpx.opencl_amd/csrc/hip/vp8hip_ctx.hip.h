@@ -3,6 +3,7 @@
 //   vp8hip_launch.hip   vp8hip_decode: which kernels a launch runs; the two forms a frame buffer has on the device
 //   vp8hip_entropy.hip  vp8hip_entropy_decode
 //   vp8hip_postproc.hip vp8hip_postproc, vp8hip_mfqe
+//   vp8hip_visualize.hip vp8hip_visualize
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -119,6 +120,7 @@ struct vp8hip_ctx {
     // vp8hip_postproc: dither table (440 shorts), noise table (3072) and per-row noise phases (16384) on the device
     char *d_pp, *h_pp; bool pp_rv_loaded; hipEvent_t ev_pp;
     uint8_t *d_mfqe, *h_mfqe; int mfqe_cap; hipEvent_t ev_mfqe;     // vp8hip_mfqe: the macroblock classes of the frame
+    char *d_vis, *h_vis; hipEvent_t ev_vis;         // vp8hip_visualize: the frame-info and rate strings on their way to the device
     // vp8hip_entropy_decode: the frames' descriptions, their bytes, per-frame scratch and status on the device; the stream the
     // launch runs on (its own: beside the pixel path of other slots) and the events that order it against the main stream
     // (descriptions and bytes in TWO sets: a launch's input is copied on a stream of its own, stream_h2d, while the launch before

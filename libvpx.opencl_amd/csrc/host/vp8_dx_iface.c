@@ -56,6 +56,8 @@ struct vpx_codec_alg_priv {
     vp8_pp_state           *pp;
     uint8_t                *mb_class;        /* VP8_MFQE: a byte per macroblock (vp8_pp_mfqe_classes) */
     size_t                  mb_class_cap;
+    /* VP8_SET_DBG_* (vp8_dx_iface.c:69-72 with CONFIG_POSTPROC_VISUALIZER): the debug overlays' masks */
+    int                     dbg_color_ref_frame_flag, dbg_color_mb_modes_flag, dbg_color_b_modes_flag, dbg_display_mv_flag;
     char                    detail[160];
     double                  t_parse, t_launch, t_down;   /* VP8HIP_TRACE: seconds per phase of vp8_decode */
     long                    t_frames;
@@ -326,6 +328,14 @@ static vpx_codec_err_t vp8_decode(vpx_codec_alg_priv_t *p, const uint8_t *data, 
                 p->postproc_cfg.noise_level = 0;
                 p->postproc_cfg_set = 1;
             }
+            /* the flags word of vp8_dx_iface.c:446-465: the configured flags and a debug bit for every nonzero VP8_SET_DBG_* */
+            const int flags_word = p->postproc_cfg.post_proc_flag
+                                 | (p->dbg_color_ref_frame_flag ? VP8HIP_VIS_CLR_FRM_REF_BLKS : 0)
+                                 | (p->dbg_color_mb_modes_flag || p->dbg_color_b_modes_flag ? VP8HIP_VIS_CLR_BLK_MODES : 0)
+                                 | (p->dbg_display_mv_flag ? VP8HIP_VIS_DRAW_MV : 0);
+            const int debug = flags_word & (VP8HIP_VIS_TXT_FRAME_INFO | VP8HIP_VIS_TXT_MBLK_MODES | VP8HIP_VIS_TXT_DC_DIFF
+                                            | VP8HIP_VIS_TXT_RATE_INFO | VP8HIP_VIS_DRAW_MV | VP8HIP_VIS_CLR_BLK_MODES
+                                            | VP8HIP_VIS_CLR_FRM_REF_BLKS);
             {
                 int qprev = 0;
                 const int mfqe = vp8_pp_mfqe_step(p->pp, &p->postproc_cfg, hdr.base_qindex, &qprev);
@@ -345,11 +355,30 @@ static vpx_codec_err_t vp8_decode(vpx_codec_alg_priv_t *p, const uint8_t *data, 
                     } else if (filters && vp8hip_postproc(p->hip, FB_POST, FB_POST, FB_PPTMP, &pp))
                         return gpu_error(p, "vp8hip_postproc");
                     show_fb = FB_POST;
-                } else if (filters || (p->postproc_cfg.post_proc_flag & VP8_MFQE)) {
-                    /* (with VP8_MFQE the buffer holds every shown frame, filtered or not: :982-986) */
+                } else if (filters || (p->postproc_cfg.post_proc_flag & VP8_MFQE) || debug) {
+                    /* (with VP8_MFQE the buffer holds every shown frame, filtered or not: :982-986; the overlays are drawn into
+                       that buffer, never into a frame the decoder predicts from) */
                     if (vp8hip_postproc(p->hip, show_fb, FB_POST, FB_PPTMP, &pp)) return gpu_error(p, "vp8hip_postproc");
                     show_fb = FB_POST;
                 }
+            }
+            if (debug) {
+                /* postproc.c:1007-1362, into post_proc_buffer: with VP8_MFQE the next frame is blended against the overlaid
+                   picture, as in the reference.  The reference never computes bit rate or frame rate (onyxd_if.c:653 is
+                   compiled out): the rate string shows zeros. */
+                char info[96], rate[96];
+                vp8hip_vis vis;
+                snprintf(info, sizeof info, "F%1dG%1dQ%3dF%3dP%d_s%dx%d", hdr.frame_type == 0, hdr.refresh_golden, hdr.base_qindex,
+                         hdr.filter_level, flags_word, hdr.mb_cols, hdr.mb_rows);
+                snprintf(rate, sizeof rate, "Bitrate: %10.2f frame_rate: %10.2f ", 0.0, 0.0);
+                vis.flags = (unsigned)debug;
+                vis.ref_frame_mask = p->dbg_color_ref_frame_flag;
+                vis.mb_modes_mask = p->dbg_color_mb_modes_flag;
+                vis.b_modes_mask = p->dbg_color_b_modes_flag;
+                vis.mv_mask = p->dbg_display_mv_flag;
+                vis.frame_info = info;
+                vis.rate_info = rate;
+                if (vp8hip_visualize(p->hip, show_fb, 0, &vis)) return gpu_error(p, "vp8hip_visualize");
             }
         }
         /* the whole frame buffer, borders included, in one linear copy into the pinned mirror (same vp8ir_geom layout) */
@@ -383,11 +412,18 @@ static vpx_codec_err_t ctl_get_int(vpx_codec_alg_priv_t *p, int ctrl_id, va_list
     return VPX_CODEC_OK;
 }
 
-static vpx_codec_err_t ctl_incapable(vpx_codec_alg_priv_t *p, int ctrl_id, va_list ap)
+/* vp8_set_dbg_options (vp8_dx_iface.c:674-697 with CONFIG_POSTPROC_VISUALIZER): which modes / reference frames the debug
+ * overlays mark; they are drawn by a decoder created with VPX_CODEC_USE_POSTPROC (vp8hip_visualize) */
+static vpx_codec_err_t ctl_set_dbg(vpx_codec_alg_priv_t *p, int ctrl_id, va_list ap)
 {
-    (void)ctrl_id; (void)ap;
-    /* the debug overlays of CONFIG_POSTPROC_VISUALIZER (vp8_dx_iface.c:674-697 answers the same way without it) */
-    return set_detail(p, VPX_CODEC_INCAPABLE, "control not implemented by the HIP decoder");
+    const int data = va_arg(ap, int);
+    switch (ctrl_id) {
+    case VP8_SET_DBG_COLOR_REF_FRAME: p->dbg_color_ref_frame_flag = data; break;
+    case VP8_SET_DBG_COLOR_MB_MODES: p->dbg_color_mb_modes_flag = data; break;
+    case VP8_SET_DBG_COLOR_B_MODES: p->dbg_color_b_modes_flag = data; break;
+    case VP8_SET_DBG_DISPLAY_MV: p->dbg_display_mv_flag = data; break;
+    }
+    return VPX_CODEC_OK;
 }
 
 /* vp8_set_postproc (vp8_dx_iface.c:653-672) */
@@ -473,10 +509,10 @@ static vpx_codec_ctrl_fn_map_t vp8_ctf_maps[] = {
     { VP8_SET_REFERENCE, ctl_reference },
     { VP8_COPY_REFERENCE, ctl_reference },
     { VP8_SET_POSTPROC, ctl_set_postproc },
-    { VP8_SET_DBG_COLOR_REF_FRAME, ctl_incapable },
-    { VP8_SET_DBG_COLOR_MB_MODES, ctl_incapable },
-    { VP8_SET_DBG_COLOR_B_MODES, ctl_incapable },
-    { VP8_SET_DBG_DISPLAY_MV, ctl_incapable },
+    { VP8_SET_DBG_COLOR_REF_FRAME, ctl_set_dbg },
+    { VP8_SET_DBG_COLOR_MB_MODES, ctl_set_dbg },
+    { VP8_SET_DBG_COLOR_B_MODES, ctl_set_dbg },
+    { VP8_SET_DBG_DISPLAY_MV, ctl_set_dbg },
     { VP8D_GET_LAST_REF_UPDATES, ctl_get_int },
     { VP8D_GET_FRAME_CORRUPTED, ctl_get_int },
     { VP8D_GET_LAST_REF_USED, ctl_get_int },

@@ -6,7 +6,9 @@
  * --summary / --progress (frames, microseconds inside vpx_codec_decode only, fps -- the same
  * bracket as vpxdec.c:1041-1055), --limit, --skip, -t/--threads (host threads for the token partitions of a frame: the
  * entropy decode is the CPU side of this decoder, vp8_parser_set_threads), --codec=vp8, -v, and the VP8 post-processing options --postproc, --deblock,
- * --demacroblock-level=<n>, --noise-level=<n>, --mfqe (vpxdec.c:111-133, 779-812, 983-1002).
+ * --demacroblock-level=<n>, --noise-level=<n>, --mfqe (vpxdec.c:111-133, 779-812, 983-1002), and the debug overlays
+ * --pp-debug-info=<n>, --pp-dbg-ref-frame=<n>, --pp-dbg-mb-modes=<n>, --pp-dbg-b-modes=<n>, --pp-dbg-mvs=<n> (vpxdec.c:813-857,
+ * 1004-1030).
  * Input: IVF or WebM, probed in that order like vpxdec.c:573-587 (webm.h; the reference reads WebM through its bundled
  * nestegg).  Headerless raw input is not provided.
  */
@@ -36,6 +38,12 @@ static void usage_exit(void)
             "      --deblock         Enable VP8 deblocking\n"
             "      --demacroblock-level=<arg>  Enable VP8 demacroblocking, w/ level\n"
             "      --noise-level=<arg>         Enable VP8 postproc add noise\n"
+            "      --mfqe            Enable multiframe quality enhancement\n"
+            "      --pp-debug-info=<arg>       Enable VP8 visible debug info\n"
+            "      --pp-dbg-ref-frame=<arg>    Display only selected reference frame per macro block\n"
+            "      --pp-dbg-mb-modes=<arg>     Display only selected macro block modes\n"
+            "      --pp-dbg-b-modes=<arg>      Display only selected block modes\n"
+            "      --pp-dbg-mvs=<arg>          Draw only selected motion vectors\n"
             "      --progress        Show progress after each frame decodes\n"
             "      --limit=<arg>     Stop decoding after n frames\n"
             "      --skip=<arg>      Skip the first n input frames\n"
@@ -75,6 +83,11 @@ int main(int argc, char **argv)
     int use_y4m_order = 0, flipuv = 0, noblit = 0, do_md5 = 0, progress = 0, summary = 0, verbose = 0;
     int stop_after = 0, skip = 0, frame_in = 0, frame_out = 0, frames_corrupted = 0, rc, postproc = 0;
     vp8_postproc_cfg_t pp_cfg = { 0, 0, 0 };
+    /* VP8_SET_DBG_COLOR_REF_FRAME, _MB_MODES, _B_MODES, VP8_SET_DBG_DISPLAY_MV */
+    static const char *const dbg_opt[4] = { "--pp-dbg-ref-frame", "--pp-dbg-mb-modes", "--pp-dbg-b-modes", "--pp-dbg-mvs" };
+    static const int dbg_ctrl[4] = { VP8_SET_DBG_COLOR_REF_FRAME, VP8_SET_DBG_COLOR_MB_MODES, VP8_SET_DBG_COLOR_B_MODES,
+                                     VP8_SET_DBG_DISPLAY_MV };
+    int dbg[4] = { 0, 0, 0, 0 }, k;
     unsigned long dx_time = 0;
     vpx_codec_ctx_t decoder;
     vpx_codec_dec_cfg_t cfg = { 0, 0, 0 };
@@ -104,7 +117,20 @@ int main(int argc, char **argv)
             postproc = 1, pp_cfg.post_proc_flag |= VP8_ADDNOISE, pp_cfg.noise_level = atoi(v);
         else if ((v = optval(a, "--demacroblock-level", argv, &i, argc, NULL)))
             postproc = 1, pp_cfg.post_proc_flag |= VP8_DEMACROBLOCK, pp_cfg.deblocking_level = atoi(v);
-        else if ((v = optval(a, "--codec", argv, &i, argc, NULL))) {
+        else if ((v = optval(a, "--pp-debug-info", argv, &i, argc, NULL))) {
+            /* the level replaces the filter bits (vpxdec.c:813-822) */
+            const unsigned level = (unsigned)strtoul(v, NULL, 10);
+            postproc = 1;
+            pp_cfg.post_proc_flag &= ~0x7;
+            if (level) pp_cfg.post_proc_flag |= (int)level;
+        } else if (!strncmp(a, "--pp-dbg-", 9)) {
+            for (k = 0; k < 4 && !(v = optval(a, dbg_opt[k], argv, &i, argc, NULL)); k++) { }
+            if (k == 4) { fprintf(stderr, "Error: Unrecognized option %s\n", a); usage_exit(); }
+            {   /* a value of 0 is ignored (vpxdec.c:823-857) */
+                const int flags = (int)strtol(v, NULL, 10);
+                if (flags) postproc = 1, dbg[k] = flags;
+            }
+        } else if ((v = optval(a, "--codec", argv, &i, argc, NULL))) {
             if (strcmp(v, "vp8")) { fprintf(stderr, "Error: Unrecognized argument (%s) to --codec\n", v); return EXIT_FAILURE; }
         } else if ((v = optval(a, "--limit", argv, &i, argc, NULL))) stop_after = atoi(v);
         else if ((v = optval(a, "--skip", argv, &i, argc, NULL))) skip = atoi(v);
@@ -137,6 +163,11 @@ int main(int argc, char **argv)
         fprintf(stderr, "Failed to configure postproc: %s\n", vpx_codec_error(&decoder));
         return EXIT_FAILURE;
     }
+    for (k = 0; k < 4; k++)
+        if (dbg[k] && vpx_codec_control_(&decoder, dbg_ctrl[k], dbg[k])) {
+            fprintf(stderr, "Failed to configure %s: %s\n", dbg_opt[k] + 2, vpx_codec_error(&decoder));
+            return EXIT_FAILURE;
+        }
     if (verbose) fprintf(stderr, "%s\n", decoder.name);
 
 #define NEXT_FRAME() (is_webm ? webm_next(&wm, &buf, &buf_sz) : ivf_next(&in, &buf, &buf_sz))
