@@ -80,7 +80,8 @@ const char *vp8hip_last_error(const vp8hip_ctx *ctx);   /* ctx may be NULL: crea
 /* (Re)allocate device state for frames of width x height: num_fb frame buffers (vp8ir_geom layout, borders included) and
  * num_slots IR slots.  A slot holds one frame's macroblock data in the DEVICE FORM of include/vp8_ir.h (records, block stream
  * sized for the worst case, vectors: 960 bytes per macroblock) and gets pinned host staging of the same layout when it is first
- * mapped.  Existing contents are discarded. */
+ * mapped.  Existing contents are discarded, and so is input staged by vp8hip_entropy_stage and not launched (once its copy has
+ * finished reading the caller's memory). */
 int  vp8hip_configure(vp8hip_ctx *ctx, int width, int height, int num_fb, int num_slots);
 /* The same with the slots' block streams out of ONE pool.  The worst case a slot of vp8hip_configure is sized for -- 24 blocks a
  * macroblock, 768 of its 960 bytes per macroblock -- is rarely what a frame needs (a 1080p key frame of 200 KB: 62 k blocks = 2.0 of

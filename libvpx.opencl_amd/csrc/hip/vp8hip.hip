@@ -266,6 +266,7 @@ static int configure_pools(vp8hip_ctx *c, int width, int height, int num_fb, int
         return fail(c, -2, "vp8hip_configure: bad arguments %dx%d fb=%d slots=%d", width, height, num_fb, num_slots);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->stream_h2d) HIPCHK(c, hipStreamSynchronize(c->stream_h2d));    // (a staged input's copy may still read the caller's set)
     free_pools(c);
     c->ent_staged.count = 0;                 // (input staged for the geometry before: dropped)
     read_knobs(c->knobs);

@@ -22,10 +22,10 @@
  * flight (frames in flight over the time of the largest is what the entropy decoder's rate is; 24,576 is what the device holds
  * at once, vp8hip_entropy.hip).  The E slots hold records and vectors only and the blocks of a launch come out of ONE pool
  * (vp8hip_configure_pooled; --pool-mb M sets its size, by default what the largest launch is expected to need; a launch that finds
- * the pool empty ends the attempt, and the work is run again with twice the pool, up to three times: pooled_attempts): a frame in
- * flight costs what it needs, not the worst case.  With --no-download the launch's frames are hashed in one go (E frame buffers,
- * as tiles), beside the next launch of the entropy decoder.  Frames the device reports as cut short (vp8hip_entropy_status) are
- * counted and named on stderr, as the host feeder's *corrupt would.
+ * the pool empty ends the attempt, run_pooled, and this process runs the work again with twice the pool, up to three times, then
+ * exits with status 75): a frame in flight costs what it needs, not the worst case.  With --no-download the launch's frames are
+ * hashed in one go (E frame buffers, as tiles), beside the next launch of the entropy decoder.  Frames the device reports as cut
+ * short (vp8hip_entropy_status) are counted and named on stderr, as the host feeder's *corrupt would.
  *
  * --streams S: S streams of ANY frame types decoded side by side, position t of all of them in one launch (stream s plays input
  * s mod inputs; all inputs of one frame size; the shortest sets the length): only the frame headers are read on the host, a
@@ -35,17 +35,20 @@
  * S > 1).  This is how inter-frame streams use the device's entropy decoder: a stream's frames depend on each other, streams do not.
  *
  * --gpus G: G worker processes, one per device (one feeder pool and one context each), over contiguous shares of the work --
- * frames of the looped stream, or streams --; the listings are merged in order.  VP8BATCH_SINGLE_DEVICE=1 (test boxes with one
- * GPU) puts every worker on device 0.
+ * frames of the looped stream, or streams --; the listings are merged in order.  A worker dies with the parent (a time limit or a
+ * Ctrl-C that ends the parent ends the workers).  VP8BATCH_SINGLE_DEVICE=1 (test boxes with one GPU) puts every worker on device 0.
  *
  * Prints frames, seconds and frames/s for the region "first byte parsed .. last digest done" on stderr. */
 #define _GNU_SOURCE
 #include <sched.h>
+#include <signal.h>
+#include <sys/prctl.h>
 #include <sys/wait.h>
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sysexits.h>
 #include <time.h>
 #include <unistd.h>
 #include "ivf.h"
@@ -102,6 +105,21 @@ static void task_wait(task *t, int slot)
     if (pool.slot[slot] == t) pool.slot[slot] = NULL;
     pthread_mutex_unlock(&pool.mu);
 }
+static pthread_t *start_feeders(int threads)
+{
+    pthread_t *tid = calloc((size_t)threads, sizeof *tid);
+    for (int t = 0; t < threads; t++) pthread_create(&tid[t], NULL, worker_main, (void *)(size_t)t);
+    return tid;
+}
+static void stop_feeders(pthread_t *tid, int threads)
+{
+    pthread_mutex_lock(&pool.mu);
+    pool.stop = 1;
+    pthread_cond_broadcast(&pool.work);
+    pthread_mutex_unlock(&pool.mu);
+    for (int t = 0; t < threads; t++) pthread_join(tid[t], NULL);
+    free(tid);
+}
 
 /* ---- the stream in memory -------------------------------------------------------------------------------------------- */
 typedef struct frame { uint8_t *data; size_t size; } frame;
@@ -143,11 +161,6 @@ static size_t g_ent_cap;
 static size_t g_pool_bytes;                         /* --entropy-batch: the block pool of the context */
 
 typedef struct batch_ref { int b, n; long first; } batch_ref;     /* batch number, frames in it, index of its first frame */
-/* The pipeline, batch by batch (three slot / frame-buffer sets, two pinned host sets):
- *   feeder threads   parse batch b+1 into slot set (b+1)%3            (the device form, include/vp8_ir.h)
- *   this thread      uploads batch b (one copy per frame), launches its pixel path, then asks for the
- *                    frames back: ONE asynchronous device-to-host copy of the whole batch on a stream of its own
- *   hash threads     MD5 of batch b-1, which that copy delivered during the previous iteration */
 
 static inline long run_index(long k) { return g_order ? g_order[k] : k; }
 static int by_size_desc(const void *pa, const void *pb)
@@ -216,47 +229,20 @@ static void take_digests(const batch_ref *br)
 {
     for (int i = 0; i < br->n; i++) memcpy(g_digest[run_index(br->first + i)], g_dig[br->b & 1] + 16 * (size_t)i, 16);
 }
-#define EXIT_POOL_STARVED 75         /* (pooled_attempts, below) */
-/* the status words of an entropy launch (set `set`, n frames from run position `first` on), once its copy has landed */
-static void take_status(int set, long first, int n)
+/* the status words of an entropy launch (set `set`, n frames from run position `first` on), once its copy has landed.  Returns 1 if
+   the launch found the block pool empty: its frames were decoded from half an IR, and nothing of the attempt is kept (run_pooled) */
+static int take_status(int set, long first, int n)
 {
     for (int i = 0; i < n; i++) {
         if (g_ent_status[set][i] & 2u) {
-            /* the launch's frames were decoded from half an IR: nothing of this attempt is kept -- the supervising process runs the
-               work again with twice the pool (pooled_attempts) */
             fprintf(stderr, "frame %ld found the block pool (%zu MB) empty\n", run_index(first + i) + 1, g_pool_bytes >> 20);
-            fflush(NULL);
-            _exit(EXIT_POOL_STARVED);
+            return 1;
         }
         if (g_ent_status[set][i] & 1u) {
             if (g_corrupt++ < 8) fprintf(stderr, "frame %ld: a partition ended early (corrupt)\n", run_index(first + i) + 1);
         }
     }
-}
-
-/* --entropy-batch: the block pool is sized from the stream (or by --pool-mb), and a launch that finds it empty has decoded some of
-   its frames from half an IR.  The work therefore runs in a CHILD process (forked before anything touches the device); a child that
-   ends with EXIT_POOL_STARVED is run again with twice the pool, up to three times.  Returns in the child, with the factor its pool
-   is to be scaled by; the parent never returns. */
-static size_t pooled_attempts(void)
-{
-    size_t scale = 1;
-    for (int attempt = 0; attempt < 4; attempt++, scale *= 2) {
-        fflush(NULL);
-        const pid_t pid = fork();
-        if (pid < 0) { fprintf(stderr, "fork failed\n"); exit(EXIT_FAILURE); }
-        if (pid == 0) return scale;
-        int st = 0;
-        if (waitpid(pid, &st, 0) < 0) { fprintf(stderr, "waitpid failed\n"); exit(EXIT_FAILURE); }
-        if (WIFEXITED(st) && WEXITSTATUS(st) == EXIT_POOL_STARVED && attempt < 3) {
-            fprintf(stderr, "the block pool was too small: decoding again with a pool %zu times the size\n", 2 * scale);
-            continue;
-        }
-        if (WIFEXITED(st) && WEXITSTATUS(st) == EXIT_POOL_STARVED)
-            fprintf(stderr, "the block pool is still too small at %zu times its size: raise --pool-mb or lower --entropy-batch\n", scale);
-        exit(WIFEXITED(st) ? WEXITSTATUS(st) : EXIT_FAILURE);
-    }
-    exit(EXIT_FAILURE);
+    return 0;
 }
 
 static double now_s(void)
@@ -269,6 +255,20 @@ static double now_s(void)
 #define DIE(...) do { fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); exit(EXIT_FAILURE); } while (0)
 #define HIP(call) do { if (call) DIE("%s: %s", #call, vp8hip_last_error(g_hip)); } while (0)
 
+static void open_device(void)
+{
+    const char *device = getenv("VP8HIP_DEVICE");
+    if (vp8hip_create(device ? atoi(device) : -1, &g_hip)) DIE("vp8hip_create: %s (no CPU fallback)", vp8hip_last_error(NULL));
+}
+
+/* decode_to_md5's lines for n digests, numbered from first + 1, each label behind `prefix` ("stream<s>/" for --streams S > 1) */
+static void write_listing(FILE *out, const unsigned char (*digest)[16], long n, long first, const char *prefix)
+{
+    for (long f = 0; f < n; f++) {
+        for (int i = 0; i < 16; i++) fprintf(out, "%02x", digest[f][i]);
+        fprintf(out, "  %simg-%dx%d-%04ld.i420\n", prefix, g_width, g_height, first + f + 1);
+    }
+}
 
 /* ---- --gpus: workers ------------------------------------------------------------------------------------------------------- */
 static const char *g_stat_path;                     /* a worker leaves "frames seconds" here for the parent */
@@ -301,11 +301,15 @@ static int fork_workers(int G, long total, long *lo, long *hi, const char *out_p
     if (G > 64) G = 64;
     if (G > total) G = (int)total;
     const double t0 = now_s();
+    const pid_t parent = getpid();
     for (int g = 0; g < G; g++) {
         fflush(NULL);
         pid[g] = fork();
         if (pid[g] < 0) DIE("fork failed");
         if (pid[g] == 0) {
+            /* a worker dies with the parent: SIGKILL when the thread that forked ends -- the main thread, no other exists yet --,
+               and a parent that is gone already shows in getppid */
+            if (prctl(PR_SET_PDEATHSIG, SIGKILL) || getppid() != parent) exit(EXIT_FAILURE);
             char dev[16];
             snprintf(dev, sizeof dev, "%d", getenv("VP8BATCH_SINGLE_DEVICE") ? 0 : g);
             setenv("VP8HIP_DEVICE", dev, 1);
@@ -405,9 +409,7 @@ static int run_streams(int S_total, int threads, int gpus, int argc, char **argv
     char part[4096] = "";
     if (gpus > 1) { fork_workers(gpus, S_total, &lo, &hi, out_path, part, sizeof part, "streams", (long)g_width * g_height); out_path = part; }
     const int S = (int)(hi - lo);
-    int device = -1;
-    if (getenv("VP8HIP_DEVICE")) device = atoi(getenv("VP8HIP_DEVICE"));
-    if (vp8hip_create(device, &g_hip)) DIE("vp8hip_create: %s (no CPU fallback)", vp8hip_last_error(NULL));
+    open_device();
     HIP(vp8hip_configure(g_hip, g_width, g_height, 4 * S, S));
     st.in = in; st.nin = nin; st.S = S; st.s0 = lo;
     st.parser = calloc((size_t)S, sizeof *st.parser); st.refs = calloc((size_t)S, sizeof *st.refs);
@@ -432,8 +434,7 @@ static int run_streams(int S_total, int threads, int gpus, int argc, char **argv
         vp8_parser_set_device_segmap(st.parser[s], 1);
         vp8_refs_init(&st.refs[s]);
     }
-    pthread_t *tid = calloc((size_t)threads, sizeof *tid);
-    for (int t = 0; t < threads; t++) pthread_create(&tid[t], NULL, worker_main, (void *)(size_t)t);
+    pthread_t *tid = start_feeders(threads);
     unsigned char (*digest)[16] = calloc((size_t)S * (size_t)T, 16);     /* [stream][shown frame] */
     int *nshown = calloc((size_t)S, sizeof(int));
     vp8hip_job *jobs = calloc((size_t)S, sizeof *jobs);
@@ -484,291 +485,141 @@ static int run_streams(int S_total, int threads, int gpus, int argc, char **argv
     const double dt = now_s() - t0;
     FILE *out = fopen(out_path, "wb");
     if (!out) DIE("Failed to open %s for writing", out_path);
-    for (int s = 0; s < S; s++)
-        for (int k = 0; k < nshown[s]; k++) {
-            for (int i = 0; i < 16; i++) fprintf(out, "%02x", digest[(size_t)s * T + k][i]);
-            if (S_total > 1) fprintf(out, "  stream%ld/img-%dx%d-%04d.i420\n", lo + s, g_width, g_height, k + 1);
-            else fprintf(out, "  img-%dx%d-%04d.i420\n", g_width, g_height, k + 1);
-        }
+    for (int s = 0; s < S; s++) {
+        char prefix[32] = "";
+        if (S_total > 1) snprintf(prefix, sizeof prefix, "stream%ld/", lo + s);
+        write_listing(out, digest + (size_t)s * T, nshown[s], 0, prefix);
+    }
     fclose(out);
     fprintf(stderr, "%ld frames in %.3f s: %.1f frames/s, %.1f Mpix/s (%d streams of %d frames side by side, %d feeder threads, entropy decode on the device, MD5 on the device; %ld corrupt)\n",
             frames, dt, frames / dt, frames / dt * g_width * g_height / 1e6, S, T, threads, corrupt);
     leave_stats(frames, dt);
-    pthread_mutex_lock(&pool.mu);
-    pool.stop = 1;
-    pthread_cond_broadcast(&pool.work);
-    pthread_mutex_unlock(&pool.mu);
-    for (int t = 0; t < threads; t++) pthread_join(tid[t], NULL);
+    stop_feeders(tid, threads);
     for (int s = 0; s < S; s++) vp8_parser_destroy(st.parser[s]);
     vp8hip_destroy(g_hip);
     return EXIT_SUCCESS;
 }
 
-int main(int argc, char **argv)
+/* the context for E frames per entropy launch, its block pool `bytes` -- at most what a pool can count: its blocks are numbered in
+   32 bits, 137 GB */
+static void configure_pooled(size_t bytes, int no_download)
 {
-    int threads = 0, loop = 1, a = 1, host_md5 = 0, no_download = 0, streams = 0, gpus = 1;
-    long pool_mb = 0;
-    g_batch = 128;
-    for (; a < argc && argv[a][0] == '-' && argv[a][1] == '-'; a++) {
-        if (!strcmp(argv[a], "--threads") && a + 1 < argc) threads = atoi(argv[++a]);
-        else if (!strcmp(argv[a], "--host-md5")) host_md5 = 1;          /* hash on the host whatever the frame size */
-        else if (!strcmp(argv[a], "--device-entropy")) g_dev_entropy = 1;
-        else if (!strcmp(argv[a], "--no-download")) no_download = 1;
-        else if (!strcmp(argv[a], "--entropy-batch") && a + 1 < argc) g_ebatch = atoi(argv[++a]);
-        else if (!strcmp(argv[a], "--entropy-dense")) ;                 /* (what --entropy-batch does anyway since the slots hold the compact form) */
-        else if (!strcmp(argv[a], "--pool-mb") && a + 1 < argc) pool_mb = atol(argv[++a]);
-        else if (!strcmp(argv[a], "--streams") && a + 1 < argc) streams = atoi(argv[++a]);
-        else if (!strcmp(argv[a], "--gpus") && a + 1 < argc) gpus = atoi(argv[++a]);
-        else if (!strcmp(argv[a], "--batch") && a + 1 < argc) g_batch = atoi(argv[++a]);
-        else if (!strcmp(argv[a], "--loop") && a + 1 < argc) loop = atoi(argv[++a]);
-        else DIE("Usage: %s [--threads T] [--batch B] [--loop N] [--host-md5] [--device-entropy [--entropy-batch E [--pool-mb M]] [--no-download]] <in.ivf> <out.md5>", argv[0]);
-    }
-    if (threads < 1) {
-        long n = sysconf(_SC_NPROCESSORS_ONLN);
-        threads = n > 33 ? 32 : (n > 2 ? (int)n - 1 : 1);      /* more than ~32 feeders gain nothing: the host memory system is the limit */
-        if (gpus > 1 && threads > 2 * gpus) threads = threads / gpus > 2 ? threads / gpus : 2;      /* a pool per device */
-    }
-    if (gpus < 1) gpus = 1;
-    if (streams > 0) return run_streams(streams, threads, gpus, argc, argv, a);
-    if (argc - a != 2 || g_batch < 1 || loop < 1)
-        DIE("Usage: %s [--threads T] [--batch B] [--loop N] [--host-md5] [--device-entropy [--entropy-batch E [--pool-mb M]] [--no-download]] [--gpus G] <in.ivf> <out.md5>\n"
-            "       %s --streams S [--threads T] [--gpus G] <in.ivf> [<in2.ivf> ...] <out.md5>", argv[0], argv[0]);
+    const size_t chunk = (size_t)4 * ((g_width + 15) / 16) * 24 * 32;
+    const size_t most = ((size_t)0xffffffffu / (chunk / 32) - 1) * chunk;
+    g_pool_bytes = bytes < most ? bytes : most;
+    /* frames that stay on the device are hashed a launch at a time (E frame buffers, tiles only); downloads go B at a time */
+    HIP(vp8hip_configure_pooled(g_hip, g_width, g_height, no_download ? g_ebatch : 2 * g_batch, g_ebatch, g_pool_bytes));
+    HIP(vp8hip_geometry(g_hip, &g_geom));
+}
 
-    /* ---- read the whole stream; every frame must be a key frame of one size */
-    ivf_reader in;
-    const uint8_t *data; size_t size; int rc, cap = 0;
-    if (ivf_open(&in, argv[a])) DIE("%s is not an IVF file.", argv[a]);
-    while ((rc = ivf_next(&in, &data, &size)) == 1) {
-        int key, w, h;
-        if (g_nframes == cap) { cap = cap ? 2 * cap : 64; g_frames = (frame *)realloc(g_frames, sizeof(frame) * cap); }
-        if (vp8_parser_peek(data, size, &key, &w, &h) || !key)
-            DIE("frame %d is not a key frame: batch_md5 needs independently decodable frames (use decode_to_md5)", g_nframes + 1);
-        if (g_nframes == 0) { g_width = w; g_height = h; }
-        else if (w != g_width || h != g_height) DIE("frame %d changes the frame size (use decode_to_md5)", g_nframes + 1);
-        g_frames[g_nframes].data = (uint8_t *)malloc(size + 16);
-        memcpy(g_frames[g_nframes].data, data, size);
-        g_frames[g_nframes].size = size;
-        g_nframes++;
-    }
-    ivf_close(&in);
-    if (rc < 0 || !g_nframes) DIE("failed to read %s", argv[a]);
-    long total = (long)g_nframes * loop;
-    const char *out_path = argv[a + 1];
-    char part[4096] = "";
-    if (gpus > 1) {
-        long lo = 0, hi = total;
-        fork_workers(gpus, total, &lo, &hi, out_path, part, sizeof part, "frames", (long)g_width * g_height);
-        g_first = lo; total = hi - lo; out_path = part;
-    }
-    if (g_batch > total) g_batch = (int)total;
-    if (g_ebatch && (!g_dev_entropy || g_ebatch < g_batch || g_ebatch % g_batch)) DIE("--entropy-batch goes with --device-entropy and is a multiple of --batch");
-    if (g_ebatch == g_batch) g_ebatch = 0;
-    const int unit = g_ebatch ? g_ebatch : g_batch;            /* frames per entropy launch */
-
-    /* ---- device and host state */
-    const size_t pool_scale = g_ebatch ? pooled_attempts() : 1;
-    int device = -1;
-    if (getenv("VP8HIP_DEVICE")) device = atoi(getenv("VP8HIP_DEVICE"));
-    if (vp8hip_create(device, &g_hip)) DIE("vp8hip_create: %s (no CPU fallback)", vp8hip_last_error(NULL));
-    g_dev_md5 = !host_md5;
-    if (g_ebatch && !g_dev_md5) DIE("--entropy-batch needs the MD5s computed on the device (no --host-md5)");
-    if (no_download && !g_dev_md5) DIE("--no-download needs the MD5s computed on the device (no --host-md5)");
-    /* slots and frame buffers: three sets for the host feeder (parsed / on the GPU / coming back); with the entropy decoder on
-       the device the IR is written and read on one stream, one set does, and the frame buffers alternate between two */
-    const int slot_sets = g_dev_entropy ? 1 : 3, fb_sets = g_dev_entropy ? 2 : 3;
-    if (!g_ebatch) {
-        HIP(vp8hip_configure(g_hip, g_width, g_height, fb_sets * g_batch, slot_sets * g_batch));
-        HIP(vp8hip_geometry(g_hip, &g_geom));
-    }
-    if (g_dev_entropy) {
-        {   /* a batch's bytes at most: the frames are taken in order of size within windows of SORT_WINDOW batches */
-            g_order = (long *)malloc(sizeof(long) * (size_t)total);
-            for (long k = 0; k < total; k++) g_order[k] = k;
-            /* (whole launches: a launch that straddles two windows would get the smallest frames of one and the largest of the next) */
-            long window = ((long)SORT_WINDOW * g_batch + unit - 1) / unit * unit;
-            if (window < 4L * unit) window = 4L * unit;
-            for (long w0 = 0; w0 < total; w0 += window) {
-                const long wn = total - w0 < window ? total - w0 : window;
-                qsort(g_order + w0, (size_t)wn, sizeof(long), by_size_desc);
-            }
-            for (long k0 = 0; k0 < total; k0 += unit) {
-                size_t run = 0;
-                for (long k = k0; k < k0 + unit && k < total; k++) run += FRAME_AT(g_order[k])->size;
-                if (run > g_ent_cap) g_ent_cap = run;
-            }
-        }
-        if (g_ebatch) {
-            /* E frames per entropy launch: E slots without block streams of their own and ONE pool for the blocks of a launch
-               (vp8hip_configure_pooled) -- a frame in flight costs what it needs (records 192 bytes a macroblock + its blocks), not
-               the worst case (960), and frames in flight are what the entropy decoder's rate is made of.  The pool: what the
-               launch that needs most is expected to need -- a frame's blocks are 6 to 13 times its compressed bytes in the
-               fixtures: 14 times, capped by the worst case; / 0.75, because the kernel leaves a chunk as soon as what is left of it
-               would not hold a macroblock row's WORST case (a quarter of a chunk; real rows take a third of that), + two chunks per
-               frame for the chunks a frame begins and ends in. */
-            const size_t nmb = (size_t)((g_width + 15) / 16) * (size_t)((g_height + 15) / 16);
-            const size_t worst = nmb * 24 * 32, chunk = (size_t)4 * ((g_width + 15) / 16) * 24 * 32;
-            size_t pool = 0;
-            for (long k0 = 0; k0 < total; k0 += unit) {
-                size_t need = 0;
-                for (long k = k0; k < k0 + unit && k < total; k++) {
-                    const size_t est = 14 * FRAME_AT(g_order[k])->size;
-                    need += (est < worst ? est : worst) * 4 / 3 + 2 * chunk;
-                }
-                if (need > pool) pool = need;
-            }
-            pool += 4 * chunk;
-            {   /* (a pool counts its blocks in 32 bits: 137 GB at most) */
-                const size_t most = ((size_t)0xffffffffu / (chunk / 32) - 1) * chunk;
-                if (pool > most) pool = most;
-            }
-            if (pool_mb > 0) pool = (size_t)pool_mb << 20;
-            pool *= pool_scale;                      /* (an attempt after one that found the pool empty: pooled_attempts) */
-            {
-                const size_t most = ((size_t)0xffffffffu / (chunk / 32) - 1) * chunk;
-                if (pool > most) pool = most;
-            }
-            g_pool_bytes = pool;
-            /* frames that stay on the device are hashed a launch at a time (E frame buffers, tiles only); downloads go B at a time */
-            HIP(vp8hip_configure_pooled(g_hip, g_width, g_height, no_download ? g_ebatch : 2 * g_batch, g_ebatch, pool));
-            HIP(vp8hip_geometry(g_hip, &g_geom));
-        }
-        for (int k = 0; k < 3; k++) {
-            if (!(g_ent[k] = (vp8hip_entropy_frame *)vp8hip_host_alloc(g_hip, (size_t)unit * sizeof(vp8hip_entropy_frame))) ||
-                !(g_ent_data[k] = (uint8_t *)vp8hip_host_alloc(g_hip, g_ent_cap + 16)) ||
-                !(g_ent_status[k] = (uint32_t *)vp8hip_host_alloc(g_hip, (size_t)unit * sizeof(uint32_t)))) DIE("vp8hip_host_alloc: %s", vp8hip_last_error(g_hip));
-        }
-    } else {
-        g_maps = calloc((size_t)3 * g_batch, sizeof *g_maps);
-        for (int s = 0; s < 3 * g_batch; s++)
-            HIP(vp8hip_ir_map_compact(g_hip, s, &g_maps[s].hdr, &g_maps[s].mbx, &g_maps[s].blocks, &g_maps[s].cap, &g_maps[s].mvs));
-    }
-    g_stride = vp8hip_frame_stride(g_hip);
-    g_packed = g_dev_md5 && !no_download && g_width % 8 == 0 && !getenv("VP8BATCH_WHOLE_BUFFERS");
-    if (g_packed) g_stride = vp8hip_i420_bytes(g_hip);
-    for (int k = 0; k < 2; k++) {
-        if (!no_download && !(g_host[k] = (uint8_t *)vp8hip_host_alloc(g_hip, (size_t)g_batch * g_stride))) DIE("vp8hip_host_alloc: %s", vp8hip_last_error(g_hip));
-        if (!(g_dig[k] = (uint8_t *)vp8hip_host_alloc(g_hip, (size_t)(g_ebatch && no_download ? g_ebatch : g_batch) * 16))) DIE("vp8hip_host_alloc: %s", vp8hip_last_error(g_hip));
-    }
-    g_digest = calloc((size_t)total, 16);
-    g_parsers = calloc((size_t)threads, sizeof *g_parsers);
-    pthread_t *tid = calloc((size_t)threads, sizeof *tid);
-    for (int t = 0; t < threads; t++) {
-        if (!(g_parsers[t] = vp8_parser_create())) DIE("out of memory");
-        pthread_create(&tid[t], NULL, worker_main, (void *)(size_t)t);
-    }
-    vp8hip_job *jobs = calloc((size_t)g_batch, sizeof *jobs);
-
-    if (g_ebatch) {
-        /* ---- the pipeline with the entropy decoder on the device in launches of up to E frames, the pixel path B at a time:
-           headers of launch L+1 on the host while launch L is on the GPU; per part of a launch: decode, digests back. */
+/* ---- --entropy-batch: one attempt with the block pool as configured ----------------------------------------------------------------
+   The entropy decoder on the device in launches of up to E frames, the pixel path B at a time: headers of launch L+1 on the host while
+   launch L is on the GPU; per part of a launch: decode, digests back.  Returns 0 with every digest in g_digest and *dt the attempt's
+   time, or 1 as soon as a launch's status shows it found the pool empty: the feeder is idle then, the device may not be (main). */
+static int run_pooled(vp8hip_job *jobs, long total, int no_download, double *dt)
+{
 #define LAUNCH_FRAMES(first, n_out) do { (n_out) = (int)(total - (first) < g_ebatch ? total - (first) : g_ebatch); } while (0)
-        task parse_t;
-        batch_ref cur = { 0, 0, 0 }, prev = { -1, 0, 0 };
-        long part_no = 0, L = 0, prev_launch = -1;
-        /* the status words of a launch are good once a fetch queued behind their copy has come back: any part of that launch */
-        struct { int valid, n; long first, launch; } pend[3] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
+    task parse_t;
+    batch_ref cur = { 0, 0, 0 }, prev = { -1, 0, 0 };
+    long part_no = 0, L = 0, prev_launch = -1;
+    /* the status words of a launch are good once a fetch queued behind their copy has come back: any part of that launch */
+    struct { int valid, n; long first, launch; } pend[3] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
 #define TAKE_PENDING() do { for (int k_ = 0; k_ < 3; k_++) if (pend[k_].valid && pend[k_].launch <= prev_launch) {          \
-                                take_status(k_, pend[k_].first, pend[k_].n); pend[k_].valid = 0; } } while (0)
-        const double t0 = now_s();
-        LAUNCH_FRAMES(0, cur.n);
-        size_t bytes = place_frames(&cur), next_bytes = 0;
-        task_start(&parse_t, 0, export_one, &cur, cur.n);
-        batch_ref prev_launch_ref = { -1, 0, 0 };
-        const int late_stage = getenv("VP8BATCH_LATE_STAGE") != NULL;      /* (experiments: a launch's input is sent when the launch is queued) */
-        const int trace = getenv("VP8BATCH_TRACE") != NULL;          /* where the main thread's time goes, launch by launch */
-        for (long done = 0; done < total; L++) {
-            if (L == 0 || late_stage) {           /* (every later launch's input was sent while the launch before it was being queued: below) */
-                task_wait(&parse_t, 0);
-                if (g_failed) DIE("a frame of launch %ld failed to parse", L);
-                HIP(vp8hip_entropy_stage(g_hip, cur.n, g_ent[ESET(cur.b)], g_ent_data[ESET(cur.b)], L == 0 ? bytes : next_bytes));
-            }
-            if (trace) fprintf(stderr, "launch %ld: at %.3f s\n", L, now_s() - t0);
-            const batch_ref now = cur;
-            done += now.n;
-            const int have_next = done < total;
-            if (have_next) {
-                /* the headers of the next launch, at once: its page-locked set (one of three) belonged to launch L - 2, whose digests
-                   came back an iteration ago -- the feeder threads work while this thread queues launch L and the device runs it */
-                const long first = cur.first + cur.n;
-                cur.b = cur.b + 1; cur.first = first;
-                LAUNCH_FRAMES(first, cur.n);
-                next_bytes = place_frames(&cur);
-                task_start(&parse_t, 0, export_one, &cur, cur.n);
-            }
-            HIP(vp8hip_pool_reset(g_hip));               /* (on the stream: behind the pixel path of the launch before) */
-            HIP(vp8hip_entropy_decode(g_hip, 0, now.n, NULL, NULL, 0));      /* (the kernel over the input staged before) */
-            HIP(vp8hip_entropy_status_async(g_hip, now.n, g_ent_status[ESET(now.b)]));
-            if (L == 0) HIP(vp8hip_reserve(g_hip, 1, !no_download && !g_packed));     /* (the frame buffers' pools, while the first launch runs) */
-            pend[ESET(now.b)].valid = 1; pend[ESET(now.b)].n = now.n; pend[ESET(now.b)].first = now.first; pend[ESET(now.b)].launch = L;
-            for (int at = 0; at < now.n; at += g_batch, part_no++) {
-                const batch_ref part = { (int)(part_no & 0x3fffffff), now.n - at < g_batch ? now.n - at : g_batch, now.first + at };
-                const int fb0 = no_download ? at : (part.b & 1) * g_batch;
-                for (int i = 0; i < part.n; i++) {
-                    jobs[i].ir_slot = at + i; jobs[i].dst_fb = fb0 + i;
-                    jobs[i].ref_fb[0] = jobs[i].ref_fb[1] = jobs[i].ref_fb[2] = jobs[i].ref_fb[3] = -1;
-                }
-                const double td0 = now_s();
-                HIP(vp8hip_decode(g_hip, jobs, part.n, VP8HIP_STAGE_ALL));
-                if (trace) fprintf(stderr, "launch %ld: vp8hip_decode of part %d took the host %.3f s\n", L, at / g_batch, now_s() - td0);
-                if (no_download) continue;
-                if (prev.b >= 0) {
-                    HIP(vp8hip_download_wait(g_hip));
-                    take_digests(&prev);
-                    TAKE_PENDING();
-                }
-                HIP((g_packed ? vp8hip_frames_fetch_i420_async : vp8hip_frames_fetch_async)(g_hip, fb0, part.n, g_host[part.b & 1], g_dig[part.b & 1]));
-                prev = part; prev_launch = L;
-            }
-            if (have_next && !late_stage) {
-                /* the next launch's input on its way now -- checked, and copied on the entropy decoder's copy stream while the
-                   device is busy with this launch; its kernel is launched at the top of the next iteration */
-                const double tw0 = now_s();
-                task_wait(&parse_t, 0);
-                if (g_failed) DIE("a frame of launch %ld failed to parse", L + 1);
-                HIP(vp8hip_entropy_stage(g_hip, cur.n, g_ent[ESET(cur.b)], g_ent_data[ESET(cur.b)], next_bytes));
-                if (trace) fprintf(stderr, "launch %ld: waited %.3f s for the next launch's headers, %.2f GB staged\n", L, now_s() - tw0, next_bytes / 1e9);
-            }
-            if (no_download) {
-                /* the frames stay: ONE hash launch over the launch's frames, on the download stream -- beside the entropy decoder's
-                   next launch, which is most of the time.  The launch before has come back by now: its page-locked set is free
-                   for the headers of the next one */
-                if (prev_launch_ref.b >= 0) {
-                    const double tw1 = now_s();
-                    HIP(vp8hip_download_wait(g_hip));
-                    if (trace) fprintf(stderr, "launch %ld: queued at %.3f s, waited %.3f s for the digests of the launch before\n", L, tw1 - t0, now_s() - tw1);
-                    take_digests(&prev_launch_ref);
-                    prev_launch = L - 1;
-                    TAKE_PENDING();
-                }
-                HIP(vp8hip_frames_fetch_async(g_hip, 0, now.n, NULL, g_dig[now.b & 1]));
-                prev_launch_ref = now; prev = now; prev_launch = L;
-            }
+                                if (take_status(k_, pend[k_].first, pend[k_].n)) goto starved;                           \
+                                pend[k_].valid = 0; } } while (0)
+    const double t0 = now_s();
+    LAUNCH_FRAMES(0, cur.n);
+    size_t bytes = place_frames(&cur), next_bytes = 0;
+    task_start(&parse_t, 0, export_one, &cur, cur.n);
+    batch_ref prev_launch_ref = { -1, 0, 0 };
+    const int late_stage = getenv("VP8BATCH_LATE_STAGE") != NULL;      /* (experiments: a launch's input is sent when the launch is queued) */
+    const int trace = getenv("VP8BATCH_TRACE") != NULL;          /* where the main thread's time goes, launch by launch */
+    for (long done = 0; done < total; L++) {
+        if (L == 0 || late_stage) {           /* (every later launch's input was sent while the launch before it was being queued: below) */
+            task_wait(&parse_t, 0);
+            if (g_failed) DIE("a frame of launch %ld failed to parse", L);
+            HIP(vp8hip_entropy_stage(g_hip, cur.n, g_ent[ESET(cur.b)], g_ent_data[ESET(cur.b)], L == 0 ? bytes : next_bytes));
         }
-        HIP(vp8hip_download_wait(g_hip));
-        take_digests(&prev);
-        TAKE_PENDING();
-        const double dt = now_s() - t0;
-        FILE *out = fopen(out_path, "wb");
-        if (!out) DIE("Failed to open %s for writing", out_path);
-        for (long f = 0; f < total; f++) {
-            for (int i = 0; i < 16; i++) fprintf(out, "%02x", g_digest[f][i]);
-            fprintf(out, "  img-%dx%d-%04ld.i420\n", g_width, g_height, g_first + f + 1);
+        if (trace) fprintf(stderr, "launch %ld: at %.3f s\n", L, now_s() - t0);
+        const batch_ref now = cur;
+        done += now.n;
+        const int have_next = done < total;
+        if (have_next) {
+            /* the headers of the next launch, at once: its page-locked set (one of three) belonged to launch L - 2, whose digests
+               came back an iteration ago -- the feeder threads work while this thread queues launch L and the device runs it */
+            const long first = cur.first + cur.n;
+            cur.b = cur.b + 1; cur.first = first;
+            LAUNCH_FRAMES(first, cur.n);
+            next_bytes = place_frames(&cur);
+            task_start(&parse_t, 0, export_one, &cur, cur.n);
         }
-        fclose(out);
-        fprintf(stderr, "%ld frames in %.3f s: %.1f frames/s, %.1f Mpix/s (%d feeder threads, %d frames per launch, entropy decode on the %s, MD5 on the %s%s; %d frames per entropy launch; %ld corrupt)\n",
-                total, dt, total / dt, total / dt * g_width * g_height / 1e6, threads, g_batch, "device", "device",
-                no_download ? ", frames not downloaded" : "", g_ebatch, g_corrupt);
-        leave_stats(total, dt);
-        pthread_mutex_lock(&pool.mu);
-        pool.stop = 1;
-        pthread_cond_broadcast(&pool.work);
-        pthread_mutex_unlock(&pool.mu);
-        for (int t = 0; t < threads; t++) { pthread_join(tid[t], NULL); vp8_parser_destroy(g_parsers[t]); }
-        vp8hip_destroy(g_hip);
-        return EXIT_SUCCESS;
+        HIP(vp8hip_pool_reset(g_hip));               /* (on the stream: behind the pixel path of the launch before) */
+        HIP(vp8hip_entropy_decode(g_hip, 0, now.n, NULL, NULL, 0));      /* (the kernel over the input staged before) */
+        HIP(vp8hip_entropy_status_async(g_hip, now.n, g_ent_status[ESET(now.b)]));
+        if (L == 0) HIP(vp8hip_reserve(g_hip, 1, !no_download && !g_packed));     /* (the frame buffers' pools, while the first launch runs) */
+        pend[ESET(now.b)].valid = 1; pend[ESET(now.b)].n = now.n; pend[ESET(now.b)].first = now.first; pend[ESET(now.b)].launch = L;
+        for (int at = 0; at < now.n; at += g_batch, part_no++) {
+            const batch_ref part = { (int)(part_no & 0x3fffffff), now.n - at < g_batch ? now.n - at : g_batch, now.first + at };
+            const int fb0 = no_download ? at : (part.b & 1) * g_batch;
+            for (int i = 0; i < part.n; i++) {
+                jobs[i].ir_slot = at + i; jobs[i].dst_fb = fb0 + i;
+                jobs[i].ref_fb[0] = jobs[i].ref_fb[1] = jobs[i].ref_fb[2] = jobs[i].ref_fb[3] = -1;
+            }
+            const double td0 = now_s();
+            HIP(vp8hip_decode(g_hip, jobs, part.n, VP8HIP_STAGE_ALL));
+            if (trace) fprintf(stderr, "launch %ld: vp8hip_decode of part %d took the host %.3f s\n", L, at / g_batch, now_s() - td0);
+            if (no_download) continue;
+            if (prev.b >= 0) {
+                HIP(vp8hip_download_wait(g_hip));
+                take_digests(&prev);
+                TAKE_PENDING();
+            }
+            HIP((g_packed ? vp8hip_frames_fetch_i420_async : vp8hip_frames_fetch_async)(g_hip, fb0, part.n, g_host[part.b & 1], g_dig[part.b & 1]));
+            prev = part; prev_launch = L;
+        }
+        if (have_next && !late_stage) {
+            /* the next launch's input on its way now -- checked, and copied on the entropy decoder's copy stream while the
+               device is busy with this launch; its kernel is launched at the top of the next iteration */
+            const double tw0 = now_s();
+            task_wait(&parse_t, 0);
+            if (g_failed) DIE("a frame of launch %ld failed to parse", L + 1);
+            HIP(vp8hip_entropy_stage(g_hip, cur.n, g_ent[ESET(cur.b)], g_ent_data[ESET(cur.b)], next_bytes));
+            if (trace) fprintf(stderr, "launch %ld: waited %.3f s for the next launch's headers, %.2f GB staged\n", L, now_s() - tw0, next_bytes / 1e9);
+        }
+        if (no_download) {
+            /* the frames stay: ONE hash launch over the launch's frames, on the download stream -- beside the entropy decoder's
+               next launch, which is most of the time.  The launch before has come back by now: its page-locked set is free
+               for the headers of the next one */
+            if (prev_launch_ref.b >= 0) {
+                const double tw1 = now_s();
+                HIP(vp8hip_download_wait(g_hip));
+                if (trace) fprintf(stderr, "launch %ld: queued at %.3f s, waited %.3f s for the digests of the launch before\n", L, tw1 - t0, now_s() - tw1);
+                take_digests(&prev_launch_ref);
+                prev_launch = L - 1;
+                TAKE_PENDING();
+            }
+            HIP(vp8hip_frames_fetch_async(g_hip, 0, now.n, NULL, g_dig[now.b & 1]));
+            prev_launch_ref = now; prev = now; prev_launch = L;
+        }
     }
+    HIP(vp8hip_download_wait(g_hip));
+    take_digests(&prev);
+    TAKE_PENDING();
+    *dt = now_s() - t0;
+    return 0;
+starved:
+    task_wait(&parse_t, 0);                     /* (the feeder may still be writing the next launch's input) */
+    return 1;
+}
 
-    /* ---- the pipeline */
+/* ---- the pipeline, batch by batch (three slot / frame-buffer sets, two pinned host sets); returns its time:
+ *   feeder threads   parse batch b+1 into slot set (b+1)%3            (the device form, include/vp8_ir.h)
+ *   this thread      uploads batch b (one copy per frame), launches its pixel path, then asks for the
+ *                    frames back: ONE asynchronous device-to-host copy of the whole batch on a stream of its own
+ *   hash threads     MD5 of batch b-1, which that copy delivered during the previous iteration
+ * (--device-entropy: no block pool, take_status never finds one empty) */
+static double run_batches(vp8hip_job *jobs, long total, int no_download)
+{
     const long nbatch = (total + g_batch - 1) / g_batch;
     task parse_t, hash_t;
     batch_ref cur = { 0, (int)(total < g_batch ? total : g_batch), 0 }, nxt, prev = { -1, 0, 0 }, hashing = { -1, 0, 0 };
@@ -833,31 +684,179 @@ int main(int argc, char **argv)
         task_start(&hash_t, 1, hash_one, &hashing, hashing.n);
         task_wait(&hash_t, 1);
     }
-    const double dt = now_s() - t0;
+    return now_s() - t0;
+}
+
+int main(int argc, char **argv)
+{
+    int threads = 0, loop = 1, a = 1, host_md5 = 0, no_download = 0, streams = 0, gpus = 1;
+    long pool_mb = 0;
+    g_batch = 128;
+    for (; a < argc && argv[a][0] == '-' && argv[a][1] == '-'; a++) {
+        if (!strcmp(argv[a], "--threads") && a + 1 < argc) threads = atoi(argv[++a]);
+        else if (!strcmp(argv[a], "--host-md5")) host_md5 = 1;          /* hash on the host whatever the frame size */
+        else if (!strcmp(argv[a], "--device-entropy")) g_dev_entropy = 1;
+        else if (!strcmp(argv[a], "--no-download")) no_download = 1;
+        else if (!strcmp(argv[a], "--entropy-batch") && a + 1 < argc) g_ebatch = atoi(argv[++a]);
+        else if (!strcmp(argv[a], "--entropy-dense")) ;                 /* (what --entropy-batch does anyway since the slots hold the compact form) */
+        else if (!strcmp(argv[a], "--pool-mb") && a + 1 < argc) pool_mb = atol(argv[++a]);
+        else if (!strcmp(argv[a], "--streams") && a + 1 < argc) streams = atoi(argv[++a]);
+        else if (!strcmp(argv[a], "--gpus") && a + 1 < argc) gpus = atoi(argv[++a]);
+        else if (!strcmp(argv[a], "--batch") && a + 1 < argc) g_batch = atoi(argv[++a]);
+        else if (!strcmp(argv[a], "--loop") && a + 1 < argc) loop = atoi(argv[++a]);
+        else DIE("Usage: %s [--threads T] [--batch B] [--loop N] [--host-md5] [--device-entropy [--entropy-batch E [--pool-mb M]] [--no-download]] <in.ivf> <out.md5>", argv[0]);
+    }
+    if (threads < 1) {
+        long n = sysconf(_SC_NPROCESSORS_ONLN);
+        threads = n > 33 ? 32 : (n > 2 ? (int)n - 1 : 1);      /* more than ~32 feeders gain nothing: the host memory system is the limit */
+        if (gpus > 1 && threads > 2 * gpus) threads = threads / gpus > 2 ? threads / gpus : 2;      /* a pool per device */
+    }
+    if (gpus < 1) gpus = 1;
+    if (streams > 0) return run_streams(streams, threads, gpus, argc, argv, a);
+    if (argc - a != 2 || g_batch < 1 || loop < 1)
+        DIE("Usage: %s [--threads T] [--batch B] [--loop N] [--host-md5] [--device-entropy [--entropy-batch E [--pool-mb M]] [--no-download]] [--gpus G] <in.ivf> <out.md5>\n"
+            "       %s --streams S [--threads T] [--gpus G] <in.ivf> [<in2.ivf> ...] <out.md5>", argv[0], argv[0]);
+
+    /* ---- read the whole stream; every frame must be a key frame of one size */
+    ivf_reader in;
+    const uint8_t *data; size_t size; int rc, cap = 0;
+    if (ivf_open(&in, argv[a])) DIE("%s is not an IVF file.", argv[a]);
+    while ((rc = ivf_next(&in, &data, &size)) == 1) {
+        int key, w, h;
+        if (g_nframes == cap) { cap = cap ? 2 * cap : 64; g_frames = (frame *)realloc(g_frames, sizeof(frame) * cap); }
+        if (vp8_parser_peek(data, size, &key, &w, &h) || !key)
+            DIE("frame %d is not a key frame: batch_md5 needs independently decodable frames (use decode_to_md5)", g_nframes + 1);
+        if (g_nframes == 0) { g_width = w; g_height = h; }
+        else if (w != g_width || h != g_height) DIE("frame %d changes the frame size (use decode_to_md5)", g_nframes + 1);
+        g_frames[g_nframes].data = (uint8_t *)malloc(size + 16);
+        memcpy(g_frames[g_nframes].data, data, size);
+        g_frames[g_nframes].size = size;
+        g_nframes++;
+    }
+    ivf_close(&in);
+    if (rc < 0 || !g_nframes) DIE("failed to read %s", argv[a]);
+    long total = (long)g_nframes * loop;
+    const char *out_path = argv[a + 1];
+    char part[4096] = "";
+    if (gpus > 1) {
+        long lo = 0, hi = total;
+        fork_workers(gpus, total, &lo, &hi, out_path, part, sizeof part, "frames", (long)g_width * g_height);
+        g_first = lo; total = hi - lo; out_path = part;
+    }
+    if (g_batch > total) g_batch = (int)total;
+    if (g_ebatch && (!g_dev_entropy || g_ebatch < g_batch || g_ebatch % g_batch)) DIE("--entropy-batch goes with --device-entropy and is a multiple of --batch");
+    if (g_ebatch == g_batch) g_ebatch = 0;
+    const int unit = g_ebatch ? g_ebatch : g_batch;            /* frames per entropy launch */
+
+    /* ---- device and host state */
+    open_device();
+    g_dev_md5 = !host_md5;
+    if (g_ebatch && !g_dev_md5) DIE("--entropy-batch needs the MD5s computed on the device (no --host-md5)");
+    if (no_download && !g_dev_md5) DIE("--no-download needs the MD5s computed on the device (no --host-md5)");
+    /* slots and frame buffers: three sets for the host feeder (parsed / on the GPU / coming back); with the entropy decoder on
+       the device the IR is written and read on one stream, one set does, and the frame buffers alternate between two */
+    const int slot_sets = g_dev_entropy ? 1 : 3, fb_sets = g_dev_entropy ? 2 : 3;
+    if (!g_ebatch) {
+        HIP(vp8hip_configure(g_hip, g_width, g_height, fb_sets * g_batch, slot_sets * g_batch));
+        HIP(vp8hip_geometry(g_hip, &g_geom));
+    }
+    size_t pool = 0;                                    /* --entropy-batch: the block pool of the first attempt */
+    if (g_dev_entropy) {
+        {   /* a batch's bytes at most: the frames are taken in order of size within windows of SORT_WINDOW batches */
+            g_order = (long *)malloc(sizeof(long) * (size_t)total);
+            for (long k = 0; k < total; k++) g_order[k] = k;
+            /* (whole launches: a launch that straddles two windows would get the smallest frames of one and the largest of the next) */
+            long window = ((long)SORT_WINDOW * g_batch + unit - 1) / unit * unit;
+            if (window < 4L * unit) window = 4L * unit;
+            for (long w0 = 0; w0 < total; w0 += window) {
+                const long wn = total - w0 < window ? total - w0 : window;
+                qsort(g_order + w0, (size_t)wn, sizeof(long), by_size_desc);
+            }
+            for (long k0 = 0; k0 < total; k0 += unit) {
+                size_t run = 0;
+                for (long k = k0; k < k0 + unit && k < total; k++) run += FRAME_AT(g_order[k])->size;
+                if (run > g_ent_cap) g_ent_cap = run;
+            }
+        }
+        if (g_ebatch) {
+            /* E frames per entropy launch: E slots without block streams of their own and ONE pool for the blocks of a launch
+               (vp8hip_configure_pooled) -- a frame in flight costs what it needs (records 192 bytes a macroblock + its blocks), not
+               the worst case (960), and frames in flight are what the entropy decoder's rate is made of.  The pool: what the
+               launch that needs most is expected to need -- a frame's blocks are 6 to 13 times its compressed bytes in the
+               fixtures: 14 times, capped by the worst case; / 0.75, because the kernel leaves a chunk as soon as what is left of it
+               would not hold a macroblock row's WORST case (a quarter of a chunk; real rows take a third of that), + two chunks per
+               frame for the chunks a frame begins and ends in. */
+            const size_t nmb = (size_t)((g_width + 15) / 16) * (size_t)((g_height + 15) / 16);
+            const size_t worst = nmb * 24 * 32, chunk = (size_t)4 * ((g_width + 15) / 16) * 24 * 32;
+            for (long k0 = 0; k0 < total; k0 += unit) {
+                size_t need = 0;
+                for (long k = k0; k < k0 + unit && k < total; k++) {
+                    const size_t est = 14 * FRAME_AT(g_order[k])->size;
+                    need += (est < worst ? est : worst) * 4 / 3 + 2 * chunk;
+                }
+                if (need > pool) pool = need;
+            }
+            pool += 4 * chunk;
+            if (pool_mb > 0) pool = (size_t)pool_mb << 20;
+            configure_pooled(pool, no_download);
+        }
+        for (int k = 0; k < 3; k++) {
+            if (!(g_ent[k] = (vp8hip_entropy_frame *)vp8hip_host_alloc(g_hip, (size_t)unit * sizeof(vp8hip_entropy_frame))) ||
+                !(g_ent_data[k] = (uint8_t *)vp8hip_host_alloc(g_hip, g_ent_cap + 16)) ||
+                !(g_ent_status[k] = (uint32_t *)vp8hip_host_alloc(g_hip, (size_t)unit * sizeof(uint32_t)))) DIE("vp8hip_host_alloc: %s", vp8hip_last_error(g_hip));
+        }
+    } else {
+        g_maps = calloc((size_t)3 * g_batch, sizeof *g_maps);
+        for (int s = 0; s < 3 * g_batch; s++)
+            HIP(vp8hip_ir_map_compact(g_hip, s, &g_maps[s].hdr, &g_maps[s].mbx, &g_maps[s].blocks, &g_maps[s].cap, &g_maps[s].mvs));
+    }
+    g_stride = vp8hip_frame_stride(g_hip);
+    g_packed = g_dev_md5 && !no_download && g_width % 8 == 0 && !getenv("VP8BATCH_WHOLE_BUFFERS");
+    if (g_packed) g_stride = vp8hip_i420_bytes(g_hip);
+    for (int k = 0; k < 2; k++) {
+        if (!no_download && !(g_host[k] = (uint8_t *)vp8hip_host_alloc(g_hip, (size_t)g_batch * g_stride))) DIE("vp8hip_host_alloc: %s", vp8hip_last_error(g_hip));
+        if (!(g_dig[k] = (uint8_t *)vp8hip_host_alloc(g_hip, (size_t)(g_ebatch && no_download ? g_ebatch : g_batch) * 16))) DIE("vp8hip_host_alloc: %s", vp8hip_last_error(g_hip));
+    }
+    g_digest = calloc((size_t)total, 16);
+    g_parsers = calloc((size_t)threads, sizeof *g_parsers);
+    for (int t = 0; t < threads; t++)
+        if (!(g_parsers[t] = vp8_parser_create())) DIE("out of memory");
+    pthread_t *tid = start_feeders(threads);
+    vp8hip_job *jobs = calloc((size_t)g_batch, sizeof *jobs);
+
+    double dt;
+    if (!g_ebatch) dt = run_batches(jobs, total, no_download);
+    else for (size_t scale = 1; run_pooled(jobs, total, no_download, &dt); ) {
+        if (scale == 8) {
+            fprintf(stderr, "the block pool is still too small at %zu times its size: raise --pool-mb or lower --entropy-batch\n", scale);
+            return EX_TEMPFAIL;
+        }
+        scale *= 2;
+        fprintf(stderr, "the block pool was too small: decoding again with a pool %zu times the size\n", scale);
+        /* nothing of the attempt is kept: the device drained, digests and corrupt frames anew, the pools allocated again at the new
+           size (the tile pool with launch 0), with no staging of packed downloads beside them -- as in a fresh process */
+        HIP(vp8hip_sync(g_hip));
+        HIP(vp8hip_download_wait(g_hip));
+        HIP(vp8hip_release_staging(g_hip));
+        memset(g_digest, 0, (size_t)total * 16);
+        g_corrupt = 0; g_failed = 0;
+        configure_pooled(pool * scale, no_download);
+    }
 
     /* ---- the listing */
     FILE *out = fopen(out_path, "wb");
     if (!out) DIE("Failed to open %s for writing", out_path);
-    for (long f = 0; f < total; f++) {
-        for (int i = 0; i < 16; i++) fprintf(out, "%02x", g_digest[f][i]);
-        fprintf(out, "  img-%dx%d-%04ld.i420\n", g_width, g_height, g_first + f + 1);
-    }
+    write_listing(out, g_digest, total, g_first, "");
     fclose(out);
+    char tail[96] = "";
+    if (g_ebatch) snprintf(tail, sizeof tail, "; %d frames per entropy launch; %ld corrupt", g_ebatch, g_corrupt);
+    else if (g_corrupt) snprintf(tail, sizeof tail, "; CORRUPT FRAMES, see above");
     fprintf(stderr, "%ld frames in %.3f s: %.1f frames/s, %.1f Mpix/s (%d feeder threads, %d frames per launch, entropy decode on the %s, MD5 on the %s%s%s)\n",
             total, dt, total / dt, total / dt * g_width * g_height / 1e6, threads, g_batch, g_dev_entropy ? "device" : "host",
-            g_dev_md5 ? "device" : "host", no_download ? ", frames not downloaded" : "", g_corrupt ? "; CORRUPT FRAMES, see above" : "");
+            g_dev_md5 ? "device" : "host", no_download ? ", frames not downloaded" : "", tail);
     leave_stats(total, dt);
-
-    pthread_mutex_lock(&pool.mu);
-    pool.stop = 1;
-    pthread_cond_broadcast(&pool.work);
-    pthread_mutex_unlock(&pool.mu);
-    for (int t = 0; t < threads; t++) { pthread_join(tid[t], NULL); vp8_parser_destroy(g_parsers[t]); }
-    if (g_host[0]) vp8hip_host_free(g_hip, g_host[0]);
-    if (g_host[1]) vp8hip_host_free(g_hip, g_host[1]);
-    for (int k = 0; k < 2; k++) if (g_ent[k]) { vp8hip_host_free(g_hip, g_ent[k]); vp8hip_host_free(g_hip, g_ent_data[k]); }
-    vp8hip_host_free(g_hip, g_dig[0]);
-    vp8hip_host_free(g_hip, g_dig[1]);
+    stop_feeders(tid, threads);
+    for (int t = 0; t < threads; t++) vp8_parser_destroy(g_parsers[t]);
     vp8hip_destroy(g_hip);
     return EXIT_SUCCESS;
 }
