@@ -289,6 +289,21 @@ int  vp8hip_frames_fetch_i420_async(vp8hip_ctx *ctx, int first_fb, int count, ui
 /* The digests alone, of ANY n frame buffers (fbs[i]; not necessarily neighbours: the shown frames of many streams decoded side by
  * side, bin/batch_md5 --streams): digests[16 * i].  Same stream and same wait as vp8hip_frames_fetch_async. */
 int  vp8hip_frames_md5_list_async(vp8hip_ctx *ctx, const int *fbs, int n, uint8_t *digests);
+/* Frames for consumers on the device       <- I420Scale, third_party/libyuv/source/scale.c:3762
+ * Any n frame buffers (fbs: any order, repeats allowed; reusable when the call returns) as PACKED I420 in the caller's DEVICE
+ * memory: dst_w x dst_h luma, then U and V, each ((dst_w + 1) / 2) x ((dst_h + 1) / 2), no padding, vp8hip_i420_size(dst_w,
+ * dst_h) bytes; frame i at dst + i * dst_stride, any byte alignment.  At the display size the call is a plain copy (any width);
+ * otherwise the bytes are those of the reference tree's libyuv (its C rows) scaling the image vpx_codec_get_frame returns:
+ * filter 0 point sampling, 1 bilinear, 2 (kFilterBox) the same as 1 -- I420Scale never reaches its box filter.  Each frame is
+ * read in a form it has (raster where it exists, else tiles): nothing is converted or allocated.  Enqueued on the context's
+ * stream (vp8hip_stream): later launches that write these frame buffers run behind it; a caller's stream waits on it with an
+ * event.  Only bytes inside [dst + i * dst_stride, + size) are written.  Returns -2, with nothing enqueued, for n < 1, a frame
+ * buffer out of range, a size outside 1..16383, another filter, dst_stride < size, a dst that is not device memory of the
+ * context's device, or n frames that do not fit in dst's allocation.  vp8hip_i420_size: 0 outside 1..16383. */
+size_t vp8hip_i420_size(int w, int h);
+int  vp8hip_frames_scale_async(vp8hip_ctx *ctx, const int *fbs, int n, int dst_w, int dst_h, int filter, void *dst, size_t dst_stride);
+/* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
+int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which
  * the small-launch kernels write and everything that reads pixels by coordinate reads (inter prediction, vp8hip_frame_download,
  * the post-processing filters), and the TILED form a large launch leaves (macroblock-window tiles: the form in which a lane of

@@ -16,6 +16,7 @@ import ctypes
 import hashlib
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -346,10 +347,26 @@ def parse_to_numpy(parser, data):
     return hdr, changed, mbs, coef, mvs
 
 
+def i420_size(w, h):
+    """bytes of a packed I420 frame: w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2)"""
+    return w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
+
+
+def split_i420(t, w, h):
+    """Y [.., h, w], U and V [.., (h + 1) / 2, (w + 1) / 2] views of packed I420 frames t [..., i420_size(w, h)] (numpy or torch)"""
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    lead = tuple(t.shape[:-1])
+    y = t[..., :w * h].reshape(lead + (h, w))
+    u = t[..., w * h:w * h + cw * ch].reshape(lead + (ch, cw))
+    v = t[..., w * h + cw * ch:w * h + 2 * cw * ch].reshape(lead + (ch, cw))
+    return y, u, v
+
+
 # ------------------------------------------------------------------------------------------
 # HIP pixel path (vp8hip.h)
 # ------------------------------------------------------------------------------------------
 _hip = None
+_torch_first = None     # was torch imported before libvp8hip.so was loaded? (Vp8Hip.frames_scaled)
 
 
 class PostprocParams(ctypes.Structure):     # vp8hip_pp, include/vp8hip.h
@@ -403,6 +420,15 @@ def load_hip():
         L.vp8hip_entropy_status.argtypes = [c_void_p, c_int, c_void_p]
         L.vp8hip_ir_fetch.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
         L.vp8hip_ir_fetch_mvs.argtypes = [c_void_p, c_int, c_void_p]
+        L.vp8hip_i420_size.argtypes = [c_int, c_int]
+        L.vp8hip_i420_size.restype = c_size_t
+        L.vp8hip_frames_scale_async.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]
+        L.vp8hip_device.argtypes = [c_void_p]
+        # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
+        # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
+        # pointers this library's runtime does not know
+        global _torch_first
+        _torch_first = "torch" in sys.modules
         _hip = L
     return _hip
 
@@ -600,6 +626,43 @@ class Vp8Hip:
             out = np.ctypeslib.as_array(ctypes.cast(host, ctypes.POINTER(ctypes.c_uint8)), shape=(count, nb)).copy()
         finally:
             self.L.vp8hip_host_free(self.h, host)
+        return out
+
+    def device(self):
+        """the HIP device index the context runs on (-1 at creation resolved)"""
+        return self.L.vp8hip_device(self.h)
+
+    def frames_scaled(self, fbs, width=None, height=None, filter=1, out=None):
+        """Frame buffers `fbs` (any order, repeats allowed) as packed I420 on the context's device, at the display size (a copy) or
+        scaled to width x height as libyuv's I420Scale scales them (vp8hip_frames_scale_async; filter 0 point, 1 bilinear, 2 = 1):
+        a torch.uint8 tensor [n, i420_size(width, height)] -- `out` when given (a view is fine: stride(1) == 1, stride(0) is the
+        frame stride).  Ordered against torch's current stream both ways: usable there without a sync, and the tensor may outlive
+        the context.  The tensor is not recorded on the context's stream (record_stream would make freeing it after close() touch a
+        destroyed stream): an `out` allocated on another stream than the current one must not be freed and reused on that stream
+        before torch's current stream has passed this call.  split_i420 gives the planes."""
+        import torch
+        if not _torch_first:
+            raise RuntimeError("frames_scaled: import torch before the first Vp8Hip (one HIP runtime per process: torch loaded after "
+                               "libvp8hip.so maps a second one, whose device pointers this library cannot use)")
+        fbs = [int(f) for f in fbs]
+        w = self.width if width is None else int(width)
+        h = self.height if height is None else int(height)
+        size = int(self.L.vp8hip_i420_size(w, h))
+        dev = torch.device("cuda", self.device())
+        if out is None:
+            out = torch.empty((len(fbs), size), dtype=torch.uint8, device=dev)
+        if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != len(fbs) or out.shape[1] != size or out.stride(1) != 1 \
+                or out.device != dev:
+            raise ValueError(f"frames_scaled: out must be a uint8 tensor [{len(fbs)}, {size}] on {dev} with stride(1) == 1")
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ext.wait_stream(cur)                    # whatever torch queued that touches `out` first
+        arr = (c_int * max(len(fbs), 1))(*fbs)
+        self._chk(self.L.vp8hip_frames_scale_async(self.h, arr, len(fbs), w, h, int(filter), c_void_p(out.data_ptr()), out.stride(0)),
+                  "vp8hip_frames_scale_async")
+        cur.wait_stream(ext)                    # torch's work after this call sees the frames
+        # (no out.record_stream(ext): the allocator would record an event on the context's stream when the tensor is freed,
+        # which crashes once the context -- and its stream -- is gone; torch's stream waiting on ours already orders any reuse)
         return out
 
     def frames_to_raster(self, first_fb, count):

@@ -26,6 +26,41 @@ struct DevGeom {
     int y_off, u_off, v_off;
 };
 
+// One plane of vp8hip_frames_scale_async (vp8_scale.hip), as the host's plan (vp8hip_scale.hip: scale_plan) left it
+struct ScalePlane {
+    int path, filt;               // SCALE_* below; filt: the path's filtered form
+    int sw, sh, dw, dh;           // the plane's picture and its scaled size
+    int aw, ah;                   // the aligned area every source coordinate is clamped to
+    int dx, dy, x0, y0, maxx, maxy;   // 16.16 steps, first positions and clamps (POINT, BILIN8, BILIN16)
+    int src_off, src_stride;      // raster form: the plane's origin in the frame buffer
+    int tile_plane;               // tiled form: 0 luma, 1 U, 2 V
+    int doff, dsize;              // the plane in a packed frame: offset and bytes
+    int blk0;                     // first workgroup (blockIdx.x) of the plane
+    int br;                       // output rows per workgroup (a band, its source rows staged in LDS); 0: read from the frame
+    int nr, rw;                   // LDS slots per output row (source rows it reads), bytes per slot
+    int adv_rows, adv_cols;       // 1024 destination bytes (a lane's step) as rows and columns of the plane: 1024 = adv_rows * dw + adv_cols
+};
+#define SCALE_COPY 0              // ScalePlane::path: ScalePlane's dispatch (scale.c:3702)
+#define SCALE_DOWN2 1
+#define SCALE_DOWN4 2
+#define SCALE_DOWN8 3
+#define SCALE_DOWN34 4
+#define SCALE_DOWN38 5
+#define SCALE_POINT 6             // ScalePlaneSimple
+#define SCALE_BILIN8 7            // ScalePlaneBilinear's rows: 8-bit row fraction
+#define SCALE_BILIN16 8           // ScalePlaneBilinearSimple
+#define SCALE_FROM_RASTER 0       // ScaleLaunch::fb: the form a frame is read from
+#define SCALE_FROM_TILES 1
+#define SCALE_FROM_ZERO 2         // a frame buffer never written: its raster form would be zeros (and the pool need not exist)
+#define SCALE_MAX_FRAMES 512      // frame buffers per launch (kernel arguments)
+#define SCALE_MAX_LDS 65536       // LDS of a band
+#define SCALE_WIN 4               // destination bytes per lane: an aligned dword
+struct ScaleLaunch {
+    ScalePlane p[3];
+    int blocks, mb_cols;          // workgroups of a frame (gridDim.x); the frame's width in macroblocks
+    int fb[SCALE_MAX_FRAMES];     // frame buffer << 2 | form (SCALE_FROM_*)
+};
+
 #define WAVE 64
 
 // Macroblock tiles of the one-MB-row-per-lane pipeline (vp8_keyframe_simt.hip has the layout): three 128-byte lines per macroblock.
