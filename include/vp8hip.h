@@ -114,7 +114,8 @@ int  vp8hip_memory_usage(const vp8hip_ctx *ctx, vp8hip_memory *out);
  * VP8HIP_MD5_PACK_FROM (12,288) tiled frames and more is hashed from: 3.1 MB per 1080p frame, 51 GB at 16,384, allocated when first
  * needed (a fetch that finds no room for it hashes the tiles) and KEPT for the next batch.  It is a cache: the library frees it by
  * itself when one of the two pools cannot be allocated beside it, and vp8hip_release_staging frees it now (waits for fetches in
- * flight). */
+ * flight).  The scratch of vp8hip_frames_rgb_async (scaled frames as packed I420, at most 256 MB; vp8hip_rgb_scratch_bytes, not one
+ * of the six fields) is a cache of the same kind and is freed by the same call. */
 int  vp8hip_release_staging(vp8hip_ctx *ctx);
 int  vp8hip_geometry(const vp8hip_ctx *ctx, vp8ir_geom *g);
 
@@ -302,6 +303,51 @@ int  vp8hip_frames_md5_list_async(vp8hip_ctx *ctx, const int *fbs, int n, uint8_
  * context's device, or n frames that do not fit in dst's allocation.  vp8hip_i420_size: 0 outside 1..16383. */
 size_t vp8hip_i420_size(int w, int h);
 int  vp8hip_frames_scale_async(vp8hip_ctx *ctx, const int *fbs, int n, int dst_w, int dst_h, int filter, void *dst, size_t dst_stride);
+/* Frames for models on the device: RGB tensors (bytes, halves or floats)
+ * The result for a frame is convert(S), S being the packed I420 image vp8hip_frames_scale_async would write for the same
+ * (frame buffer, dst_w, dst_h, filter): sizes, libyuv's paths, odd sizes and the clamp to the aligned area are the scaler's, bit
+ * for bit.  convert, for output pixel (x, y): Y = S.y[y][x], U = S.u[y >> 1][x >> 1], V = S.v[y >> 1][x >> 1] (chroma replicated,
+ * not interpolated), then in 32-bit integers, >> arithmetic:
+ *     l = cy * (Y - yoff) + 128
+ *     R = clamp255((l + crv * (V - 128)) >> 8)
+ *     G = clamp255((l + cgu * (U - 128) + cgv * (V - 128)) >> 8)
+ *     B = clamp255((l + cbu * (U - 128)) >> 8)
+ *     matrix                            yoff   cy  crv   cgu   cgv  cbu      (the exact matrices times 256, rounded: within 1 of
+ *     VP8HIP_RGB_BT601 (limited range)    16  298  409  -100  -208  516       the rounded float64 result for every (Y, U, V))
+ *     VP8HIP_RGB_BT601_FULL                0  256  359   -88  -183  454
+ *     VP8HIP_RGB_BT709 (limited range)    16  298  459   -55  -136  541
+ * The stream's color_space / clamping_type bits are not read: the matrix is the caller's choice (a VP8 stream with color_space 0
+ * is BT.601, limited range).
+ * dtype: VP8HIP_RGB_U8 the byte v; VP8HIP_RGB_F32 (float)((double)v * (double)scale[c] + (double)bias[c]) for colour c (R, G, B --
+ * by colour, not by position; the product is exact in double, so fused or not gives the same float); VP8HIP_RGB_F16 that float
+ * rounded to nearest-even.  scale and bias are read for the float types only.
+ * layout, per frame, dense, frame i at dst + i * dst_stride BYTES: VP8HIP_RGB_PLANAR three planes [3][dst_h][dst_w] in the order
+ * `order` gives (NCHW); VP8HIP_RGB_PACKED3 [dst_h][dst_w][3] (RGB24 / BGR24, channels last); VP8HIP_RGB_PACKED4 [dst_h][dst_w][4],
+ * fourth byte 255, bytes only.  order: 0 = R, G, B; 1 = B, G, R.
+ * Same rules as vp8hip_frames_scale_async: any list of frame buffers, repeats allowed, fbs reusable on return; enqueued on the
+ * context's stream; each frame read in a form it has, none converted, no raster pool made for frames left as tiles; only bytes
+ * inside [dst + i * dst_stride, + vp8hip_rgb_size) written.  -2 with nothing enqueued for n < 1, a frame buffer out of range, a size
+ * outside 1..16383, a bad filter / matrix / layout / order / dtype, PACKED4 with a float type, dst_stride < size, a dst that is not
+ * device memory of the context's device, frames that do not fit in dst's allocation, or a dst / dst_stride not aligned to the
+ * element type (bytes: any alignment).  Whole-piece stores need dst_w % 4 == 0 and dst, dst_stride aligned to 4 bytes (planar and
+ * packed bytes), 8 (halves) or 16 (floats, four-byte pixels) -- what a dense torch tensor gives; anything else is written element
+ * by element, correctly but slowly.
+ * At the display size the frame is read directly.  At any other size the scaler runs into a scratch of packed I420 that the context
+ * owns and the conversion reads that: one chunk of at most 512 frames and at most 256 MB (fewer frames per chunk for large targets,
+ * one at least), reused chunk after chunk in stream order, allocated on first need, reported by vp8hip_rgb_scratch_bytes, freed by
+ * vp8hip_release_staging and vp8hip_destroy; it is the only device memory the call adds.
+ * vp8hip_rgb_size: bytes of one frame; 0 for anything the call would refuse on p alone. */
+enum { VP8HIP_RGB_BT601 = 0, VP8HIP_RGB_BT601_FULL = 1, VP8HIP_RGB_BT709 = 2 };
+enum { VP8HIP_RGB_PLANAR = 0, VP8HIP_RGB_PACKED3 = 1, VP8HIP_RGB_PACKED4 = 2 };
+enum { VP8HIP_RGB_U8 = 0, VP8HIP_RGB_F16 = 1, VP8HIP_RGB_F32 = 2 };
+typedef struct vp8hip_rgb {
+    int dst_w, dst_h, filter;      /* as vp8hip_frames_scale_async */
+    int matrix, layout, order, dtype;
+    float scale[3], bias[3];       /* by colour R, G, B; read for F16 / F32 only */
+} vp8hip_rgb;
+size_t vp8hip_rgb_size(const vp8hip_rgb *p);
+int  vp8hip_frames_rgb_async(vp8hip_ctx *ctx, const int *fbs, int n, const vp8hip_rgb *p, void *dst, size_t dst_stride);
+size_t vp8hip_rgb_scratch_bytes(const vp8hip_ctx *ctx);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

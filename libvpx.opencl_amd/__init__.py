@@ -362,6 +362,27 @@ def split_i420(t, w, h):
     return y, u, v
 
 
+RGB_MATRICES = {"bt601": 0, "bt601-full": 1, "bt709": 2}       # VP8HIP_RGB_BT601 ...
+RGB_LAYOUTS = {"nchw": 0, "nhwc": 1, "nhwc4": 2}                # VP8HIP_RGB_PLANAR, PACKED3, PACKED4
+RGB_ORDERS = {"rgb": 0, "bgr": 1}
+RGB_U8, RGB_F16, RGB_F32 = 0, 1, 2
+
+
+def rgb_size(w, h, layout="nchw", dtype=RGB_U8):
+    """bytes of one frame of Vp8Hip.frames_rgb (vp8hip_rgb_size): w * h * channels * element size; 0 for a size outside 1..16383,
+    an unknown layout / type, or "nhwc4" with a float type.  dtype: RGB_U8 / RGB_F16 / RGB_F32 or the torch / numpy type's name"""
+    dt = _rgb_dtype(dtype)
+    if layout not in RGB_LAYOUTS or dt is None or not (1 <= w <= 16383 and 1 <= h <= 16383) or (layout == "nhwc4" and dt != RGB_U8):
+        return 0
+    return w * h * (4 if layout == "nhwc4" else 3) * (1, 2, 4)[dt]
+
+
+def _rgb_dtype(dtype):
+    if isinstance(dtype, int):
+        return dtype if dtype in (RGB_U8, RGB_F16, RGB_F32) else None
+    return {"uint8": RGB_U8, "float16": RGB_F16, "float32": RGB_F32}.get(str(dtype).split(".")[-1])
+
+
 # ------------------------------------------------------------------------------------------
 # HIP pixel path (vp8hip.h)
 # ------------------------------------------------------------------------------------------
@@ -375,6 +396,11 @@ class PostprocParams(ctypes.Structure):     # vp8hip_pp, include/vp8hip.h
 
 
 PP_DEBLOCK, PP_DEMACROBLOCK, PP_ADDNOISE = 1, 2, 4
+
+
+class RgbParams(ctypes.Structure):          # vp8hip_rgb, include/vp8hip.h
+    _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("filter", c_int), ("matrix", c_int), ("layout", c_int), ("order", c_int),
+                ("dtype", c_int), ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3)]
 
 
 class VisParams(ctypes.Structure):          # vp8hip_vis, include/vp8hip.h
@@ -424,6 +450,12 @@ def load_hip():
         L.vp8hip_i420_size.restype = c_size_t
         L.vp8hip_frames_scale_async.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]
         L.vp8hip_device.argtypes = [c_void_p]
+        L.vp8hip_rgb_size.argtypes = [ctypes.POINTER(RgbParams)]
+        L.vp8hip_rgb_size.restype = c_size_t
+        L.vp8hip_frames_rgb_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(RgbParams), c_void_p, c_size_t]
+        L.vp8hip_rgb_scratch_bytes.argtypes = [c_void_p]
+        L.vp8hip_rgb_scratch_bytes.restype = c_size_t
+        L.vp8hip_release_staging.argtypes = [c_void_p]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -640,30 +672,85 @@ class Vp8Hip:
         the context.  The tensor is not recorded on the context's stream (record_stream would make freeing it after close() touch a
         destroyed stream): an `out` allocated on another stream than the current one must not be freed and reused on that stream
         before torch's current stream has passed this call.  split_i420 gives the planes."""
-        import torch
-        if not _torch_first:
-            raise RuntimeError("frames_scaled: import torch before the first Vp8Hip (one HIP runtime per process: torch loaded after "
-                               "libvp8hip.so maps a second one, whose device pointers this library cannot use)")
         fbs = [int(f) for f in fbs]
         w = self.width if width is None else int(width)
         h = self.height if height is None else int(height)
         size = int(self.L.vp8hip_i420_size(w, h))
+
+        def ok(torch, out, dev):
+            return out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == len(fbs) and out.shape[1] == size and out.stride(1) == 1 \
+                and out.device == dev
+        return self._to_torch("frames_scaled", len(fbs), "uint8", (size,), out, ok, f"a uint8 tensor [{len(fbs)}, {size}] with stride(1) == 1",
+                              lambda arr_out, stride: self.L.vp8hip_frames_scale_async(
+                                  self.h, (c_int * max(len(fbs), 1))(*fbs), len(fbs), w, h, int(filter), arr_out, stride),
+                              "vp8hip_frames_scale_async")
+
+    def _to_torch(self, who, n, dtype, shape, out, ok, want, call, what):
+        """The torch side of a hand-over on the device (frames_scaled, frames_rgb): `out` (made here when None: [n, *shape] of
+        `dtype`) checked with ok(torch, out, device), then call(data pointer, frame stride in bytes) between the two stream waits."""
+        import torch
+        if not _torch_first:
+            raise RuntimeError(f"{who}: import torch before the first Vp8Hip (one HIP runtime per process: torch loaded after "
+                               "libvp8hip.so maps a second one, whose device pointers this library cannot use)")
         dev = torch.device("cuda", self.device())
         if out is None:
-            out = torch.empty((len(fbs), size), dtype=torch.uint8, device=dev)
-        if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != len(fbs) or out.shape[1] != size or out.stride(1) != 1 \
-                or out.device != dev:
-            raise ValueError(f"frames_scaled: out must be a uint8 tensor [{len(fbs)}, {size}] on {dev} with stride(1) == 1")
+            out = torch.empty((n,) + tuple(shape), dtype=getattr(torch, dtype), device=dev)
+        if not ok(torch, out, dev):
+            raise ValueError(f"{who}: out must be {want} on {dev}")
         ext = torch.cuda.ExternalStream(self.stream(), device=dev)
         cur = torch.cuda.current_stream(dev)
         ext.wait_stream(cur)                    # whatever torch queued that touches `out` first
-        arr = (c_int * max(len(fbs), 1))(*fbs)
-        self._chk(self.L.vp8hip_frames_scale_async(self.h, arr, len(fbs), w, h, int(filter), c_void_p(out.data_ptr()), out.stride(0)),
-                  "vp8hip_frames_scale_async")
+        self._chk(call(c_void_p(out.data_ptr()), out.stride(0) * out.element_size()), what)
         cur.wait_stream(ext)                    # torch's work after this call sees the frames
         # (no out.record_stream(ext): the allocator would record an event on the context's stream when the tensor is freed,
         # which crashes once the context -- and its stream -- is gone; torch's stream waiting on ours already orders any reuse)
         return out
+
+    def frames_rgb(self, fbs, width=None, height=None, filter=1, dtype=None, layout="nchw", order="rgb", matrix="bt601", mean=None, std=None,
+                   out=None):
+        """Frame buffers `fbs` (any order, repeats allowed) as RGB on the context's device (vp8hip_frames_rgb_async): a tensor
+        [n, 3, h, w] ("nchw"), [n, h, w, 3] ("nhwc") or [n, h, w, 4] ("nhwc4": fourth byte 255, uint8 only) of torch.uint8 (the
+        default), torch.float16 or torch.float32, channels in `order` ("rgb" / "bgr"), at the display size or scaled as
+        frames_scaled scales (width, height, filter), converted with `matrix` ("bt601": limited range, what a VP8 stream is;
+        "bt601-full"; "bt709"): the integer arithmetic of include/vp8hip.h, chroma replicated.  Float types: the value for byte v
+        of colour c (R, G, B) is float32(float64(v) * scale[c] + bias[c]) -- float16: that, rounded to nearest-even -- with
+        scale = float32(1 / (255 * std)) and bias = float32(-mean / std), each computed in float64 from `mean` / `std` (per colour,
+        on the 0..1 scale; default 0 and 1) and cast once: THIS PAIR of float32 numbers defines the values, not (v / 255 - mean) /
+        std evaluated some other way.  `out`: the inner three dimensions dense, stride(0) free.  Stream ordering, the `import
+        torch` first rule and the remark on record_stream: as frames_scaled."""
+        import torch
+        fbs = [int(f) for f in fbs]
+        w = self.width if width is None else int(width)
+        h = self.height if height is None else int(height)
+        dtype = torch.uint8 if dtype is None else dtype
+        dt = _rgb_dtype(dtype)
+        if dt is None or layout not in RGB_LAYOUTS or order not in RGB_ORDERS or matrix not in RGB_MATRICES:
+            raise ValueError(f"frames_rgb: dtype {dtype}, layout {layout!r}, order {order!r}, matrix {matrix!r}")
+        mean = np.zeros(3) if mean is None else np.asarray(mean, np.float64).reshape(3)
+        std = np.ones(3) if std is None else np.asarray(std, np.float64).reshape(3)
+        p = RgbParams(w, h, int(filter), RGB_MATRICES[matrix], RGB_LAYOUTS[layout], RGB_ORDERS[order], dt)
+        for c in range(3):
+            p.scale[c] = np.float32(1.0 / (255.0 * std[c]))
+            p.bias[c] = np.float32(-mean[c] / std[c])
+        if not self.L.vp8hip_rgb_size(ctypes.byref(p)):
+            raise ValueError(f"frames_rgb: {w}x{h}, filter {filter}, {dtype}, layout {layout!r}: refused (sizes 1..16383; nhwc4 is uint8 only)")
+        shape = (3, h, w) if layout == "nchw" else (h, w, 3 if layout == "nhwc" else 4)
+        name = ("uint8", "float16", "float32")[dt]
+
+        def ok(torch, out, dev):
+            return out.dtype == getattr(torch, name) and tuple(out.shape) == (len(fbs),) + shape and (not fbs or out[0].is_contiguous()) and out.device == dev
+        return self._to_torch("frames_rgb", len(fbs), name, shape, out, ok, f"a {name} tensor {[len(fbs)] + list(shape)}, each frame dense",
+                              lambda arr_out, stride: self.L.vp8hip_frames_rgb_async(
+                                  self.h, (c_int * max(len(fbs), 1))(*fbs), len(fbs), ctypes.byref(p), arr_out, stride),
+                              "vp8hip_frames_rgb_async")
+
+    def rgb_scratch_bytes(self):
+        """device bytes of frames_rgb's scratch (vp8hip_rgb_scratch_bytes): a chunk of scaled frames as packed I420; a cache"""
+        return int(self.L.vp8hip_rgb_scratch_bytes(self.h))
+
+    def release_staging(self):
+        """vp8hip_release_staging: free the packed staging of downloads and frames_rgb's scratch now"""
+        self._chk(self.L.vp8hip_release_staging(self.h), "vp8hip_release_staging")
 
     def frames_to_raster(self, first_fb, count):
         """Ask for the raster form of frame buffers a large launch left as tiles (vp8hip_frames_to_raster; asynchronous)."""

@@ -26,7 +26,7 @@ struct DevGeom {
     int y_off, u_off, v_off;
 };
 
-// One plane of vp8hip_frames_scale_async (vp8_scale.hip), as the host's plan (vp8hip_scale.hip: scale_plan) left it
+// One plane of vp8hip_frames_scale_async (vp8_scale.hip), as the host's plan (vp8hip_scale.hip: vp8hip_scale_plan) left it
 struct ScalePlane {
     int path, filt;               // SCALE_* below; filt: the path's filtered form
     int sw, sh, dw, dh;           // the plane's picture and its scaled size
@@ -59,6 +59,26 @@ struct ScaleLaunch {
     ScalePlane p[3];
     int blocks, mb_cols;          // workgroups of a frame (gridDim.x); the frame's width in macroblocks
     int fb[SCALE_MAX_FRAMES];     // frame buffer << 2 | form (SCALE_FROM_*)
+};
+
+// One launch of vp8hip_frames_rgb_async (vp8_rgb.hip), as the host's plan (vp8hip_rgb.hip: rgb_plan) left it
+#define RGB_PLANAR 0              // vp8hip_rgb::layout
+#define RGB_PACKED3 1
+#define RGB_PACKED4 2
+#define RGB_U8 0                  // vp8hip_rgb::dtype
+#define RGB_F16 1
+#define RGB_F32 2
+#define SCALE_FROM_PACKED 3       // RgbLaunch::fb's form: a packed I420 image of the scaled size (the call's scratch)
+struct RgbLaunch {
+    ScalePlane p[3];              // the SOURCE planes: aw, ah, rw, src_off, src_stride, tile_plane (of a packed image: aw = its width, src_off its offset)
+    int w, h;                     // the output
+    int br;                       // output rows per workgroup (even): br luma rows and br / 2 rows of each chroma plane in LDS
+    int mb_cols;
+    int vec;                      // every store of a lane is a whole aligned piece (w % 4 == 0 and dst, dst_stride aligned to the piece)
+    int cy, k0;                   // channel at POSITION p of pixel = clamp255((cy * Y + k0 + cu[p] * (U - 128) + cv[p] * (V - 128)) >> 8)
+    int cu[3], cv[3];             // (k0 = 128 - cy * yoff)
+    float scale[3], bias[3];      // by position; float types
+    int fb[SCALE_MAX_FRAMES];     // frame buffer << 2 | form (SCALE_FROM_*); SCALE_FROM_PACKED: frame k of the launch is image k of the scratch
 };
 
 #define WAVE 64

@@ -191,6 +191,7 @@ extern "C" void vp8hip_destroy(vp8hip_ctx *c)
     }
     if (c->stream_h2d) (void)hipStreamDestroy(c->stream_h2d);
     if (c->d_i420) (void)hipFree(c->d_i420);
+    if (c->d_rgb) (void)hipFree(c->d_rgb);
     if (c->ev_pack) (void)hipEventDestroy(c->ev_pack);
     for (int k = 0; k < 3; k++) {
         if (c->stream_d2h_more[k]) (void)hipStreamDestroy(c->stream_d2h_more[k]);
@@ -342,7 +343,14 @@ static int configure_pools(vp8hip_ctx *c, int width, int height, int num_fb, int
 // (fetch_impl) -- is a cache: given back when a pool that the context cannot do without finds no room.
 int vp8hip_drop_staging(vp8hip_ctx *c)
 {
-    if (!c->d_i420) return 0;
+    int freed = 0;
+    if (c->d_rgb) {              // the scratch of vp8hip_frames_rgb_async (vp8hip_rgb.hip): read and written on the main stream
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->d_rgb);
+        c->d_rgb = nullptr; c->rgb_cap = 0;
+        freed = 1;
+    }
+    if (!c->d_i420) return freed;
     if (c->stream_d2h) HIPCHK(c, hipStreamSynchronize(c->stream_d2h));
     for (int k = 0; k < 3; k++) if (c->stream_d2h_more[k]) HIPCHK(c, hipStreamSynchronize(c->stream_d2h_more[k]));
     (void)hipFree(c->d_i420);

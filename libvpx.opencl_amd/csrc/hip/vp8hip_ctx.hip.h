@@ -109,6 +109,7 @@ struct vp8hip_ctx {
     // batch's uploads run beside it
     hipStream_t stream_d2h;
     uint8_t *d_i420; size_t i420_cap; hipEvent_t ev_pack;     // vp8hip_frames_fetch_i420_async: the batch as packed I420, before it leaves
+    uint8_t *d_rgb; size_t rgb_cap;                           // vp8hip_frames_rgb_async: a chunk of frames as packed I420 at the scaled size (a cache)
     hipStream_t stream_d2h_more[3]; hipEvent_t ev_d2h_more[3];      // a batch download in up to four pieces on streams of their own (a copy engine each)
     hipEvent_t ev_d2h_from, ev_d2h_done;
     int d2h_first, d2h_count;      // frame buffers of the copy in flight (count 0: none)
@@ -153,8 +154,20 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 // pipeline whose frames are written as tiles, hashed as tiles and never read by coordinate never pays for it -- at 1080p 3.2 MB
 // per frame buffer, a quarter of what a frame in flight costs.
 int vp8hip_raster_pool(vp8hip_ctx *c);
-int vp8hip_drop_staging(vp8hip_ctx *c);       // vp8hip.hip: frees the packed staging (1: freed, 0: there was none)
+int vp8hip_drop_staging(vp8hip_ctx *c);       // vp8hip.hip: frees the packed staging and the RGB call's scratch (1: freed, 0: there was none)
 int vp8hip_need_raster(vp8hip_ctx *c, int first, int count);
 int vp8hip_need_raster_list(vp8hip_ctx *c, const int *fbs, int n);
 // vp8hip.hip
 int vp8hip_check_status(vp8hip_ctx *c);       // after a stream synchronisation: did a kernel of the cross-CU family give up on a hand-over?
+// vp8hip_scale.hip: what vp8hip_frames_scale_async and vp8hip_frames_rgb_async (vp8hip_rgb.hip) share -- the plan of a target size
+// (returns the LDS a workgroup takes), the check of a destination in the caller's device memory (0, or -2 with the error set), one
+// launch of at most SCALE_MAX_FRAMES frames
+int vp8hip_scale_plan(const vp8hip_ctx *c, int dw, int dh, int filter, ScaleLaunch &L);
+int vp8hip_check_device_span(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, int n);
+int vp8hip_scale_enqueue(vp8hip_ctx *c, const int *fbs, int m, ScaleLaunch &L, int lds, void *dst, size_t dst_stride);
+// the form a reader that converts nothing takes a frame buffer in: raster where it exists, else tiles; never written: zeros
+static inline int vp8hip_frame_form(const vp8hip_ctx *c, int fb)
+{
+    const uint8_t st = c->fb_state[(size_t)fb];
+    return (st & FB_RASTER) && c->fb_block ? SCALE_FROM_RASTER : (st & FB_TILES) ? SCALE_FROM_TILES : SCALE_FROM_ZERO;
+}

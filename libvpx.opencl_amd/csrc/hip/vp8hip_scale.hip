@@ -19,7 +19,7 @@ extern "C" int vp8hip_device(const vp8hip_ctx *c) { return c ? c->device : -1; }
 // The whole dispatch of I420Scale for one frame geometry (returns the LDS a workgroup needs): ScalePlane (scale.c:3702) per plane -- chroma on its own sizes,
 // (v + 1) >> 1 on both sides -- with the parameters of the path it takes.  kFilterBox goes where kFilterBilinear goes:
 // ScalePlaneDown tests src_height * 2 > dst_height (scale.c:3664), true for every downscale.
-static int scale_plan(const vp8hip_ctx *c, int dw, int dh, int filter, ScaleLaunch &L)
+int vp8hip_scale_plan(const vp8hip_ctx *c, int dw, int dh, int filter, ScaleLaunch &L)
 {
     const int w = c->width, h = c->height;
     const vp8ir_geom &g = c->geom;
@@ -76,6 +76,45 @@ static int scale_plan(const vp8hip_ctx *c, int dw, int dh, int filter, ScaleLaun
     return lds;
 }
 
+// the destination of n frames of `size` bytes, dst_stride apart: device memory of this context's device, inside one allocation
+int vp8hip_check_device_span(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, int n)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    // the destination: device memory of this context's device, the n frames inside one allocation
+    hipPointerAttribute_t pa;
+    memset(&pa, 0, sizeof pa);
+    if (hipPointerGetAttributes(&pa, dst) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, -2, "%s: the destination is not memory HIP knows", who);
+    }
+    if (pa.type != hipMemoryTypeDevice || pa.device != c->device)
+        return fail(c, -2, "%s: the destination is not device memory of device %d", who, c->device);
+    hipDeviceptr_t abase = nullptr;
+    size_t asize = 0;
+    if (hipMemGetAddressRange(&abase, &asize, (hipDeviceptr_t)dst) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, -2, "%s: no allocation holds the destination", who);
+    }
+    const uintptr_t a0 = (uintptr_t)abase, d0 = (uintptr_t)dst;
+    const bool wraps = dst_stride > (SIZE_MAX - size) / (size_t)n;
+    const size_t span = wraps ? SIZE_MAX : dst_stride * (size_t)(n - 1) + size;
+    if (wraps || d0 < a0 || (d0 - a0) > asize || span > asize - (d0 - a0))
+        return fail(c, -2, "%s: %d frames of %zu bytes, %zu apart, do not fit in the destination's allocation", who, n, size,
+                    dst_stride);
+    return 0;
+}
+
+// m <= SCALE_MAX_FRAMES frames of a planned call on the context's stream; each frame is read in a form it has: raster where it
+// exists, else tiles; never converted
+int vp8hip_scale_enqueue(vp8hip_ctx *c, const int *fbs, int m, ScaleLaunch &L, int lds, void *dst, size_t dst_stride)
+{
+    for (int k = 0; k < m; k++) L.fb[k] = fbs[k] << 2 | vp8hip_frame_form(c, fbs[k]);
+    hipLaunchKernelGGL(vp8_scale_kernel, dim3((unsigned)L.blocks, (unsigned)m), dim3(256), (unsigned)lds, c->stream, (const uint8_t *)c->fb_block,
+                       c->fb_stride, (const uint8_t *)c->tile_block, c->tile_frame, (uint8_t *)dst, dst_stride, L);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 extern "C" int vp8hip_frames_scale_async(vp8hip_ctx *c, const int *fbs, int n, int dst_w, int dst_h, int filter, void *dst, size_t dst_stride)
 {
     if (!c || !fbs || n < 1 || !dst || c->fb.empty()) return fail(c, -2, "vp8hip_frames_scale_async: bad arguments");
@@ -85,44 +124,13 @@ extern "C" int vp8hip_frames_scale_async(vp8hip_ctx *c, const int *fbs, int n, i
     if (!size) return fail(c, -2, "vp8hip_frames_scale_async: size %dx%d outside 1..%d", dst_w, dst_h, SCALE_MAX_SIZE);
     if (filter < 0 || filter > 2) return fail(c, -2, "vp8hip_frames_scale_async: filter %d (0 none, 1 bilinear, 2 box)", filter);
     if (dst_stride < size) return fail(c, -2, "vp8hip_frames_scale_async: stride %zu below the frame's %zu bytes", dst_stride, size);
-    HIPCHK(c, hipSetDevice(c->device));
-    // the destination: device memory of this context's device, the n frames inside one allocation
-    hipPointerAttribute_t pa;
-    memset(&pa, 0, sizeof pa);
-    if (hipPointerGetAttributes(&pa, dst) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, -2, "vp8hip_frames_scale_async: the destination is not memory HIP knows");
-    }
-    if (pa.type != hipMemoryTypeDevice || pa.device != c->device)
-        return fail(c, -2, "vp8hip_frames_scale_async: the destination is not device memory of device %d", c->device);
-    hipDeviceptr_t abase = nullptr;
-    size_t asize = 0;
-    if (hipMemGetAddressRange(&abase, &asize, (hipDeviceptr_t)dst) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, -2, "vp8hip_frames_scale_async: no allocation holds the destination");
-    }
-    const uintptr_t a0 = (uintptr_t)abase, d0 = (uintptr_t)dst;
-    const bool wraps = dst_stride > (SIZE_MAX - size) / (size_t)n;
-    const size_t span = wraps ? SIZE_MAX : dst_stride * (size_t)(n - 1) + size;
-    if (wraps || d0 < a0 || (d0 - a0) > asize || span > asize - (d0 - a0))
-        return fail(c, -2, "vp8hip_frames_scale_async: %d frames of %zu bytes, %zu apart, do not fit in the destination's allocation", n, size,
-                    dst_stride);
+    if (int rc = vp8hip_check_device_span(c, "vp8hip_frames_scale_async", dst, dst_stride, size, n)) return rc;
 
     ScaleLaunch L;
-    const int lds = scale_plan(c, dst_w, dst_h, filter, L);       // (bytes of LDS a workgroup takes)
-    const unsigned blocks = (unsigned)L.blocks;
-    // each frame is read in a form it has: raster where it exists, else tiles; never converted
+    const int lds = vp8hip_scale_plan(c, dst_w, dst_h, filter, L);       // (bytes of LDS a workgroup takes)
     for (int i0 = 0; i0 < n; i0 += SCALE_MAX_FRAMES) {
         const int m = n - i0 < SCALE_MAX_FRAMES ? n - i0 : SCALE_MAX_FRAMES;
-        for (int k = 0; k < m; k++) {
-            const int fb = fbs[i0 + k];
-            const uint8_t st = c->fb_state[(size_t)fb];
-            const int form = (st & FB_RASTER) && c->fb_block ? SCALE_FROM_RASTER : (st & FB_TILES) ? SCALE_FROM_TILES : SCALE_FROM_ZERO;
-            L.fb[k] = fb << 2 | form;
-        }
-        hipLaunchKernelGGL(vp8_scale_kernel, dim3(blocks, (unsigned)m), dim3(256), (unsigned)lds, c->stream, (const uint8_t *)c->fb_block, c->fb_stride,
-                           (const uint8_t *)c->tile_block, c->tile_frame, (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
-        HIPCHK(c, hipGetLastError());
+        if (int rc = vp8hip_scale_enqueue(c, fbs + i0, m, L, lds, (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride)) return rc;
     }
     return 0;
 }
