@@ -348,6 +348,60 @@ typedef struct vp8hip_rgb {
 size_t vp8hip_rgb_size(const vp8hip_rgb *p);
 int  vp8hip_frames_rgb_async(vp8hip_ctx *ctx, const int *fbs, int n, const vp8hip_rgb *p, void *dst, size_t dst_stride);
 size_t vp8hip_rgb_scratch_bytes(const vp8hip_ctx *ctx);
+/* What the decoder knows about a frame beside its pixels, for models on the device: motion vectors and macroblock modes as tensors.
+ * Any n IR slots (slots: any order, repeats allowed; reusable when the call returns) -- slots, not frame buffers: that is where the
+ * data lies (include/vp8_ir.h: the vp8ir_mbx records and mvs[nmb * 16]), whoever wrote them (vp8hip_ir_upload*, vp8hip_ir_copy,
+ * vp8hip_entropy_decode; also on a vp8hip_configure_pooled context: the blocks are not read); the caller knows which slot it decoded
+ * into which frame buffer.  Two tensors per frame, dense, frame i at dst + i * stride BYTES; either destination may be NULL, not both:
+ *     mv    [2][gh][gw] of mv_dtype; channel 0 = x (the IR's col), channel 1 = y (row)
+ *     info  [popcount(planes)][gh][gw] bytes, the planes in the order of their bits
+ * The grid.  dst_w = dst_h = 0, the native grid: gw = 4 * mb_cols, gh = 4 * mb_rows, and cell (by, bx) is luma block
+ * k = (by & 3) * 4 + (bx & 3) of macroblock (by >> 2, bx >> 2) -- the coded area, past the display size.  Otherwise gw = dst_w,
+ * gh = dst_h, and output (y, x) takes the cell (by, bx) = (sy >> 2, sx >> 2) with, in integers (d_w x d_h: the display size),
+ *     sx = ((2 * x + 1) * d_w) / (2 * dst_w)        sy = ((2 * y + 1) * d_h) / (2 * dst_h)
+ * -- the source pixel under the output's centre: at the display size (x >> 2, y >> 2), so that the tensor lines up pixel for pixel
+ * with vp8hip_frames_rgb_async's at the same size.
+ * The cell's values, mb = by >> 2 times mb_cols + bx >> 2, m = the slot's record of mb, h = the slot's header as of the call:
+ *     vector    mvs[mb * 16 + k] as stored: 1/8-pel units, not clamped to the frame, no sign-bias flip; (0, 0) in every cell of a key
+ *               frame (h.frame_type 0: the slot's vector area is stale and is not read) and of a macroblock with m.ref_frame == 0
+ *       VP8HIP_SIDE_I16  the stored int16 v
+ *       VP8HIP_SIDE_F32  (float)((double)v * (double)scale[c]), c = 0 for x, 1 for y (the product is exact in double: one rounding)
+ *       VP8HIP_SIDE_F16  that float rounded to nearest-even
+ *     VP8HIP_SIDE_REF      m.ref_frame (VP8IR_INTRA_FRAME .. VP8IR_ALTREF_FRAME)
+ *     VP8HIP_SIDE_MODE     m.y_mode, or 10 + m.b_modes[k] where m.y_mode == VP8IR_B_PRED
+ *     VP8HIP_SIDE_SKIP     m.flags & VP8IR_MB_SKIP
+ *     VP8HIP_SIDE_SEGMENT  m.segment_id as the record holds it
+ *     VP8HIP_SIDE_QINDEX   h.base_qindex when !h.segmentation_enabled; else, with s = m.segment_id & 3, h.segment_quant[s] when
+ *                          h.mb_segment_abs_delta and h.base_qindex + h.segment_quant[s] otherwise, clamped to 0..127
+ *                          (mb_init_dequantizer, vp8/decoder/decodframe.c)
+ *     VP8HIP_SIDE_CODED    vp8ir_block_kind(&m, k): 0 no residual, 1 a lone DC, 2 more
+ * Enqueued on the context's stream like vp8hip_frames_rgb_async: a later vp8hip_ir_upload*, vp8hip_ir_copy or vp8hip_entropy_decode
+ * that rewrites one of the slots runs behind it.  Only bytes inside [dst + i * stride, + size) are written.  No device memory is
+ * added and no frame buffer is touched.  Returns -2 with nothing enqueued for n < 1; a slot out of range or one that holds no frame
+ * of the context's size (never filled); one of dst_w, dst_h zero and the other not; a size outside 1..16383; a bad mv_dtype; unknown
+ * plane bits; info_dst with planes == 0; both destinations NULL; a stride below the size; an mv_dst / mv_stride not aligned to the
+ * element; a destination that is not device memory of the context's device or that cannot hold n frames.  Whole-piece stores need
+ * gw % 4 == 0 and destination and stride aligned to 4 bytes (info), 8 (int16, halves) or 16 (floats); anything else is written
+ * element by element, correctly but slowly.
+ * vp8hip_side_mv_size / vp8hip_side_info_size: bytes of one frame's tensor (2 * gh * gw * element size; popcount(planes) * gh * gw);
+ * 0 for what the call would refuse on p alone.  ctx is read for the native grid only and may be NULL for a sized one. */
+enum { VP8HIP_SIDE_I16 = 0, VP8HIP_SIDE_F16 = 1, VP8HIP_SIDE_F32 = 2 };
+#define VP8HIP_SIDE_REF 1      /* bit order = plane order */
+#define VP8HIP_SIDE_MODE 2
+#define VP8HIP_SIDE_SKIP 4
+#define VP8HIP_SIDE_SEGMENT 8
+#define VP8HIP_SIDE_QINDEX 16
+#define VP8HIP_SIDE_CODED 32
+typedef struct vp8hip_side {
+    int dst_w, dst_h;          /* both 0: the native block grid, 4 * mb_cols x 4 * mb_rows; otherwise 1..16383 each */
+    int mv_dtype;              /* VP8HIP_SIDE_I16 / F16 / F32 */
+    unsigned planes;           /* VP8HIP_SIDE_* bits for the info tensor */
+    float scale[2];            /* x, y; read for F16 / F32 only */
+} vp8hip_side;
+size_t vp8hip_side_mv_size(const vp8hip_ctx *ctx, const vp8hip_side *p);
+size_t vp8hip_side_info_size(const vp8hip_ctx *ctx, const vp8hip_side *p);
+int  vp8hip_frames_side_async(vp8hip_ctx *ctx, const int *slots, int n, const vp8hip_side *p, void *mv_dst, size_t mv_stride,
+                              void *info_dst, size_t info_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

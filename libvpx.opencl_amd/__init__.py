@@ -383,6 +383,39 @@ def _rgb_dtype(dtype):
     return {"uint8": RGB_U8, "float16": RGB_F16, "float32": RGB_F32}.get(str(dtype).split(".")[-1])
 
 
+SIDE_PLANES = {"ref": 1, "mode": 2, "skip": 4, "segment": 8, "qindex": 16, "coded": 32}      # VP8HIP_SIDE_*: bit order = plane order
+SIDE_I16, SIDE_F16, SIDE_F32 = 0, 1, 2
+
+
+def _side_dtype(dtype):
+    if isinstance(dtype, int):
+        return dtype if dtype in (SIDE_I16, SIDE_F16, SIDE_F32) else None
+    return {"int16": SIDE_I16, "float16": SIDE_F16, "float32": SIDE_F32}.get(str(dtype).split(".")[-1])
+
+
+def _side_planes(planes):
+    """names (any order; the tensor's planes come in bit order) or the mask itself -> the mask, None for an unknown plane"""
+    if isinstance(planes, int):
+        return planes if 0 <= planes < 64 else None
+    mask = 0
+    for name in planes:
+        if name not in SIDE_PLANES:
+            return None
+        mask |= SIDE_PLANES[name]
+    return mask
+
+
+def side_sizes(gw, gh, mv_dtype=SIDE_I16, planes=("ref", "mode", "skip")):
+    """(bytes of one frame's mv tensor, bytes of its info tensor) of Vp8Hip.frames_side on a grid of gw x gh (vp8hip_side_mv_size,
+    vp8hip_side_info_size): 2 * gh * gw * element size and planes * gh * gw; (0, 0) for a size outside 1..16383, an unknown type or
+    plane.  For the native grid gw, gh = 4 * mb_cols, 4 * mb_rows."""
+    dt, mask = _side_dtype(mv_dtype), _side_planes(planes)
+    if dt is None or mask is None or gw == 0 or gh == 0:         # (0 x 0 would ask for the native grid, which needs a context)
+        return 0, 0
+    L, p = load_hip(), SideParams(int(gw), int(gh), dt, mask)
+    return int(L.vp8hip_side_mv_size(None, ctypes.byref(p))), int(L.vp8hip_side_info_size(None, ctypes.byref(p)))
+
+
 # ------------------------------------------------------------------------------------------
 # HIP pixel path (vp8hip.h)
 # ------------------------------------------------------------------------------------------
@@ -401,6 +434,10 @@ PP_DEBLOCK, PP_DEMACROBLOCK, PP_ADDNOISE = 1, 2, 4
 class RgbParams(ctypes.Structure):          # vp8hip_rgb, include/vp8hip.h
     _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("filter", c_int), ("matrix", c_int), ("layout", c_int), ("order", c_int),
                 ("dtype", c_int), ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3)]
+
+
+class SideParams(ctypes.Structure):         # vp8hip_side, include/vp8hip.h
+    _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("mv_dtype", c_int), ("planes", ctypes.c_uint), ("scale", ctypes.c_float * 2)]
 
 
 class VisParams(ctypes.Structure):          # vp8hip_vis, include/vp8hip.h
@@ -456,6 +493,11 @@ def load_hip():
         L.vp8hip_rgb_scratch_bytes.argtypes = [c_void_p]
         L.vp8hip_rgb_scratch_bytes.restype = c_size_t
         L.vp8hip_release_staging.argtypes = [c_void_p]
+        L.vp8hip_side_mv_size.argtypes = [c_void_p, ctypes.POINTER(SideParams)]
+        L.vp8hip_side_mv_size.restype = c_size_t
+        L.vp8hip_side_info_size.argtypes = [c_void_p, ctypes.POINTER(SideParams)]
+        L.vp8hip_side_info_size.restype = c_size_t
+        L.vp8hip_frames_side_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(SideParams), c_void_p, c_size_t, c_void_p, c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -688,23 +730,33 @@ class Vp8Hip:
     def _to_torch(self, who, n, dtype, shape, out, ok, want, call, what):
         """The torch side of a hand-over on the device (frames_scaled, frames_rgb): `out` (made here when None: [n, *shape] of
         `dtype`) checked with ok(torch, out, device), then call(data pointer, frame stride in bytes) between the two stream waits."""
-        import torch
-        if not _torch_first:
-            raise RuntimeError(f"{who}: import torch before the first Vp8Hip (one HIP runtime per process: torch loaded after "
-                               "libvp8hip.so maps a second one, whose device pointers this library cannot use)")
-        dev = torch.device("cuda", self.device())
+        torch, dev = self._torch_device(who)
         if out is None:
             out = torch.empty((n,) + tuple(shape), dtype=getattr(torch, dtype), device=dev)
         if not ok(torch, out, dev):
             raise ValueError(f"{who}: out must be {want} on {dev}")
+        self._between_stream_waits(dev, lambda: call(c_void_p(out.data_ptr()), out.stride(0) * out.element_size()), what)
+        return out
+
+    def _torch_device(self, who):
+        """-> (torch, the context's device as torch names it); refuses when torch came after the library"""
+        import torch
+        if not _torch_first:
+            raise RuntimeError(f"{who}: import torch before the first Vp8Hip (one HIP runtime per process: torch loaded after "
+                               "libvp8hip.so maps a second one, whose device pointers this library cannot use)")
+        return torch, torch.device("cuda", self.device())
+
+    def _between_stream_waits(self, dev, fn, what):
+        """fn() -- a call that writes torch tensors on the context's stream; its status is checked as `what` -- ordered against
+        torch's current stream both ways"""
+        import torch
         ext = torch.cuda.ExternalStream(self.stream(), device=dev)
         cur = torch.cuda.current_stream(dev)
-        ext.wait_stream(cur)                    # whatever torch queued that touches `out` first
-        self._chk(call(c_void_p(out.data_ptr()), out.stride(0) * out.element_size()), what)
-        cur.wait_stream(ext)                    # torch's work after this call sees the frames
-        # (no out.record_stream(ext): the allocator would record an event on the context's stream when the tensor is freed,
+        ext.wait_stream(cur)                    # whatever torch queued that touches the tensors first
+        self._chk(fn(), what)
+        cur.wait_stream(ext)                    # torch's work after this call sees what was written
+        # (no record_stream(ext) on the tensors: the allocator would record an event on the context's stream when one is freed,
         # which crashes once the context -- and its stream -- is gone; torch's stream waiting on ours already orders any reuse)
-        return out
 
     def frames_rgb(self, fbs, width=None, height=None, filter=1, dtype=None, layout="nchw", order="rgb", matrix="bt601", mean=None, std=None,
                    out=None):
@@ -743,6 +795,68 @@ class Vp8Hip:
                               lambda arr_out, stride: self.L.vp8hip_frames_rgb_async(
                                   self.h, (c_int * max(len(fbs), 1))(*fbs), len(fbs), ctypes.byref(p), arr_out, stride),
                               "vp8hip_frames_rgb_async")
+
+    def frames_side(self, slots, width=None, height=None, mv_dtype=None, planes=("ref", "mode", "skip"), scale=None, out_mv=None,
+                    out_info=None):
+        """IR slots `slots` (any order, repeats allowed) as (mv, info) tensors on the context's device (vp8hip_frames_side_async):
+        mv [n, 2, gh, gw] of torch.int16 (the default: the stored 1/8-pel vectors), torch.float16 or torch.float32, channel 0 = x,
+        1 = y; info [n, C, gh, gw] of torch.uint8, the planes of `planes` ("ref", "mode", "skip", "segment", "qindex", "coded", or
+        the mask) in bit order.  With no size the native grid, a cell per 4x4 luma block of the coded area (gw, gh = 4 * mb_cols,
+        4 * mb_rows); with width x height the cell under each output pixel's centre (include/vp8hip.h), so that at frames_rgb's
+        size the tensors line up with its pixels.  Float types: float32(float64(v) * scale[c]) with scale = (x, y) float32 numbers
+        (default 1, 1); scale="pixels" is (0.125 * gw / d_w, 0.125 * gh / d_h), computed in float64 and rounded once: the flow in
+        pixels of the tensor (native grid: d_w, d_h = the coded size).  planes=() gives info None, and out_mv=False / out_info=False
+        skip that tensor; a tensor passed as out_mv / out_info is filled (each frame dense, stride(0) free).  Stream ordering, the
+        `import torch` first rule and the remark on record_stream: as frames_scaled."""
+        torch, dev = self._torch_device("frames_side")
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        native = width is None and height is None
+        if not native and (width is None or height is None):
+            raise ValueError("frames_side: width and height, or neither")
+        gw = 4 * (self.g.aligned_w // 16) if native else int(width)
+        gh = 4 * (self.g.aligned_h // 16) if native else int(height)
+        mv_dtype = torch.int16 if mv_dtype is None else mv_dtype
+        dt, mask = _side_dtype(mv_dtype), _side_planes(planes)
+        if dt is None or mask is None:
+            raise ValueError(f"frames_side: mv_dtype {mv_dtype}, planes {planes!r}")
+        want_mv = out_mv is not False
+        want_info = out_info is not False and mask != 0
+        if not want_mv and not want_info:
+            raise ValueError("frames_side: neither tensor asked for")
+        if scale is None:
+            sc = (1.0, 1.0)
+        elif isinstance(scale, str):
+            if scale != "pixels":
+                raise ValueError(f"frames_side: scale {scale!r}")
+            dw, dh = (self.g.aligned_w, self.g.aligned_h) if native else (self.width, self.height)
+            sc = (0.125 * gw / dw, 0.125 * gh / dh)
+        else:
+            sc = tuple(float(v) for v in scale)
+        p = SideParams(0 if native else gw, 0 if native else gh, dt, mask)
+        p.scale[0], p.scale[1] = np.float32(sc[0]), np.float32(sc[1])
+        if not self.L.vp8hip_side_mv_size(self.h, ctypes.byref(p)):
+            raise ValueError(f"frames_side: grid {gw}x{gh}: refused (sizes 1..16383)")
+        name = ("int16", "float16", "float32")[dt]
+        nc = bin(mask).count("1")
+        if want_mv and out_mv is None:
+            out_mv = torch.empty((n, 2, gh, gw), dtype=getattr(torch, name), device=dev)
+        if want_info and out_info is None:
+            out_info = torch.empty((n, nc, gh, gw), dtype=torch.uint8, device=dev)
+        mv = out_mv if want_mv else None
+        info = out_info if want_info else None
+
+        def dense(t, dtype, ch):
+            return t.dtype == dtype and tuple(t.shape) == (n, ch, gh, gw) and (n == 0 or t[0].is_contiguous()) and t.device == dev
+        if mv is not None and not dense(mv, getattr(torch, name), 2):
+            raise ValueError(f"frames_side: out_mv must be a {name} tensor {[n, 2, gh, gw]}, each frame dense, on {dev}")
+        if info is not None and not dense(info, torch.uint8, nc):
+            raise ValueError(f"frames_side: out_info must be a uint8 tensor {[n, nc, gh, gw]}, each frame dense, on {dev}")
+        self._between_stream_waits(dev, lambda: self.L.vp8hip_frames_side_async(
+            self.h, (c_int * max(n, 1))(*slots), n, ctypes.byref(p),
+            c_void_p(mv.data_ptr()) if mv is not None else None, mv.stride(0) * mv.element_size() if mv is not None else 0,
+            c_void_p(info.data_ptr()) if info is not None else None, info.stride(0) if info is not None else 0), "vp8hip_frames_side_async")
+        return mv, info
 
     def rgb_scratch_bytes(self):
         """device bytes of frames_rgb's scratch (vp8hip_rgb_scratch_bytes): a chunk of scaled frames as packed I420; a cache"""

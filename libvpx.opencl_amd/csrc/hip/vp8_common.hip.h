@@ -81,6 +81,28 @@ struct RgbLaunch {
     int fb[SCALE_MAX_FRAMES];     // frame buffer << 2 | form (SCALE_FROM_*); SCALE_FROM_PACKED: frame k of the launch is image k of the scratch
 };
 
+// One launch of vp8hip_frames_side_async (vp8_side.hip), as the host's plan (vp8hip_side.hip: side_plan) left it
+#define SIDE_I16 0                // vp8hip_side::mv_dtype
+#define SIDE_F16 1
+#define SIDE_F32 2
+#define SIDE_MAX_FRAMES 256       // slots per launch (kernel arguments)
+#define SIDE_X_ANY 0              // SideLaunch::xmode: sx by the division; ...
+#define SIDE_X_DISPLAY 1          // ... gw is the display width: the four outputs of a group share the cell x >> 2; ...
+#define SIDE_X_NATIVE 2           // ... the native grid: the cell is x
+struct SideLaunch {
+    int gw, gh;                   // the output grid
+    int dw, dh;                   // the size the grid is laid over: the display size, or the coded size for the native grid
+    int mb_cols, mb_rows;
+    int R;                        // macroblock rows a workgroup stages (a group); LDS = R * mb_cols * 128 bytes
+    int S;                        // workgroups that share the output rows of a group (gridDim.x = groups * S)
+    int xmode;                    // SIDE_X_*
+    int mv_vec, info_vec;         // every store of a lane is a whole aligned piece (gw % 4 == 0 and destination, stride aligned to the piece)
+    unsigned planes;              // VP8HIP_SIDE_* bits of the info tensor
+    float scale[2];               // x, y; float types
+    int slot[SIDE_MAX_FRAMES];    // IR slot of frame k of the launch
+    unsigned q[SIDE_MAX_FRAMES];  // ... its header: the quantiser index of segment s in bits 7s .. 7s + 6, bit 28 = key frame
+};
+
 #define WAVE 64
 
 // Macroblock tiles of the one-MB-row-per-lane pipeline (vp8_keyframe_simt.hip has the layout): three 128-byte lines per macroblock.

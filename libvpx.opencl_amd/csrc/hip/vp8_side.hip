@@ -1,0 +1,188 @@
+// What the decoder knows about a frame beside its pixels, as tensors in device memory (vp8hip_frames_side_async, vp8hip_side.hip;
+// include/vp8hip.h has the definition): a motion vector per 4x4 block, and per block the macroblock's reference frame, mode, skip
+// flag, segment and quantiser index and whether the block carries residual -- gathered from the IR slots as they lie in HBM
+// (include/vp8_ir.h: vp8ir_mbx records and mvs[nmb * 16]) onto a grid of gw x gh cells:
+//     output (y, x) takes luma block (by, bx) = (sy >> 2, sx >> 2), sx = ((2x + 1) * dw) / (2 * gw), sy = ((2y + 1) * dh) / (2 * gh)
+// (dw x dh: the display size; for the native grid the coded size, which makes (by, bx) = (y, x)).
+//
+// Small input, large output.  A workgroup takes a group of R macroblock rows and the output rows whose cells lie in them (sy is
+// monotone: they are one range; S workgroups share it where a grid is much taller than the frame).  It stages the first 64 bytes
+// of each record -- the vp8ir_mb part -- and the rows' vectors into LDS with 16-byte loads (no vectors for a key frame: its vector
+// area is stale).  Then a lane makes four neighbouring outputs of every plane and stores each four as one piece, neighbouring
+// lanes contiguous: a dword of info bytes, 8 bytes of int16 / halves, 16 bytes of floats.  With mv_vec / info_vec clear -- a grid
+// width that is no multiple of 4, a destination not aligned to the piece -- every element is stored by itself: each exactly once,
+// none outside the frame.  Slot indices and the per-frame header bits travel in the kernel arguments.  Integer and conversion
+// arithmetic only (the one product, vector x scale, is a single-precision multiply: the exact product rounded once, the definition's).
+#include <hip/hip_fp16.h>
+#include "vp8_common.hip.h"
+#include "vp8hip.h"
+
+typedef unsigned int side_x4_t __attribute__((ext_vector_type(4)));
+typedef unsigned int side_x2_t __attribute__((ext_vector_type(2)));
+
+template <int DTYPE> struct SideElem;
+template <> struct SideElem<SIDE_I16> { typedef unsigned short T; };
+template <> struct SideElem<SIDE_F16> { typedef unsigned short T; };
+template <> struct SideElem<SIDE_F32> { typedef unsigned int T; };
+
+// the first output row whose cell lies in macroblock row m or below it: sy >= 16 m  <=>  (2y + 1) * dh >= 32 * m * gh
+__device__ __forceinline__ int side_first_row(int m, int gh, int dh)
+{
+    const int num = 32 * m * gh - dh;            // (m <= 1024, gh <= 16383: below 2^30)
+    return num <= 0 ? 0 : min((num + 2 * dh - 1) / (2 * dh), gh);
+}
+
+struct SideCell {
+    unsigned mv;                                 // row in the low half, col in the high one (vp8ir_mv)
+    unsigned v[6];                               // the info planes in bit order
+};
+
+// rec: the staged records, 16 dwords each; mvs: the staged vectors, 16 dwords per macroblock; mb: the macroblock's index in the
+// staged rows; k: the luma block
+__device__ __forceinline__ void side_cell(const unsigned *rec, const unsigned *mvs, int mb, int k, bool read_mv, unsigned planes, unsigned qf,
+                                          SideCell &c)
+{
+    const unsigned r0 = rec[mb * 16], seg = rec[mb * 16 + 1] & 255u;
+    const unsigned y_mode = r0 & 255u, ref = (r0 >> 16) & 255u, skip = (r0 >> 24) & VP8IR_MB_SKIP;
+    c.mv = read_mv && ref != VP8IR_INTRA_FRAME ? mvs[mb * 16 + k] : 0u;
+    c.v[0] = ref;
+    c.v[1] = y_mode;
+    c.v[2] = skip;
+    c.v[3] = seg;
+    c.v[4] = (qf >> (7 * (seg & 3u))) & 127u;
+    c.v[5] = 0;
+    if (planes & (VP8HIP_SIDE_MODE | VP8HIP_SIDE_CODED)) {
+        const unsigned char *b = (const unsigned char *)(rec + mb * 16);
+        const unsigned eob = b[8 + k];
+        const bool has_y2 = y_mode != VP8IR_B_PRED && y_mode != VP8IR_SPLITMV;
+        if (y_mode == VP8IR_B_PRED) c.v[1] = 10u + b[40 + k];
+        c.v[5] = skip ? 0u : eob > 1 ? 2u : (eob == 1 && !has_y2) ? 1u : 0u;          // vp8ir_block_kind for k < 16
+    }
+}
+
+template <int DTYPE>
+__device__ __forceinline__ unsigned side_value(int v, float scale)
+{
+    if constexpr (DTYPE == SIDE_I16) return (unsigned)v & 0xffffu;
+    else {
+        // (float)((double)v * (double)scale): the product of an int16 and a float is exact in double, so this is that product
+        // rounded once -- which is what the single-precision multiply gives (denormal results kept: the kernels' float mode)
+        const float f = __fmul_rn((float)v, scale);
+        if constexpr (DTYPE == SIDE_F32) return __float_as_uint(f);
+        else return (unsigned)__half_as_ushort(__float2half_rn(f));
+    }
+}
+
+template <int DTYPE>
+__device__ __forceinline__ void side_body(const char *__restrict__ slot_base, size_t slot_bytes, size_t o_mbx, size_t o_mvs,
+                                          uint8_t *__restrict__ mv_dst, size_t mv_stride, uint8_t *__restrict__ info_dst, size_t info_stride,
+                                          const SideLaunch &L)
+{
+    typedef typename SideElem<DTYPE>::T elem_t;
+    constexpr int ES = (int)sizeof(elem_t);
+    extern __shared__ __attribute__((aligned(16))) unsigned side_lds[];
+    const int f = (int)blockIdx.y;
+    const int gw = L.gw, gh = L.gh, cols = L.mb_cols;
+    const int grp = (int)blockIdx.x / L.S, part = (int)blockIdx.x - grp * L.S;
+    const int m0 = grp * L.R, m1 = min(m0 + L.R, L.mb_rows);
+    const int ya = side_first_row(m0, gh, L.dh), yb = m1 == L.mb_rows ? gh : side_first_row(m1, gh, L.dh);
+    const int per = (yb - ya + L.S - 1) / L.S;
+    const int y0 = ya + part * per, y1 = min(yb, y0 + per);
+    if (y0 >= y1) return;                        // (a group no output row falls into: a grid much smaller than the frame)
+
+    const unsigned qf = L.q[f];
+    const bool read_mv = mv_dst && !((qf >> 28) & 1u);
+    const char *slot = slot_base + slot_bytes * (size_t)L.slot[f];
+    side_x4_t *lrec = (side_x4_t *)side_lds;
+    side_x4_t *lmvs = lrec + L.R * cols * 4;
+    {
+        const GLOBAL_AS side_x4_t *grec = (const GLOBAL_AS side_x4_t *)(slot + o_mbx) + (size_t)m0 * cols * 8;
+        const GLOBAL_AS side_x4_t *gmvs = (const GLOBAL_AS side_x4_t *)(slot + o_mvs) + (size_t)m0 * cols * 4;
+        const int n = (m1 - m0) * cols * 4;      // 16-byte pieces: four of a record's eight, the four of a macroblock's vectors
+#pragma unroll 1
+        for (int t = threadIdx.x; t < n; t += 256) lrec[t] = grec[(t >> 2) * 8 + (t & 3)];
+        if (read_mv) {
+#pragma unroll 1
+            for (int t = threadIdx.x; t < n; t += 256) lmvs[t] = gmvs[t];
+        }
+    }
+    __syncthreads();
+
+    const unsigned *rec = (const unsigned *)lrec, *mvs = (const unsigned *)lmvs;
+    uint8_t *Dm = mv_dst ? mv_dst + mv_stride * f : nullptr;
+    uint8_t *Di = info_dst ? info_dst + info_stride * f : nullptr;
+    const size_t plane = (size_t)gh * gw;
+    const int nq = (gw + 3) >> 2;                                   // groups of four outputs in a row
+    const int adv_rows = 256 / nq, adv_cols = 256 - adv_rows * nq;  // a lane's step of 256 groups
+    const int nrows = y1 - y0;
+    int row = (int)threadIdx.x / nq, col = (int)threadIdx.x - row * nq;
+#pragma unroll 1
+    while (row < nrows) {
+        const int y = y0 + row, x = col << 2;
+        const int by = (int)(((unsigned)(2 * y + 1) * (unsigned)L.dh) / (unsigned)(2 * gh)) >> 2;
+        const int mb_row = ((by >> 2) - m0) * cols, kr = (by & 3) * 4;
+        SideCell c[4];
+        if (L.xmode == SIDE_X_DISPLAY) {
+            side_cell(rec, mvs, mb_row + (col >> 2), kr + (col & 3), read_mv, L.planes, qf, c[0]);
+            c[1] = c[0]; c[2] = c[0]; c[3] = c[0];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int xi = min(x + i, gw - 1);
+                const int bx = L.xmode == SIDE_X_NATIVE ? xi : (int)(((unsigned)(2 * xi + 1) * (unsigned)L.dw) / (unsigned)(2 * gw)) >> 2;
+                side_cell(rec, mvs, mb_row + (bx >> 2), kr + (bx & 3), read_mv, L.planes, qf, c[i]);
+            }
+        }
+        const size_t pix = (size_t)y * gw + x;
+        if (Dm) {
+#pragma unroll
+            for (int ch = 0; ch < 2; ch++) {
+                unsigned e[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int v = ch == 0 ? (int)c[i].mv >> 16 : (int)(short)(c[i].mv & 0xffffu);      // x = col, y = row
+                    e[i] = side_value<DTYPE>(v, L.scale[ch]);
+                }
+                uint8_t *o = Dm + ((size_t)ch * plane + pix) * ES;
+                if (L.mv_vec) {
+                    if constexpr (ES == 2) *(GLOBAL_AS side_x2_t *)o = side_x2_t{e[0] | e[1] << 16, e[2] | e[3] << 16};
+                    else *(GLOBAL_AS side_x4_t *)o = side_x4_t{e[0], e[1], e[2], e[3]};
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (x + i < gw) ((GLOBAL_AS elem_t *)o)[i] = (elem_t)e[i];
+                }
+            }
+        }
+        if (Di) {
+            uint8_t *o = Di + pix;
+#pragma unroll
+            for (int b = 0; b < 6; b++) {
+                if (!((L.planes >> b) & 1u)) continue;
+                if (L.info_vec) *(g_u32p)o = c[0].v[b] | c[1].v[b] << 8 | c[2].v[b] << 16 | c[3].v[b] << 24;
+                else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (x + i < gw) ((g_u8p)o)[i] = (unsigned char)c[i].v[b];
+                }
+                o += plane;
+            }
+        }
+        col += adv_cols;
+        row += adv_rows;
+        if (col >= nq) { col -= nq; row++; }
+    }
+}
+
+// grid: x = the groups of macroblock rows of a frame times L.S, y = the frames of the launch.  slot_base: IR slot 0, slot_bytes
+// apart, records at o_mbx and vectors at o_mvs inside; mv_dst / info_dst: the launch's first frame (either may be null).
+#define SIDE_KERNEL(NAME, DTYPE)                                                                                                          \
+    extern "C" __global__ void __launch_bounds__(256)                                                                                     \
+    NAME(const char *__restrict__ slot_base, size_t slot_bytes, size_t o_mbx, size_t o_mvs, uint8_t *__restrict__ mv_dst, size_t mv_stride, \
+         uint8_t *__restrict__ info_dst, size_t info_stride, SideLaunch L)                                                                \
+    {                                                                                                                                     \
+        side_body<DTYPE>(slot_base, slot_bytes, o_mbx, o_mvs, mv_dst, mv_stride, info_dst, info_stride, L);                               \
+    }
+SIDE_KERNEL(vp8_side_i16_kernel, SIDE_I16)
+SIDE_KERNEL(vp8_side_f16_kernel, SIDE_F16)
+SIDE_KERNEL(vp8_side_f32_kernel, SIDE_F32)
