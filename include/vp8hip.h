@@ -402,6 +402,58 @@ size_t vp8hip_side_mv_size(const vp8hip_ctx *ctx, const vp8hip_side *p);
 size_t vp8hip_side_info_size(const vp8hip_ctx *ctx, const vp8hip_side *p);
 int  vp8hip_frames_side_async(vp8hip_ctx *ctx, const int *slots, int n, const vp8hip_side *p, void *mv_dst, size_t mv_stride,
                               void *info_dst, size_t info_stride);
+/* The third input of a model on the compressed domain, beside the picture and the motion vectors: the decoded RESIDUAL, as a tensor.
+ * Any n IR slots (slots: any order, repeats allowed; reusable when the call returns), whoever wrote them (vp8hip_ir_upload*,
+ * vp8hip_ir_copy, vp8hip_entropy_decode; on a vp8hip_configure_pooled context the blocks are read from the pool through the records'
+ * sparse_first, exactly as vp8hip_decode reads them: valid until the caller resets the pool).  One dense tensor per frame, frame i at
+ * dst + i * dst_stride BYTES.
+ * The residual of a sample is the value the reference's decode_macroblock adds to the prediction before the clamp: the content of
+ * the `short` it holds at that point.  Constants and order of operations: vp8/common/idctllm.c:28-204, vp8/common/idct_blk.c:20-86,
+ * vp8/decoder/decodframe.c:252-304.  With m = the slot's record of the macroblock, h = the slot's header as of the call:
+ *   - m.flags & VP8IR_MB_SKIP: 0 everywhere.
+ *   - the factors y1dc, y1ac, y2dc, y2ac, uvdc, uvac: mb_init_dequantizer / vp8cx_init_de_quantizer for h and m.segment_id & 3
+ *     (decodframe.c:50-109, quant_common.c; vp8o_mb_dequant in the oracle).
+ *   - a macroblock with a Y2 block (m.y_mode neither B_PRED nor SPLITMV): with m.eobs[24] > 1 each Y2 coefficient times its factor
+ *     (the first: y2dc, the others: y2ac) is truncated to int16, then vp8_short_inv_walsh4x4_c runs, its first pass stored to int16;
+ *     otherwise a = (int16)(y2[0] * y2dc) and all sixteen DCs are (a + 3) >> 3 (vp8_short_inv_walsh4x4_1_c).  Luma block k then has
+ *     that DC with factor 1 for its first coefficient, and its others with y1ac.
+ *   - a block with eobs[k] > 1 (vp8_short_idct4x4llm_c): each coefficient times its factor (the first: the plane's dc factor, the
+ *     others: its ac factor) truncated to int16; the vertical pass stored to int16; the horizontal pass ends with (x + 4) >> 3.
+ *   - a block with eobs[k] <= 1: dc = (int16)(first coefficient * dc factor), every sample of the block (dc + 4) >> 3
+ *     (vp8_dc_only_idct_add_c) -- also a Y2 macroblock's luma block with eobs[k] <= 1, which takes the WHT's DC; 0 for a block with
+ *     neither a DC nor coefficients.
+ *   - chroma the same with uvdc, uvac.  No Y2 for B_PRED / SPLITMV: luma with y1dc, y1ac.
+ * dtype.  VP8HIP_RES_I16: the int16 as defined.  VP8HIP_RES_F32: (float)((double)v * (double)scale[c]) for plane c (Y, U, V; the
+ * product is exact in double: one rounding).  VP8HIP_RES_F16: that float rounded to nearest-even.
+ * layout.  VP8HIP_RES_I420: three planes back to back at their own sizes, Y gh x gw, then U and V ch x cw -- the raw data, for an
+ * encoder or a transcoder.  VP8HIP_RES_PLANAR: [3][gh][gw], chroma replicated: U and V of output (y, x) are the chroma sample
+ * (sy >> 1, sx >> 1) under the luma sample (sy, sx) it takes -- sample for sample vp8hip_frames_rgb_async's planar tensor at that size.
+ * The grid.  dst_w = dst_h = 0, the native grid: the coded area, gw = 16 * mb_cols, gh = 16 * mb_rows, cw = gw / 2, ch = gh / 2,
+ * every output its own sample.  Otherwise gw = dst_w, gh = dst_h, cw = (gw + 1) / 2, ch = (gh + 1) / 2 and, in integers (d_w x d_h:
+ * the display size; dcw = (d_w + 1) / 2, dch = (d_h + 1) / 2):
+ *     luma output (y, x) takes luma sample      (((2 * y + 1) * d_h) / (2 * gh),  ((2 * x + 1) * d_w) / (2 * gw))
+ *     I420 chroma output (y, x) takes chroma sample (((2 * y + 1) * dch) / (2 * ch), ((2 * x + 1) * dcw) / (2 * cw))
+ * -- at the display size both are the identity: a crop of the coded area.
+ * Enqueued on the context's stream like vp8hip_frames_side_async: a later vp8hip_ir_upload*, vp8hip_ir_copy, vp8hip_entropy_decode or
+ * vp8hip_pool_reset that rewrites what the call reads runs behind it.  Only bytes inside [dst + i * dst_stride, + size) are written.
+ * No device memory is added and no frame buffer is touched.  A slot whose entropy status had bit 1 (the pool was empty) is read in
+ * bounds and gives garbage, as for vp8hip_decode.  Returns -2 with nothing enqueued for n < 1; a slot out of range or one that holds
+ * no frame of the context's size (never filled); one of dst_w, dst_h zero and the other not; a size outside 1..16383; a bad layout or
+ * dtype; dst_stride below the size; a dst / dst_stride not aligned to the element; a destination that is not device memory of the
+ * context's device or that cannot hold n frames.  Whole-piece stores need gw % 4 == 0 (the I420 layout's chroma planes: cw % 4 == 0)
+ * and dst, dst_stride aligned to 8 bytes (int16, halves) or 16 (floats); anything else is written element by element, each once.
+ * vp8hip_residual_size: bytes of one frame's tensor; 0 for what the call would refuse on p alone.  ctx is read for the native grid
+ * only and may be NULL for a sized one. */
+enum { VP8HIP_RES_I16 = 0, VP8HIP_RES_F16 = 1, VP8HIP_RES_F32 = 2 };
+enum { VP8HIP_RES_I420 = 0, VP8HIP_RES_PLANAR = 1 };
+typedef struct vp8hip_residual {
+    int dst_w, dst_h;          /* both 0: the native grid, the coded area; otherwise 1..16383 each */
+    int layout;                /* VP8HIP_RES_I420 / PLANAR */
+    int dtype;                 /* VP8HIP_RES_I16 / F16 / F32 */
+    float scale[3];            /* Y, U, V; read for F16 / F32 only */
+} vp8hip_residual;
+size_t vp8hip_residual_size(const vp8hip_ctx *ctx, const vp8hip_residual *p);
+int  vp8hip_frames_residual_async(vp8hip_ctx *ctx, const int *slots, int n, const vp8hip_residual *p, void *dst, size_t dst_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

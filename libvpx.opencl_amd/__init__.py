@@ -416,6 +416,33 @@ def side_sizes(gw, gh, mv_dtype=SIDE_I16, planes=("ref", "mode", "skip")):
     return int(L.vp8hip_side_mv_size(None, ctypes.byref(p))), int(L.vp8hip_side_info_size(None, ctypes.byref(p)))
 
 
+RES_LAYOUTS = {"i420": 0, "planar": 1}                        # VP8HIP_RES_I420, PLANAR
+RES_I16, RES_F16, RES_F32 = 0, 1, 2
+
+
+def _res_dtype(dtype):
+    if isinstance(dtype, int):
+        return dtype if dtype in (RES_I16, RES_F16, RES_F32) else None
+    return {"int16": RES_I16, "float16": RES_F16, "float32": RES_F32}.get(str(dtype).split(".")[-1])
+
+
+def residual_sizes(gw, gh, dtype=RES_I16, layout="planar"):
+    """bytes of one frame's tensor of Vp8Hip.frames_residual on a grid of gw x gh (vp8hip_residual_size): 3 * gh * gw elements
+    ("planar") or gh * gw + 2 * ((gh + 1) / 2) * ((gw + 1) / 2) ("i420"); 0 for a size outside 1..16383, an unknown type or layout.
+    For the native grid gw, gh = 16 * mb_cols, 16 * mb_rows."""
+    dt = _res_dtype(dtype)
+    if dt is None or layout not in RES_LAYOUTS or gw == 0 or gh == 0:       # (0 x 0 would ask for the native grid, which needs a context)
+        return 0
+    p = ResidualParams(int(gw), int(gh), RES_LAYOUTS[layout], dt)
+    return int(load_hip().vp8hip_residual_size(None, ctypes.byref(p)))
+
+
+def split_residual(t, gw, gh):
+    """Y [.., gh, gw], U and V [.., (gh + 1) / 2, (gw + 1) / 2] views of "i420" residual frames t [..., elements] (numpy or torch),
+    as split_i420 splits pictures"""
+    return split_i420(t, gw, gh)
+
+
 # ------------------------------------------------------------------------------------------
 # HIP pixel path (vp8hip.h)
 # ------------------------------------------------------------------------------------------
@@ -438,6 +465,10 @@ class RgbParams(ctypes.Structure):          # vp8hip_rgb, include/vp8hip.h
 
 class SideParams(ctypes.Structure):         # vp8hip_side, include/vp8hip.h
     _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("mv_dtype", c_int), ("planes", ctypes.c_uint), ("scale", ctypes.c_float * 2)]
+
+
+class ResidualParams(ctypes.Structure):     # vp8hip_residual, include/vp8hip.h
+    _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("layout", c_int), ("dtype", c_int), ("scale", ctypes.c_float * 3)]
 
 
 class VisParams(ctypes.Structure):          # vp8hip_vis, include/vp8hip.h
@@ -498,6 +529,9 @@ def load_hip():
         L.vp8hip_side_info_size.argtypes = [c_void_p, ctypes.POINTER(SideParams)]
         L.vp8hip_side_info_size.restype = c_size_t
         L.vp8hip_frames_side_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(SideParams), c_void_p, c_size_t, c_void_p, c_size_t]
+        L.vp8hip_residual_size.argtypes = [c_void_p, ctypes.POINTER(ResidualParams)]
+        L.vp8hip_residual_size.restype = c_size_t
+        L.vp8hip_frames_residual_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(ResidualParams), c_void_p, c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -857,6 +891,52 @@ class Vp8Hip:
             c_void_p(mv.data_ptr()) if mv is not None else None, mv.stride(0) * mv.element_size() if mv is not None else 0,
             c_void_p(info.data_ptr()) if info is not None else None, info.stride(0) if info is not None else 0), "vp8hip_frames_side_async")
         return mv, info
+
+    def frames_residual(self, slots, width=None, height=None, dtype=None, layout="planar", scale=None, out=None):
+        """IR slots `slots` (any order, repeats allowed) as residual tensors on the context's device
+        (vp8hip_frames_residual_async): what the stream adds to the prediction, before the clamp, as include/vp8hip.h defines
+        it.  layout "planar": [n, 3, gh, gw], chroma replicated, sample for sample frames_rgb's "nchw" tensor at that size;
+        "i420": a flat [n, elements], the three planes at their own sizes (split_residual gives the views).  torch.int16 (the
+        default), torch.float16 or torch.float32; float types: float32(float64(v) * scale[c]) with scale = one number or (Y, U,
+        V), float32 (default 1).  With no size the native grid: the coded area, gw, gh = 16 * mb_cols, 16 * mb_rows; with width
+        x height the sample under each output's centre, at the display size a crop.  `out`: a tensor of that shape and type,
+        each frame dense, stride(0) free.  Stream ordering, the `import torch` first rule and the remark on record_stream: as
+        frames_scaled."""
+        import torch
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        native = width is None and height is None
+        if not native and (width is None or height is None):
+            raise ValueError("frames_residual: width and height, or neither")
+        gw = self.g.aligned_w if native else int(width)
+        gh = self.g.aligned_h if native else int(height)
+        dtype = torch.int16 if dtype is None else dtype
+        dt = _res_dtype(dtype)
+        if dt is None or layout not in RES_LAYOUTS:
+            raise ValueError(f"frames_residual: dtype {dtype}, layout {layout!r}")
+        if scale is None:
+            sc = (1.0, 1.0, 1.0)
+        elif np.ndim(scale) == 0:
+            sc = (float(scale),) * 3
+        else:
+            sc = tuple(float(v) for v in scale)
+            if len(sc) != 3:
+                raise ValueError(f"frames_residual: scale {scale!r}")
+        p = ResidualParams(0 if native else gw, 0 if native else gh, RES_LAYOUTS[layout], dt)
+        for c in range(3):
+            p.scale[c] = np.float32(sc[c])
+        size = int(self.L.vp8hip_residual_size(self.h, ctypes.byref(p)))
+        if not size:
+            raise ValueError(f"frames_residual: grid {gw}x{gh}: refused (sizes 1..16383)")
+        name = ("int16", "float16", "float32")[dt]
+        shape = (3, gh, gw) if layout == "planar" else (size // (2, 2, 4)[dt],)
+
+        def ok(torch, out, dev):
+            return out.dtype == getattr(torch, name) and tuple(out.shape) == (n,) + shape and (n == 0 or out[0].is_contiguous()) and out.device == dev
+        return self._to_torch("frames_residual", n, name, shape, out, ok, f"a {name} tensor {[n] + list(shape)}, each frame dense",
+                              lambda arr_out, stride: self.L.vp8hip_frames_residual_async(
+                                  self.h, (c_int * max(n, 1))(*slots), n, ctypes.byref(p), arr_out, stride),
+                              "vp8hip_frames_residual_async")
 
     def rgb_scratch_bytes(self):
         """device bytes of frames_rgb's scratch (vp8hip_rgb_scratch_bytes): a chunk of scaled frames as packed I420; a cache"""

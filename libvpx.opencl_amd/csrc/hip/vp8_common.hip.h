@@ -103,6 +103,32 @@ struct SideLaunch {
     unsigned q[SIDE_MAX_FRAMES];  // ... its header: the quantiser index of segment s in bits 7s .. 7s + 6, bit 28 = key frame
 };
 
+// One launch of vp8hip_frames_residual_async (vp8_residual.hip), as the host's plan (vp8hip_residual.hip: residual_plan) left it
+#define RES_I16 0                 // vp8hip_residual::dtype
+#define RES_F16 1
+#define RES_F32 2
+#define RES_I420 0                // vp8hip_residual::layout
+#define RES_PLANAR 1
+#define RES_RUN 16                // macroblocks of a workgroup: a run of one macroblock row (records 2 KB + image 12.5 KB of LDS)
+#define RES_MAX_FRAMES 128        // slots per launch (kernel arguments: 16 bytes each)
+struct ResSlot {                  // what the kernel needs of a slot and its header as of the call
+    int slot;
+    unsigned q;                   // the quantiser index of segment s in bits 7s .. 7s + 6 (mb_init_dequantizer)
+    unsigned d0, d1;              // y1dc, y2dc, y2ac, uvdc _delta_q as bytes of d0; uvac_delta_q in the low byte of d1
+};
+struct ResLaunch {
+    int gw, gh;                   // the luma grid
+    int dw, dh;                   // the size it is laid over: the display size, or the coded size for the native grid
+    int cw, ch, dcw, dch;         // I420: the chroma grid and the size it is laid over
+    int mb_cols, mb_rows;
+    int runs;                     // runs of a macroblock row: (mb_cols + RES_RUN - 1) / RES_RUN
+    int S;                        // workgroups that share the output rows of a run (gridDim.x = mb_rows * runs * S)
+    int layout;                   // RES_*
+    int y_vec, c_vec;             // every whole group of four of a luma / chroma plane is one aligned piece
+    float scale[3];               // Y, U, V; float types
+    ResSlot s[RES_MAX_FRAMES];
+};
+
 #define WAVE 64
 
 // Macroblock tiles of the one-MB-row-per-lane pipeline (vp8_keyframe_simt.hip has the layout): three 128-byte lines per macroblock.
