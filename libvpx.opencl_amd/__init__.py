@@ -371,26 +371,26 @@ RGB_U8, RGB_F16, RGB_F32 = 0, 1, 2
 def rgb_size(w, h, layout="nchw", dtype=RGB_U8):
     """bytes of one frame of Vp8Hip.frames_rgb (vp8hip_rgb_size): w * h * channels * element size; 0 for a size outside 1..16383,
     an unknown layout / type, or "nhwc4" with a float type.  dtype: RGB_U8 / RGB_F16 / RGB_F32 or the torch / numpy type's name"""
-    dt = _rgb_dtype(dtype)
+    dt = _elem_dtype(dtype, _RGB_DTYPES)
     if layout not in RGB_LAYOUTS or dt is None or not (1 <= w <= 16383 and 1 <= h <= 16383) or (layout == "nhwc4" and dt != RGB_U8):
         return 0
     return w * h * (4 if layout == "nhwc4" else 3) * (1, 2, 4)[dt]
 
 
-def _rgb_dtype(dtype):
+_RGB_DTYPES = ("uint8", "float16", "float32")                 # by RGB_U8, RGB_F16, RGB_F32
+_INT16_DTYPES = ("int16", "float16", "float32")                # by SIDE_I16 ... and RES_I16 ...
+
+
+def _elem_dtype(dtype, names):
+    """a tensor type's number -- itself, or the torch / numpy type's name looked up in `names` -- or None for one that is not there"""
     if isinstance(dtype, int):
-        return dtype if dtype in (RGB_U8, RGB_F16, RGB_F32) else None
-    return {"uint8": RGB_U8, "float16": RGB_F16, "float32": RGB_F32}.get(str(dtype).split(".")[-1])
+        return dtype if 0 <= dtype < len(names) else None
+    name = str(dtype).split(".")[-1]
+    return names.index(name) if name in names else None
 
 
 SIDE_PLANES = {"ref": 1, "mode": 2, "skip": 4, "segment": 8, "qindex": 16, "coded": 32}      # VP8HIP_SIDE_*: bit order = plane order
 SIDE_I16, SIDE_F16, SIDE_F32 = 0, 1, 2
-
-
-def _side_dtype(dtype):
-    if isinstance(dtype, int):
-        return dtype if dtype in (SIDE_I16, SIDE_F16, SIDE_F32) else None
-    return {"int16": SIDE_I16, "float16": SIDE_F16, "float32": SIDE_F32}.get(str(dtype).split(".")[-1])
 
 
 def _side_planes(planes):
@@ -409,7 +409,7 @@ def side_sizes(gw, gh, mv_dtype=SIDE_I16, planes=("ref", "mode", "skip")):
     """(bytes of one frame's mv tensor, bytes of its info tensor) of Vp8Hip.frames_side on a grid of gw x gh (vp8hip_side_mv_size,
     vp8hip_side_info_size): 2 * gh * gw * element size and planes * gh * gw; (0, 0) for a size outside 1..16383, an unknown type or
     plane.  For the native grid gw, gh = 4 * mb_cols, 4 * mb_rows."""
-    dt, mask = _side_dtype(mv_dtype), _side_planes(planes)
+    dt, mask = _elem_dtype(mv_dtype, _INT16_DTYPES), _side_planes(planes)
     if dt is None or mask is None or gw == 0 or gh == 0:         # (0 x 0 would ask for the native grid, which needs a context)
         return 0, 0
     L, p = load_hip(), SideParams(int(gw), int(gh), dt, mask)
@@ -420,17 +420,11 @@ RES_LAYOUTS = {"i420": 0, "planar": 1}                        # VP8HIP_RES_I420,
 RES_I16, RES_F16, RES_F32 = 0, 1, 2
 
 
-def _res_dtype(dtype):
-    if isinstance(dtype, int):
-        return dtype if dtype in (RES_I16, RES_F16, RES_F32) else None
-    return {"int16": RES_I16, "float16": RES_F16, "float32": RES_F32}.get(str(dtype).split(".")[-1])
-
-
 def residual_sizes(gw, gh, dtype=RES_I16, layout="planar"):
     """bytes of one frame's tensor of Vp8Hip.frames_residual on a grid of gw x gh (vp8hip_residual_size): 3 * gh * gw elements
     ("planar") or gh * gw + 2 * ((gh + 1) / 2) * ((gw + 1) / 2) ("i420"); 0 for a size outside 1..16383, an unknown type or layout.
     For the native grid gw, gh = 16 * mb_cols, 16 * mb_rows."""
-    dt = _res_dtype(dtype)
+    dt = _elem_dtype(dtype, _INT16_DTYPES)
     if dt is None or layout not in RES_LAYOUTS or gw == 0 or gh == 0:       # (0 x 0 would ask for the native grid, which needs a context)
         return 0
     p = ResidualParams(int(gw), int(gh), RES_LAYOUTS[layout], dt)
@@ -753,24 +747,44 @@ class Vp8Hip:
         h = self.height if height is None else int(height)
         size = int(self.L.vp8hip_i420_size(w, h))
 
-        def ok(torch, out, dev):
-            return out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == len(fbs) and out.shape[1] == size and out.stride(1) == 1 \
+        def ok(out, dtype, shape, dev):
+            return out.dtype == dtype and out.dim() == 2 and out.shape[0] == len(fbs) and out.shape[1] == size and out.stride(1) == 1 \
                 and out.device == dev
-        return self._to_torch("frames_scaled", len(fbs), "uint8", (size,), out, ok, f"a uint8 tensor [{len(fbs)}, {size}] with stride(1) == 1",
+        return self._to_torch("frames_scaled", [("out", out, "uint8", (len(fbs), size))],
                               lambda arr_out, stride: self.L.vp8hip_frames_scale_async(
                                   self.h, (c_int * max(len(fbs), 1))(*fbs), len(fbs), w, h, int(filter), arr_out, stride),
-                              "vp8hip_frames_scale_async")
+                              "vp8hip_frames_scale_async", ok, "with stride(1) == 1")[0]
 
-    def _to_torch(self, who, n, dtype, shape, out, ok, want, call, what):
-        """The torch side of a hand-over on the device (frames_scaled, frames_rgb): `out` (made here when None: [n, *shape] of
-        `dtype`) checked with ok(torch, out, device), then call(data pointer, frame stride in bytes) between the two stream waits."""
+    @staticmethod
+    def _dense(t, dtype, shape, dev):
+        """t is a tensor of this type and shape [n, ...] on this device, each frame dense (stride(0) free)"""
+        return t.dtype == dtype and tuple(t.shape) == tuple(shape) and (shape[0] == 0 or t[0].is_contiguous()) and t.device == dev
+
+    def _to_torch(self, who, outs, call, what, ok=None, how="each frame dense"):
+        """The torch side of a hand-over on the device (frames_scaled, frames_rgb, frames_side, frames_residual).  outs: one or two
+        of (the argument's name, the caller's tensor or None, the type's name, the shape [n, ...]); a tensor is made here when
+        None and checked otherwise (ok: _dense).  Then call(data pointer, frame stride in bytes -- and the same of the second
+        tensor) between the two stream waits.  Returns the tensors."""
         torch, dev = self._torch_device(who)
-        if out is None:
-            out = torch.empty((n,) + tuple(shape), dtype=getattr(torch, dtype), device=dev)
-        if not ok(torch, out, dev):
-            raise ValueError(f"{who}: out must be {want} on {dev}")
-        self._between_stream_waits(dev, lambda: call(c_void_p(out.data_ptr()), out.stride(0) * out.element_size()), what)
-        return out
+        made = []
+        for arg, out, name, shape in outs:
+            if out is None:
+                out = torch.empty(tuple(shape), dtype=getattr(torch, name), device=dev)
+            if not (ok or self._dense)(out, getattr(torch, name), shape, dev):
+                raise ValueError(f"{who}: {arg} must be a {name} tensor {list(shape)}, {how}, on {dev}")
+            made.append(out)
+        args = [a for t in made for a in (c_void_p(t.data_ptr()), t.stride(0) * t.element_size())]
+        self._between_stream_waits(dev, lambda: call(*args), what)
+        return made
+
+    def _grid(self, who, width, height, cells):
+        """-> (native, gw, gh): the output grid of width x height, or with neither the native one, `cells` a macroblock each way"""
+        native = width is None and height is None
+        if not native and (width is None or height is None):
+            raise ValueError(f"{who}: width and height, or neither")
+        if native:
+            return True, cells * (self.g.aligned_w // 16), cells * (self.g.aligned_h // 16)
+        return False, int(width), int(height)
 
     def _torch_device(self, who):
         """-> (torch, the context's device as torch names it); refuses when torch came after the library"""
@@ -809,7 +823,7 @@ class Vp8Hip:
         w = self.width if width is None else int(width)
         h = self.height if height is None else int(height)
         dtype = torch.uint8 if dtype is None else dtype
-        dt = _rgb_dtype(dtype)
+        dt = _elem_dtype(dtype, _RGB_DTYPES)
         if dt is None or layout not in RGB_LAYOUTS or order not in RGB_ORDERS or matrix not in RGB_MATRICES:
             raise ValueError(f"frames_rgb: dtype {dtype}, layout {layout!r}, order {order!r}, matrix {matrix!r}")
         mean = np.zeros(3) if mean is None else np.asarray(mean, np.float64).reshape(3)
@@ -821,14 +835,10 @@ class Vp8Hip:
         if not self.L.vp8hip_rgb_size(ctypes.byref(p)):
             raise ValueError(f"frames_rgb: {w}x{h}, filter {filter}, {dtype}, layout {layout!r}: refused (sizes 1..16383; nhwc4 is uint8 only)")
         shape = (3, h, w) if layout == "nchw" else (h, w, 3 if layout == "nhwc" else 4)
-        name = ("uint8", "float16", "float32")[dt]
-
-        def ok(torch, out, dev):
-            return out.dtype == getattr(torch, name) and tuple(out.shape) == (len(fbs),) + shape and (not fbs or out[0].is_contiguous()) and out.device == dev
-        return self._to_torch("frames_rgb", len(fbs), name, shape, out, ok, f"a {name} tensor {[len(fbs)] + list(shape)}, each frame dense",
+        return self._to_torch("frames_rgb", [("out", out, _RGB_DTYPES[dt], (len(fbs),) + shape)],
                               lambda arr_out, stride: self.L.vp8hip_frames_rgb_async(
                                   self.h, (c_int * max(len(fbs), 1))(*fbs), len(fbs), ctypes.byref(p), arr_out, stride),
-                              "vp8hip_frames_rgb_async")
+                              "vp8hip_frames_rgb_async")[0]
 
     def frames_side(self, slots, width=None, height=None, mv_dtype=None, planes=("ref", "mode", "skip"), scale=None, out_mv=None,
                     out_info=None):
@@ -842,16 +852,12 @@ class Vp8Hip:
         pixels of the tensor (native grid: d_w, d_h = the coded size).  planes=() gives info None, and out_mv=False / out_info=False
         skip that tensor; a tensor passed as out_mv / out_info is filled (each frame dense, stride(0) free).  Stream ordering, the
         `import torch` first rule and the remark on record_stream: as frames_scaled."""
-        torch, dev = self._torch_device("frames_side")
+        torch = self._torch_device("frames_side")[0]
         slots = [int(s) for s in slots]
         n = len(slots)
-        native = width is None and height is None
-        if not native and (width is None or height is None):
-            raise ValueError("frames_side: width and height, or neither")
-        gw = 4 * (self.g.aligned_w // 16) if native else int(width)
-        gh = 4 * (self.g.aligned_h // 16) if native else int(height)
+        native, gw, gh = self._grid("frames_side", width, height, 4)
         mv_dtype = torch.int16 if mv_dtype is None else mv_dtype
-        dt, mask = _side_dtype(mv_dtype), _side_planes(planes)
+        dt, mask = _elem_dtype(mv_dtype, _INT16_DTYPES), _side_planes(planes)
         if dt is None or mask is None:
             raise ValueError(f"frames_side: mv_dtype {mv_dtype}, planes {planes!r}")
         want_mv = out_mv is not False
@@ -871,26 +877,17 @@ class Vp8Hip:
         p.scale[0], p.scale[1] = np.float32(sc[0]), np.float32(sc[1])
         if not self.L.vp8hip_side_mv_size(self.h, ctypes.byref(p)):
             raise ValueError(f"frames_side: grid {gw}x{gh}: refused (sizes 1..16383)")
-        name = ("int16", "float16", "float32")[dt]
         nc = bin(mask).count("1")
-        if want_mv and out_mv is None:
-            out_mv = torch.empty((n, 2, gh, gw), dtype=getattr(torch, name), device=dev)
-        if want_info and out_info is None:
-            out_info = torch.empty((n, nc, gh, gw), dtype=torch.uint8, device=dev)
-        mv = out_mv if want_mv else None
-        info = out_info if want_info else None
+        outs = [("out_mv", out_mv, _INT16_DTYPES[dt], (n, 2, gh, gw))] if want_mv else []
+        if want_info:
+            outs.append(("out_info", out_info, "uint8", (n, nc, gh, gw)))
+        none = (None, 0)
 
-        def dense(t, dtype, ch):
-            return t.dtype == dtype and tuple(t.shape) == (n, ch, gh, gw) and (n == 0 or t[0].is_contiguous()) and t.device == dev
-        if mv is not None and not dense(mv, getattr(torch, name), 2):
-            raise ValueError(f"frames_side: out_mv must be a {name} tensor {[n, 2, gh, gw]}, each frame dense, on {dev}")
-        if info is not None and not dense(info, torch.uint8, nc):
-            raise ValueError(f"frames_side: out_info must be a uint8 tensor {[n, nc, gh, gw]}, each frame dense, on {dev}")
-        self._between_stream_waits(dev, lambda: self.L.vp8hip_frames_side_async(
-            self.h, (c_int * max(n, 1))(*slots), n, ctypes.byref(p),
-            c_void_p(mv.data_ptr()) if mv is not None else None, mv.stride(0) * mv.element_size() if mv is not None else 0,
-            c_void_p(info.data_ptr()) if info is not None else None, info.stride(0) if info is not None else 0), "vp8hip_frames_side_async")
-        return mv, info
+        def call(*args):        # (pointer and stride of each tensor asked for)
+            mv, info = (args[:2] if want_mv else none), (args[-2:] if want_info else none)
+            return self.L.vp8hip_frames_side_async(self.h, (c_int * max(n, 1))(*slots), n, ctypes.byref(p), *mv, *info)
+        made = self._to_torch("frames_side", outs, call, "vp8hip_frames_side_async")
+        return made[0] if want_mv else None, made[-1] if want_info else None
 
     def frames_residual(self, slots, width=None, height=None, dtype=None, layout="planar", scale=None, out=None):
         """IR slots `slots` (any order, repeats allowed) as residual tensors on the context's device
@@ -905,13 +902,9 @@ class Vp8Hip:
         import torch
         slots = [int(s) for s in slots]
         n = len(slots)
-        native = width is None and height is None
-        if not native and (width is None or height is None):
-            raise ValueError("frames_residual: width and height, or neither")
-        gw = self.g.aligned_w if native else int(width)
-        gh = self.g.aligned_h if native else int(height)
+        native, gw, gh = self._grid("frames_residual", width, height, 16)
         dtype = torch.int16 if dtype is None else dtype
-        dt = _res_dtype(dtype)
+        dt = _elem_dtype(dtype, _INT16_DTYPES)
         if dt is None or layout not in RES_LAYOUTS:
             raise ValueError(f"frames_residual: dtype {dtype}, layout {layout!r}")
         if scale is None:
@@ -928,15 +921,11 @@ class Vp8Hip:
         size = int(self.L.vp8hip_residual_size(self.h, ctypes.byref(p)))
         if not size:
             raise ValueError(f"frames_residual: grid {gw}x{gh}: refused (sizes 1..16383)")
-        name = ("int16", "float16", "float32")[dt]
         shape = (3, gh, gw) if layout == "planar" else (size // (2, 2, 4)[dt],)
-
-        def ok(torch, out, dev):
-            return out.dtype == getattr(torch, name) and tuple(out.shape) == (n,) + shape and (n == 0 or out[0].is_contiguous()) and out.device == dev
-        return self._to_torch("frames_residual", n, name, shape, out, ok, f"a {name} tensor {[n] + list(shape)}, each frame dense",
+        return self._to_torch("frames_residual", [("out", out, _INT16_DTYPES[dt], (n,) + shape)],
                               lambda arr_out, stride: self.L.vp8hip_frames_residual_async(
                                   self.h, (c_int * max(n, 1))(*slots), n, ctypes.byref(p), arr_out, stride),
-                              "vp8hip_frames_residual_async")
+                              "vp8hip_frames_residual_async")[0]
 
     def rgb_scratch_bytes(self):
         """device bytes of frames_rgb's scratch (vp8hip_rgb_scratch_bytes): a chunk of scaled frames as packed I420; a cache"""

@@ -81,10 +81,12 @@ struct RgbLaunch {
     int fb[SCALE_MAX_FRAMES];     // frame buffer << 2 | form (SCALE_FROM_*); SCALE_FROM_PACKED: frame k of the launch is image k of the scratch
 };
 
+// The element types of the tensors the side and residual kernels write (vp8_tensor_out.hip.h): vp8hip_side::mv_dtype, vp8hip_residual::dtype
+#define TENSOR_I16 0
+#define TENSOR_F16 1
+#define TENSOR_F32 2
+
 // One launch of vp8hip_frames_side_async (vp8_side.hip), as the host's plan (vp8hip_side.hip: side_plan) left it
-#define SIDE_I16 0                // vp8hip_side::mv_dtype
-#define SIDE_F16 1
-#define SIDE_F32 2
 #define SIDE_MAX_FRAMES 256       // slots per launch (kernel arguments)
 #define SIDE_X_ANY 0              // SideLaunch::xmode: sx by the division; ...
 #define SIDE_X_DISPLAY 1          // ... gw is the display width: the four outputs of a group share the cell x >> 2; ...
@@ -104,9 +106,6 @@ struct SideLaunch {
 };
 
 // One launch of vp8hip_frames_residual_async (vp8_residual.hip), as the host's plan (vp8hip_residual.hip: residual_plan) left it
-#define RES_I16 0                 // vp8hip_residual::dtype
-#define RES_F16 1
-#define RES_F32 2
 #define RES_I420 0                // vp8hip_residual::layout
 #define RES_PLANAR 1
 #define RES_RUN 16                // macroblocks of a workgroup: a run of one macroblock row (records 2 KB + image 12.5 KB of LDS)

@@ -12,18 +12,12 @@
 //      otherwise (dc + 4) >> 3 from the record alone.  Sixteen int16 into the run's image in LDS: Y 16 rows, U and V 8 rows each,
 //      768 bytes a macroblock (and 16 bytes of padding a row).
 //   3. output  a lane makes four neighbouring outputs of a plane from the image and stores them as one piece, neighbouring lanes
-//      contiguous: 8 bytes of int16 / halves, 16 of floats.  A group of four that a run's edge cuts, a width that is no multiple of 4
-//      or a destination not aligned to the piece: element by element, each exactly once, none outside the frame.
-// Integer and conversion arithmetic only (the one product, value x scale, is a single-precision multiply: the exact product rounded
-// once, the definition's).
-#include <hip/hip_fp16.h>
+//      contiguous, or -- a group of four that a run's edge cuts -- the run's own by themselves (tensor_store4, vp8_tensor_out.hip.h,
+//      which also has the grid map and its inverse, the walk and value x scale).
+// Integer and conversion arithmetic only.
 #include "vp8_simt_prims.hip.h"
+#include "vp8_tensor_out.hip.h"
 #include "vp8hip.h"
-
-template <int DTYPE> struct ResElem;
-template <> struct ResElem<RES_I16> { typedef unsigned short T; };
-template <> struct ResElem<RES_F16> { typedef unsigned short T; };
-template <> struct ResElem<RES_F32> { typedef unsigned int T; };
 
 // rows of the image in LDS, in samples: 16 bytes of padding each, so that the four block rows of a macroblock, which a lane per
 // block writes at once, fall on different banks (without it their rows lie a multiple of 128 bytes apart)
@@ -34,13 +28,6 @@ template <> struct ResElem<RES_F32> { typedef unsigned int T; };
 // dwords of a staged record the transform phase writes: the record's reserved tail
 #define RES_W_DQ 28                // three dwords: y1dc | y1ac << 16, y2dc | y2ac << 16, uvdc | uvac << 16
 #define RES_W_MASK 31              // bit k: block k has 32 bytes in the stream (eobs[k] > 1, macroblock not skipped)
-
-// the first output whose source sample is T or beyond: ((2y + 1) * d) / (2g) >= T  <=>  (2y + 1) * d >= 2 * g * T
-__device__ __forceinline__ int res_first(int T, int g, int d)
-{
-    const int num = 2 * g * T - d;               // (T <= 16384, g <= 16383: below 2^30)
-    return num <= 0 ? 0 : min((num + 2 * d - 1) / (2 * d), g);
-}
 
 __device__ __forceinline__ int res_qi(int q, unsigned delta_byte)
 {
@@ -139,19 +126,6 @@ __device__ __forceinline__ void res_block(const unsigned *rec, int mb, int k, co
     }
 }
 
-template <int DTYPE>
-__device__ __forceinline__ unsigned res_value(int v, float scale)
-{
-    if constexpr (DTYPE == RES_I16) return (unsigned)v & 0xffffu;
-    else {
-        // (float)((double)v * (double)scale): the product of an int16 and a float is exact in double, so this is that product
-        // rounded once -- which is what the single-precision multiply gives (denormal results kept: the kernels' float mode)
-        const float f = __fmul_rn((float)v, scale);
-        if constexpr (DTYPE == RES_F32) return __float_as_uint(f);
-        else return (unsigned)__half_as_ushort(__float2half_rn(f));
-    }
-}
-
 struct ResPlane {
     const short *img;                            // the plane's image in LDS, row stride `stride` shorts
     int stride, shift;                           // shift 1: chroma under a luma sample (planar layout)
@@ -165,25 +139,23 @@ template <int DTYPE, int NP>
 __device__ __forceinline__ void res_emit(const ResPlane (&pl)[NP], int g_w, int g_h, int d_w, int d_h, int y0, int y1, int xa, int xb, int row0, int col0,
                                          int w, int h, bool vec)
 {
-    typedef typename ResElem<DTYPE>::T elem_t;
+    typedef typename TensorElem<DTYPE>::T elem_t;
     constexpr int ES = (int)sizeof(elem_t);
     if (y0 >= y1 || xa >= xb) return;
     const bool identx = g_w == d_w, identy = g_h == d_h;
-    const int q0 = xa >> 2, nq = ((xb + 3) >> 2) - q0;              // groups of four outputs the columns touch
-    const int adv_rows = 256 / nq, adv_cols = 256 - adv_rows * nq;  // a lane's step of 256 groups
-    const int nrows = y1 - y0;
-    int row = (int)threadIdx.x / nq, col = (int)threadIdx.x - row * nq;
+    const int q0 = xa >> 2, nrows = y1 - y0;
+    TensorWalk t(((xb + 3) >> 2) - q0);                             // over the groups of four outputs the columns touch
 #pragma unroll 1
-    while (row < nrows) {
-        const int y = y0 + row, x = (q0 + col) << 2;
-        const int sy = identy ? y : (int)(((unsigned)(2 * y + 1) * (unsigned)d_h) / (unsigned)(2 * g_h));
+    for (; t.row < nrows; t.next()) {
+        const int y = y0 + t.row, x = (q0 + t.col) << 2;
+        const int sy = identy ? y : tensor_src(y, g_h, d_h);
         const int ly = min(max(sy - row0, 0), h - 1);
         const bool whole = x >= xa && x + 4 <= xb;
         int lx[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int xi = min(max(x + i, xa), xb - 1);
-            const int sx = identx ? xi : (int)(((unsigned)(2 * xi + 1) * (unsigned)d_w) / (unsigned)(2 * g_w));
+            const int sx = identx ? xi : tensor_src(xi, g_w, d_w);
             lx[i] = min(max(sx - col0, 0), w - 1);
         }
         const size_t pix = (size_t)y * g_w + x;
@@ -205,36 +177,23 @@ __device__ __forceinline__ void res_emit(const ResPlane (&pl)[NP], int g_w, int 
             }
             unsigned e[4];
 #pragma unroll
-            for (int i = 0; i < 4; i++) e[i] = res_value<DTYPE>(v[i], pl[p].scale);
+            for (int i = 0; i < 4; i++) e[i] = tensor_value<DTYPE>(v[i], pl[p].scale);
             uint8_t *o = pl[p].dst + pix * ES;
-            if (vec && whole) {
-                if constexpr (ES == 2) *(GLOBAL_AS u32x2 *)o = u32x2{ e[0] | e[1] << 16, e[2] | e[3] << 16 };
-                else *(GLOBAL_AS u32x4 *)o = u32x4{ e[0], e[1], e[2], e[3] };
-            } else {
+            if (vec && whole) tensor_store4<ES>(o, e);
+            else {
 #pragma unroll
                 for (int i = 0; i < 4; i++)
                     if (x + i >= xa && x + i < xb) ((GLOBAL_AS elem_t *)o)[i] = (elem_t)e[i];
             }
         }
-        col += adv_cols;
-        row += adv_rows;
-        if (col >= nq) { col -= nq; row++; }
     }
-}
-
-// rows a .. b - 1 shared by S workgroups: the share of number `part`
-__device__ __forceinline__ void res_share(int a, int b, int S, int part, int &y0, int &y1)
-{
-    const int per = (b - a + S - 1) / S;
-    y0 = a + part * per;
-    y1 = min(b, y0 + per);
 }
 
 template <int DTYPE>
 __device__ __forceinline__ void res_body(const char *__restrict__ slot_base, size_t slot_bytes, size_t o_mbx, size_t o_blocks, const char *__restrict__ pool,
                                          unsigned cap_blocks, uint8_t *__restrict__ dst, size_t dst_stride, const ResLaunch &L)
 {
-    constexpr int ES = (int)sizeof(typename ResElem<DTYPE>::T);
+    constexpr int ES = (int)sizeof(typename TensorElem<DTYPE>::T);
     __shared__ __attribute__((aligned(16))) unsigned lrec[RES_REC_WORDS];
     __shared__ __attribute__((aligned(16))) short img[RES_IMG];
     const int f = (int)blockIdx.y;
@@ -246,12 +205,12 @@ __device__ __forceinline__ void res_body(const char *__restrict__ slot_base, siz
 
     // the outputs of the run: luma (planar: all three planes), and the chroma planes of the I420 layout
     int y0, y1, cy0 = 0, cy1 = 0, cxa = 0, cxb = 0;
-    res_share(res_first(16 * m, gh, L.dh), last_row ? gh : res_first(16 * (m + 1), gh, L.dh), L.S, part, y0, y1);
-    const int xa = res_first(16 * c0, gw, L.dw), xb = last_run ? gw : res_first(16 * c1, gw, L.dw);
+    tensor_share(tensor_first(16 * m, gh, L.dh), last_row ? gh : tensor_first(16 * (m + 1), gh, L.dh), L.S, part, y0, y1);
+    const int xa = tensor_first(16 * c0, gw, L.dw), xb = last_run ? gw : tensor_first(16 * c1, gw, L.dw);
     if (!planar) {
-        res_share(res_first(8 * m, L.ch, L.dch), last_row ? L.ch : res_first(8 * (m + 1), L.ch, L.dch), L.S, part, cy0, cy1);
-        cxa = res_first(8 * c0, L.cw, L.dcw);
-        cxb = last_run ? L.cw : res_first(8 * c1, L.cw, L.dcw);
+        tensor_share(tensor_first(8 * m, L.ch, L.dch), last_row ? L.ch : tensor_first(8 * (m + 1), L.ch, L.dch), L.S, part, cy0, cy1);
+        cxa = tensor_first(8 * c0, L.cw, L.dcw);
+        cxb = last_run ? L.cw : tensor_first(8 * c1, L.cw, L.dcw);
     }
     if ((y0 >= y1 || xa >= xb) && (cy0 >= cy1 || cxa >= cxb)) return;         // (no output falls into the run: a grid much smaller than the frame)
 
@@ -299,6 +258,6 @@ __device__ __forceinline__ void res_body(const char *__restrict__ slot_base, siz
     {                                                                                                                                        \
         res_body<DTYPE>(slot_base, slot_bytes, o_mbx, o_blocks, pool, cap_blocks, dst, dst_stride, L);                                       \
     }
-RES_KERNEL(vp8_residual_i16_kernel, RES_I16)
-RES_KERNEL(vp8_residual_f16_kernel, RES_F16)
-RES_KERNEL(vp8_residual_f32_kernel, RES_F32)
+RES_KERNEL(vp8_residual_i16_kernel, TENSOR_I16)
+RES_KERNEL(vp8_residual_f16_kernel, TENSOR_F16)
+RES_KERNEL(vp8_residual_f32_kernel, TENSOR_F32)

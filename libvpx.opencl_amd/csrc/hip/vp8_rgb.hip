@@ -8,13 +8,13 @@
 // 8-byte loads), or from the packed I420 image the scaler left in the call's scratch (dwords at the rows' own alignment).  Then a
 // lane makes four neighbouring pixels at a time: one LDS dword of Y, two bytes each of U and V, the chroma terms once per pixel
 // pair.  With vec set (width a multiple of 4, destination aligned to the piece) a lane's stores are whole pieces, neighbouring
-// lanes contiguous: a dword per plane (planar bytes), 8 / 16 bytes per plane (planar halves / floats), 12 bytes (packed bytes), 16
-// (four-byte pixels), 3 x 8 / 3 x 16 (packed halves / floats).  Otherwise -- odd widths, a tensor that starts on an odd byte --
+// lanes contiguous: a piece of four elements per plane (planar: tensor_store4, vp8_tensor_out.hip.h, which also has the walk), 12
+// bytes (packed bytes), 16 (four-byte pixels), 3 x 8 / 3 x 16 (packed halves / floats).  Otherwise -- odd widths, a tensor that starts on an odd byte --
 // every element is stored by itself: each exactly once, none outside the frame.  The matrix, the order of the channels (folded into
 // the coefficients by position) and the table are uniform arguments; layout and type are template parameters.  Integer and
 // conversion arithmetic only.
-#include <hip/hip_fp16.h>
 #include "vp8_scale_src.hip.h"
+#include "vp8_tensor_out.hip.h"
 
 typedef unsigned int u32x3_t __attribute__((ext_vector_type(3)));
 typedef unsigned int u32_any_t __attribute__((aligned(1)));
@@ -102,13 +102,11 @@ __device__ __forceinline__ void rgb_body(const uint8_t *__restrict__ raster, siz
     __syncthreads();
 
     uint8_t *D = dst + dst_stride * blockIdx.y;
-    const int nq = (w + 3) >> 2;                                    // groups of four pixels in a row
-    const int adv_rows = 256 / nq, adv_cols = 256 - adv_rows * nq;  // a lane's step of 256 groups
-    int row = (int)threadIdx.x / nq, col = (int)threadIdx.x - row * nq;
+    TensorWalk t((w + 3) >> 2);                                     // over the groups of four pixels in a row
     const unsigned short *lu16 = (const unsigned short *)lu, *lv16 = (const unsigned short *)lv;
 #pragma unroll 1
-    while (row < nrows) {
-        const int x = col << 2, y = y0 + row;
+    for (; t.row < nrows; t.next()) {
+        const int row = t.row, col = t.col, x = col << 2, y = y0 + row;
         const unsigned yw = ly[row * rwy + 1 + col];
         const int ci = (row >> 1) * (rwc << 1) + 2 + col;           // (y0 is even: the band's chroma row row >> 1; 2 bytes at byte 4 + x / 2)
         const unsigned ub = lu16[ci], vb = lv16[ci];
@@ -136,12 +134,7 @@ __device__ __forceinline__ void rgb_body(const uint8_t *__restrict__ raster, siz
         if (L.vec) {
             if constexpr (LAYOUT == RGB_PLANAR) {
 #pragma unroll
-                for (int p = 0; p < 3; p++) {
-                    uint8_t *o = D + ((size_t)p * h * w + pix) * ES;
-                    if constexpr (DTYPE == RGB_U8) *(g_u32p)o = v[p][0] | v[p][1] << 8 | v[p][2] << 16 | v[p][3] << 24;
-                    else if constexpr (DTYPE == RGB_F16) *(GLOBAL_AS u32x2_t *)o = u32x2_t{v[p][0] | v[p][1] << 16, v[p][2] | v[p][3] << 16};
-                    else *(GLOBAL_AS u32x4_t *)o = u32x4_t{v[p][0], v[p][1], v[p][2], v[p][3]};
-                }
+                for (int p = 0; p < 3; p++) tensor_store4<ES>(D + ((size_t)p * h * w + pix) * ES, v[p]);
             } else if constexpr (LAYOUT == RGB_PACKED3) {
                 uint8_t *o = D + pix * 3 * ES;
                 if constexpr (DTYPE == RGB_U8) {
@@ -178,9 +171,6 @@ __device__ __forceinline__ void rgb_body(const uint8_t *__restrict__ raster, siz
                 }
             }
         }
-        col += adv_cols;
-        row += adv_rows;
-        if (col >= nq) { col -= nq; row++; }
     }
 }
 

@@ -9,28 +9,11 @@
 // monotone: they are one range; S workgroups share it where a grid is much taller than the frame).  It stages the first 64 bytes
 // of each record -- the vp8ir_mb part -- and the rows' vectors into LDS with 16-byte loads (no vectors for a key frame: its vector
 // area is stale).  Then a lane makes four neighbouring outputs of every plane and stores each four as one piece, neighbouring
-// lanes contiguous: a dword of info bytes, 8 bytes of int16 / halves, 16 bytes of floats.  With mv_vec / info_vec clear -- a grid
-// width that is no multiple of 4, a destination not aligned to the piece -- every element is stored by itself: each exactly once,
-// none outside the frame.  Slot indices and the per-frame header bits travel in the kernel arguments.  Integer and conversion
-// arithmetic only (the one product, vector x scale, is a single-precision multiply: the exact product rounded once, the definition's).
-#include <hip/hip_fp16.h>
-#include "vp8_common.hip.h"
+// lanes contiguous (tensor_store4, vp8_tensor_out.hip.h, which also has the grid map, the walk and value x scale); with mv_vec /
+// info_vec clear that tensor takes no whole pieces and every element is stored by itself (the rule is stated there).  Slot indices and the per-frame header bits travel in the kernel arguments.
+// Integer and conversion arithmetic only.
+#include "vp8_tensor_out.hip.h"
 #include "vp8hip.h"
-
-typedef unsigned int side_x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int side_x2_t __attribute__((ext_vector_type(2)));
-
-template <int DTYPE> struct SideElem;
-template <> struct SideElem<SIDE_I16> { typedef unsigned short T; };
-template <> struct SideElem<SIDE_F16> { typedef unsigned short T; };
-template <> struct SideElem<SIDE_F32> { typedef unsigned int T; };
-
-// the first output row whose cell lies in macroblock row m or below it: sy >= 16 m  <=>  (2y + 1) * dh >= 32 * m * gh
-__device__ __forceinline__ int side_first_row(int m, int gh, int dh)
-{
-    const int num = 32 * m * gh - dh;            // (m <= 1024, gh <= 16383: below 2^30)
-    return num <= 0 ? 0 : min((num + 2 * dh - 1) / (2 * dh), gh);
-}
 
 struct SideCell {
     unsigned mv;                                 // row in the low half, col in the high one (vp8ir_mv)
@@ -61,43 +44,29 @@ __device__ __forceinline__ void side_cell(const unsigned *rec, const unsigned *m
 }
 
 template <int DTYPE>
-__device__ __forceinline__ unsigned side_value(int v, float scale)
-{
-    if constexpr (DTYPE == SIDE_I16) return (unsigned)v & 0xffffu;
-    else {
-        // (float)((double)v * (double)scale): the product of an int16 and a float is exact in double, so this is that product
-        // rounded once -- which is what the single-precision multiply gives (denormal results kept: the kernels' float mode)
-        const float f = __fmul_rn((float)v, scale);
-        if constexpr (DTYPE == SIDE_F32) return __float_as_uint(f);
-        else return (unsigned)__half_as_ushort(__float2half_rn(f));
-    }
-}
-
-template <int DTYPE>
 __device__ __forceinline__ void side_body(const char *__restrict__ slot_base, size_t slot_bytes, size_t o_mbx, size_t o_mvs,
                                           uint8_t *__restrict__ mv_dst, size_t mv_stride, uint8_t *__restrict__ info_dst, size_t info_stride,
                                           const SideLaunch &L)
 {
-    typedef typename SideElem<DTYPE>::T elem_t;
+    typedef typename TensorElem<DTYPE>::T elem_t;
     constexpr int ES = (int)sizeof(elem_t);
     extern __shared__ __attribute__((aligned(16))) unsigned side_lds[];
     const int f = (int)blockIdx.y;
     const int gw = L.gw, gh = L.gh, cols = L.mb_cols;
     const int grp = (int)blockIdx.x / L.S, part = (int)blockIdx.x - grp * L.S;
     const int m0 = grp * L.R, m1 = min(m0 + L.R, L.mb_rows);
-    const int ya = side_first_row(m0, gh, L.dh), yb = m1 == L.mb_rows ? gh : side_first_row(m1, gh, L.dh);
-    const int per = (yb - ya + L.S - 1) / L.S;
-    const int y0 = ya + part * per, y1 = min(yb, y0 + per);
+    int y0, y1;                                  // the output rows whose cells lie in the group's macroblock rows: this workgroup's share
+    tensor_share(tensor_first(16 * m0, gh, L.dh), m1 == L.mb_rows ? gh : tensor_first(16 * m1, gh, L.dh), L.S, part, y0, y1);
     if (y0 >= y1) return;                        // (a group no output row falls into: a grid much smaller than the frame)
 
     const unsigned qf = L.q[f];
     const bool read_mv = mv_dst && !((qf >> 28) & 1u);
     const char *slot = slot_base + slot_bytes * (size_t)L.slot[f];
-    side_x4_t *lrec = (side_x4_t *)side_lds;
-    side_x4_t *lmvs = lrec + L.R * cols * 4;
+    u32x4_t *lrec = (u32x4_t *)side_lds;
+    u32x4_t *lmvs = lrec + L.R * cols * 4;
     {
-        const GLOBAL_AS side_x4_t *grec = (const GLOBAL_AS side_x4_t *)(slot + o_mbx) + (size_t)m0 * cols * 8;
-        const GLOBAL_AS side_x4_t *gmvs = (const GLOBAL_AS side_x4_t *)(slot + o_mvs) + (size_t)m0 * cols * 4;
+        const GLOBAL_AS u32x4_t *grec = (const GLOBAL_AS u32x4_t *)(slot + o_mbx) + (size_t)m0 * cols * 8;
+        const GLOBAL_AS u32x4_t *gmvs = (const GLOBAL_AS u32x4_t *)(slot + o_mvs) + (size_t)m0 * cols * 4;
         const int n = (m1 - m0) * cols * 4;      // 16-byte pieces: four of a record's eight, the four of a macroblock's vectors
 #pragma unroll 1
         for (int t = threadIdx.x; t < n; t += 256) lrec[t] = grec[(t >> 2) * 8 + (t & 3)];
@@ -112,14 +81,11 @@ __device__ __forceinline__ void side_body(const char *__restrict__ slot_base, si
     uint8_t *Dm = mv_dst ? mv_dst + mv_stride * f : nullptr;
     uint8_t *Di = info_dst ? info_dst + info_stride * f : nullptr;
     const size_t plane = (size_t)gh * gw;
-    const int nq = (gw + 3) >> 2;                                   // groups of four outputs in a row
-    const int adv_rows = 256 / nq, adv_cols = 256 - adv_rows * nq;  // a lane's step of 256 groups
     const int nrows = y1 - y0;
-    int row = (int)threadIdx.x / nq, col = (int)threadIdx.x - row * nq;
 #pragma unroll 1
-    while (row < nrows) {
-        const int y = y0 + row, x = col << 2;
-        const int by = (int)(((unsigned)(2 * y + 1) * (unsigned)L.dh) / (unsigned)(2 * gh)) >> 2;
+    for (TensorWalk t((gw + 3) >> 2); t.row < nrows; t.next()) {
+        const int y = y0 + t.row, col = t.col, x = col << 2;
+        const int by = tensor_src(y, gh, L.dh) >> 2;
         const int mb_row = ((by >> 2) - m0) * cols, kr = (by & 3) * 4;
         SideCell c[4];
         if (L.xmode == SIDE_X_DISPLAY) {
@@ -129,7 +95,7 @@ __device__ __forceinline__ void side_body(const char *__restrict__ slot_base, si
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const int xi = min(x + i, gw - 1);
-                const int bx = L.xmode == SIDE_X_NATIVE ? xi : (int)(((unsigned)(2 * xi + 1) * (unsigned)L.dw) / (unsigned)(2 * gw)) >> 2;
+                const int bx = L.xmode == SIDE_X_NATIVE ? xi : tensor_src(xi, gw, L.dw) >> 2;
                 side_cell(rec, mvs, mb_row + (bx >> 2), kr + (bx & 3), read_mv, L.planes, qf, c[i]);
             }
         }
@@ -141,13 +107,11 @@ __device__ __forceinline__ void side_body(const char *__restrict__ slot_base, si
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
                     const int v = ch == 0 ? (int)c[i].mv >> 16 : (int)(short)(c[i].mv & 0xffffu);      // x = col, y = row
-                    e[i] = side_value<DTYPE>(v, L.scale[ch]);
+                    e[i] = tensor_value<DTYPE>(v, L.scale[ch]);
                 }
                 uint8_t *o = Dm + ((size_t)ch * plane + pix) * ES;
-                if (L.mv_vec) {
-                    if constexpr (ES == 2) *(GLOBAL_AS side_x2_t *)o = side_x2_t{e[0] | e[1] << 16, e[2] | e[3] << 16};
-                    else *(GLOBAL_AS side_x4_t *)o = side_x4_t{e[0], e[1], e[2], e[3]};
-                } else {
+                if (L.mv_vec) tensor_store4<ES>(o, e);
+                else {
 #pragma unroll
                     for (int i = 0; i < 4; i++)
                         if (x + i < gw) ((GLOBAL_AS elem_t *)o)[i] = (elem_t)e[i];
@@ -159,18 +123,16 @@ __device__ __forceinline__ void side_body(const char *__restrict__ slot_base, si
 #pragma unroll
             for (int b = 0; b < 6; b++) {
                 if (!((L.planes >> b) & 1u)) continue;
-                if (L.info_vec) *(g_u32p)o = c[0].v[b] | c[1].v[b] << 8 | c[2].v[b] << 16 | c[3].v[b] << 24;
+                const unsigned e[4] = {c[0].v[b], c[1].v[b], c[2].v[b], c[3].v[b]};
+                if (L.info_vec) tensor_store4<1>(o, e);
                 else {
 #pragma unroll
                     for (int i = 0; i < 4; i++)
-                        if (x + i < gw) ((g_u8p)o)[i] = (unsigned char)c[i].v[b];
+                        if (x + i < gw) ((g_u8p)o)[i] = (unsigned char)e[i];
                 }
                 o += plane;
             }
         }
-        col += adv_cols;
-        row += adv_rows;
-        if (col >= nq) { col -= nq; row++; }
     }
 }
 
@@ -183,6 +145,6 @@ __device__ __forceinline__ void side_body(const char *__restrict__ slot_base, si
     {                                                                                                                                     \
         side_body<DTYPE>(slot_base, slot_bytes, o_mbx, o_mvs, mv_dst, mv_stride, info_dst, info_stride, L);                               \
     }
-SIDE_KERNEL(vp8_side_i16_kernel, SIDE_I16)
-SIDE_KERNEL(vp8_side_f16_kernel, SIDE_F16)
-SIDE_KERNEL(vp8_side_f32_kernel, SIDE_F32)
+SIDE_KERNEL(vp8_side_i16_kernel, TENSOR_I16)
+SIDE_KERNEL(vp8_side_f16_kernel, TENSOR_F16)
+SIDE_KERNEL(vp8_side_f32_kernel, TENSOR_F32)

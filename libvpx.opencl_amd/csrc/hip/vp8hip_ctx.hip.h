@@ -4,6 +4,9 @@
 //   vp8hip_entropy.hip  vp8hip_entropy_decode
 //   vp8hip_postproc.hip vp8hip_postproc, vp8hip_mfqe
 //   vp8hip_visualize.hip vp8hip_visualize
+//   vp8hip_scale.hip, vp8hip_rgb.hip, vp8hip_side.hip, vp8hip_residual.hip   vp8hip_frames_scale_async, _rgb_async, _side_async,
+//                       _residual_async: frames, and what the slots hold beside them, as tensors in the caller's device memory
+//   vp8hip_handover.hip the checks those four share
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -160,10 +163,8 @@ int vp8hip_need_raster_list(vp8hip_ctx *c, const int *fbs, int n);
 // vp8hip.hip
 int vp8hip_check_status(vp8hip_ctx *c);       // after a stream synchronisation: did a kernel of the cross-CU family give up on a hand-over?
 // vp8hip_scale.hip: what vp8hip_frames_scale_async and vp8hip_frames_rgb_async (vp8hip_rgb.hip) share -- the plan of a target size
-// (returns the LDS a workgroup takes), the check of a destination in the caller's device memory (0, or -2 with the error set), one
-// launch of at most SCALE_MAX_FRAMES frames
+// (returns the LDS a workgroup takes), one launch of at most SCALE_MAX_FRAMES frames
 int vp8hip_scale_plan(const vp8hip_ctx *c, int dw, int dh, int filter, ScaleLaunch &L);
-int vp8hip_check_device_span(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, int n);
 int vp8hip_scale_enqueue(vp8hip_ctx *c, const int *fbs, int m, ScaleLaunch &L, int lds, void *dst, size_t dst_stride);
 // the form a reader that converts nothing takes a frame buffer in: raster where it exists, else tiles; never written: zeros
 static inline int vp8hip_frame_form(const vp8hip_ctx *c, int fb)
@@ -171,3 +172,16 @@ static inline int vp8hip_frame_form(const vp8hip_ctx *c, int fb)
     const uint8_t st = c->fb_state[(size_t)fb];
     return (st & FB_RASTER) && c->fb_block ? SCALE_FROM_RASTER : (st & FB_TILES) ? SCALE_FROM_TILES : SCALE_FROM_ZERO;
 }
+
+// vp8hip_handover.hip: what the four calls that write tensors into the caller's device memory share.  The checks return 0, or -2
+// with the error set (its text begins with `who`); vp8hip_check_dst: stride >= size, destination and stride aligned to the
+// element, then vp8hip_check_device_span: device memory of the context's device, the n frames inside one allocation.
+#define VP8HIP_MAX_OUT_SIZE 16383       // the largest width / height of an output
+int vp8hip_check_fbs(vp8hip_ctx *c, const char *who, const int *fbs, int n);
+int vp8hip_check_slots(vp8hip_ctx *c, const char *who, const int *slots, int n);
+bool vp8hip_out_grid(const vp8hip_ctx *c, int dst_w, int dst_h, int cells, int &gw, int &gh);
+int vp8hip_check_device_span(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, int n);
+int vp8hip_check_dst(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, size_t elem_size, int n);
+unsigned vp8hip_segment_q_bits(const vp8ir_frame_hdr &h);
+// bytes of an element by dtype: F16 is 1 and F32 is 2 in VP8HIP_RGB_*, VP8HIP_SIDE_* and VP8HIP_RES_*; size0: type 0's (bytes: 1, int16: 2)
+static inline int vp8hip_elem_size(int dtype, int size0) { return dtype == 2 ? 4 : dtype == 1 ? 2 : size0; }

@@ -10,32 +10,22 @@ extern "C" __global__ void vp8_residual_i16_kernel(RES_ARGS);
 extern "C" __global__ void vp8_residual_f16_kernel(RES_ARGS);
 extern "C" __global__ void vp8_residual_f32_kernel(RES_ARGS);
 
-#define RES_MAX_SIZE 16383
 #define RES_PART_ROWS 64                        // output rows of a workgroup where a grid is much taller than the frame
 static_assert(sizeof(ResLaunch) < 3072, "the kernel arguments stay well under 4 KB");
-
-static int res_elem_size(int dtype) { return dtype == VP8HIP_RES_F32 ? 4 : 2; }
 
 // the grid of p on context c (null: sized grids only); false for what the call refuses on p alone
 static bool res_grid(const vp8hip_ctx *c, const vp8hip_residual *p, int &gw, int &gh, int &cw, int &ch)
 {
     if (!p || p->dtype < 0 || p->dtype > 2 || (p->layout != VP8HIP_RES_I420 && p->layout != VP8HIP_RES_PLANAR)) return false;
-    if (p->dst_w == 0 && p->dst_h == 0) {
-        if (!c || !c->width) return false;
-        gw = 16 * c->dg.mb_cols; gh = 16 * c->dg.mb_rows;
-        cw = gw / 2; ch = gh / 2;
-        return true;
-    }
-    if (p->dst_w < 1 || p->dst_h < 1 || p->dst_w > RES_MAX_SIZE || p->dst_h > RES_MAX_SIZE) return false;
-    gw = p->dst_w; gh = p->dst_h;
-    cw = (gw + 1) / 2; ch = (gh + 1) / 2;
+    if (!vp8hip_out_grid(c, p->dst_w, p->dst_h, 16, gw, gh)) return false;
+    cw = (gw + 1) / 2; ch = (gh + 1) / 2;        // (the native grid is even both ways)
     return true;
 }
 
 static size_t res_size(const vp8hip_residual *p, int gw, int gh, int cw, int ch)
 {
     const size_t elems = p->layout == VP8HIP_RES_PLANAR ? (size_t)3 * gh * gw : (size_t)gh * gw + (size_t)2 * ch * cw;
-    return elems * res_elem_size(p->dtype);
+    return elems * vp8hip_elem_size(p->dtype, 2);
 }
 
 extern "C" size_t vp8hip_residual_size(const vp8hip_ctx *c, const vp8hip_residual *p)
@@ -44,19 +34,13 @@ extern "C" size_t vp8hip_residual_size(const vp8hip_ctx *c, const vp8hip_residua
     return res_grid(c, p, gw, gh, cw, ch) ? res_size(p, gw, gh, cw, ch) : 0;
 }
 
-// what the kernel needs of a slot's header: the quantiser index of each segment (mb_init_dequantizer, vp8/decoder/decodframe.c)
-// in seven bits each, and the five *_delta_q as the header holds them (bytes: a header built by hand may hold any int8)
+// what the kernel needs of a slot's header: the quantiser index of each segment, and the five *_delta_q as the header holds them
+// (bytes: a header built by hand may hold any int8)
 static ResSlot res_header_bits(int slot, const vp8ir_frame_hdr &h)
 {
     ResSlot s;
     s.slot = slot;
-    s.q = 0;
-    for (int k = 0; k < 4; k++) {
-        int qi = h.base_qindex;
-        if (h.segmentation_enabled) qi = h.mb_segment_abs_delta ? h.segment_quant[k] : qi + h.segment_quant[k];
-        qi = qi < 0 ? 0 : qi > 127 ? 127 : qi;
-        s.q |= (unsigned)qi << (7 * k);
-    }
+    s.q = vp8hip_segment_q_bits(h);
     s.d0 = (unsigned)(uint8_t)h.y1dc_delta_q | (unsigned)(uint8_t)h.y2dc_delta_q << 8 | (unsigned)(uint8_t)h.y2ac_delta_q << 16 |
            (unsigned)(uint8_t)h.uvdc_delta_q << 24;
     s.d1 = (unsigned)(uint8_t)h.uvac_delta_q;
@@ -85,22 +69,15 @@ static void residual_plan(const vp8hip_ctx *c, const vp8hip_residual &p, int gw,
 
 extern "C" int vp8hip_frames_residual_async(vp8hip_ctx *c, const int *slots, int n, const vp8hip_residual *p, void *dst, size_t dst_stride)
 {
-    if (!c || !slots || n < 1 || !p || !dst || c->slots.empty()) return fail(c, -2, "vp8hip_frames_residual_async: bad arguments");
-    for (int i = 0; i < n; i++) {
-        if (slots[i] < 0 || slots[i] >= (int)c->slots.size()) return fail(c, -2, "vp8hip_frames_residual_async: slot %d out of range", slots[i]);
-        const vp8ir_frame_hdr &h = c->slots[slots[i]].hdr_copy;
-        if (h.mb_cols != c->dg.mb_cols || h.mb_rows != c->dg.mb_rows)
-            return fail(c, -2, "vp8hip_frames_residual_async: slot %d holds no frame of the context's size", slots[i]);
-    }
+    const char *who = "vp8hip_frames_residual_async";
+    if (!c || !slots || n < 1 || !p || !dst || c->slots.empty()) return fail(c, -2, "%s: bad arguments", who);
+    if (int rc = vp8hip_check_slots(c, who, slots, n)) return rc;
     int gw, gh, cw, ch;
     if (!res_grid(c, p, gw, gh, cw, ch))
-        return fail(c, -2, "vp8hip_frames_residual_async: grid %dx%d (both 0, or 1..%d each), layout %d, type %d", p->dst_w, p->dst_h, RES_MAX_SIZE,
-                    p->layout, p->dtype);
-    const size_t es = (size_t)res_elem_size(p->dtype), size = res_size(p, gw, gh, cw, ch);
-    if (dst_stride < size) return fail(c, -2, "vp8hip_frames_residual_async: stride %zu below the frame's %zu bytes", dst_stride, size);
-    if ((uintptr_t)dst % es || dst_stride % es)
-        return fail(c, -2, "vp8hip_frames_residual_async: destination %p / stride %zu not aligned to the %zu-byte element", dst, dst_stride, es);
-    if (int rc = vp8hip_check_device_span(c, "vp8hip_frames_residual_async", dst, dst_stride, size, n)) return rc;
+        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), layout %d, type %d", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE, p->layout,
+                    p->dtype);
+    const size_t es = (size_t)vp8hip_elem_size(p->dtype, 2), size = res_size(p, gw, gh, cw, ch);
+    if (int rc = vp8hip_check_dst(c, who, dst, dst_stride, size, es, n)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
 
     ResLaunch L;
@@ -114,7 +91,7 @@ extern "C" int vp8hip_frames_residual_async(vp8hip_ctx *c, const int *slots, int
     L.c_vec = aligned && cw % 4 == 0 && ((size_t)gh * gw * es) % piece == 0;
     const size_t cap = c->pool ? ((size_t)c->pool_chunks + 1) * c->chunk_blocks : c->cap_blocks;
     // (the kernel clamps a block's index to cap - 1, as 32 bits: what keeps a starved slot's reads in bounds)
-    if (cap < 1 || cap > 0xffffffffull) return fail(c, -2, "vp8hip_frames_residual_async: a block stream of %zu blocks", cap);
+    if (cap < 1 || cap > 0xffffffffull) return fail(c, -2, "%s: a block stream of %zu blocks", who, cap);
     const unsigned groups = (unsigned)(L.mb_rows * L.runs * L.S);
     for (int i0 = 0; i0 < n; i0 += RES_MAX_FRAMES) {
         const int m = n - i0 < RES_MAX_FRAMES ? n - i0 : RES_MAX_FRAMES;

@@ -13,7 +13,6 @@ extern "C" __global__ void vp8_rgb_packed3_f16_kernel(RGB_ARGS);
 extern "C" __global__ void vp8_rgb_packed3_f32_kernel(RGB_ARGS);
 extern "C" __global__ void vp8_rgb_packed4_u8_kernel(RGB_ARGS);
 
-#define RGB_MAX_SIZE 16383
 #define RGB_SCRATCH_MAX ((size_t)256 << 20)     // the scratch holds one chunk of frames: at most this much (one frame at least)
 #define RGB_BAND_LDS 24576                      // rows of a band in LDS: six workgroups to a CU beside the value table
 
@@ -24,16 +23,14 @@ static const int rgb_matrix[3][6] = {
     {16, 298, 459, -55, -136, 541},             // BT.709, limited range
 };
 
-static int rgb_elem_size(int dtype) { return dtype == VP8HIP_RGB_U8 ? 1 : dtype == VP8HIP_RGB_F16 ? 2 : 4; }
-
 extern "C" size_t vp8hip_rgb_size(const vp8hip_rgb *p)
 {
-    if (!p || p->dst_w < 1 || p->dst_h < 1 || p->dst_w > RGB_MAX_SIZE || p->dst_h > RGB_MAX_SIZE) return 0;
+    if (!p || p->dst_w < 1 || p->dst_h < 1 || p->dst_w > VP8HIP_MAX_OUT_SIZE || p->dst_h > VP8HIP_MAX_OUT_SIZE) return 0;
     if (p->filter < 0 || p->filter > 2 || p->matrix < 0 || p->matrix > 2 || p->layout < 0 || p->layout > 2 || p->order < 0 || p->order > 1 ||
         p->dtype < 0 || p->dtype > 2)
         return 0;
     if (p->layout == VP8HIP_RGB_PACKED4 && p->dtype != VP8HIP_RGB_U8) return 0;
-    return (size_t)p->dst_w * p->dst_h * (p->layout == VP8HIP_RGB_PACKED4 ? 4 : 3) * rgb_elem_size(p->dtype);
+    return (size_t)p->dst_w * p->dst_h * (p->layout == VP8HIP_RGB_PACKED4 ? 4 : 3) * vp8hip_elem_size(p->dtype, 1);
 }
 
 extern "C" size_t vp8hip_rgb_scratch_bytes(const vp8hip_ctx *c) { return c ? c->rgb_cap : 0; }
@@ -80,7 +77,7 @@ static int rgb_plan(const vp8hip_ctx *c, const vp8hip_rgb &p, bool from_frames, 
         L.cu[pos] = cu[col]; L.cv[pos] = cv[col];
         L.scale[pos] = p.scale[col]; L.bias[pos] = p.bias[col];
     }
-    const int es = rgb_elem_size(p.dtype);
+    const int es = vp8hip_elem_size(p.dtype, 1);
     const size_t piece = p.layout == VP8HIP_RGB_PACKED4 ? 16 : (size_t)4 * es;
     L.vec = w % 4 == 0 && dst % piece == 0 && dst_stride % piece == 0;
     return (p.dtype == VP8HIP_RGB_U8 ? 0 : 3072) + pairs * per2;
@@ -88,20 +85,16 @@ static int rgb_plan(const vp8hip_ctx *c, const vp8hip_rgb &p, bool from_frames, 
 
 extern "C" int vp8hip_frames_rgb_async(vp8hip_ctx *c, const int *fbs, int n, const vp8hip_rgb *p, void *dst, size_t dst_stride)
 {
-    if (!c || !fbs || n < 1 || !p || !dst || c->fb.empty()) return fail(c, -2, "vp8hip_frames_rgb_async: bad arguments");
-    for (int i = 0; i < n; i++)
-        if (fbs[i] < 0 || fbs[i] >= (int)c->fb.size()) return fail(c, -2, "vp8hip_frames_rgb_async: frame buffer %d out of range", fbs[i]);
-    if (p->dst_w < 1 || p->dst_h < 1 || p->dst_w > RGB_MAX_SIZE || p->dst_h > RGB_MAX_SIZE)
-        return fail(c, -2, "vp8hip_frames_rgb_async: size %dx%d outside 1..%d", p->dst_w, p->dst_h, RGB_MAX_SIZE);
+    const char *who = "vp8hip_frames_rgb_async";
+    if (!c || !fbs || n < 1 || !p || !dst || c->fb.empty()) return fail(c, -2, "%s: bad arguments", who);
+    if (int rc = vp8hip_check_fbs(c, who, fbs, n)) return rc;
+    if (p->dst_w < 1 || p->dst_h < 1 || p->dst_w > VP8HIP_MAX_OUT_SIZE || p->dst_h > VP8HIP_MAX_OUT_SIZE)
+        return fail(c, -2, "%s: size %dx%d outside 1..%d", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE);
     const size_t size = vp8hip_rgb_size(p);
     if (!size)
-        return fail(c, -2, "vp8hip_frames_rgb_async: filter %d, matrix %d, layout %d, order %d, dtype %d (four-byte pixels: bytes only)", p->filter,
-                    p->matrix, p->layout, p->order, p->dtype);
-    if (dst_stride < size) return fail(c, -2, "vp8hip_frames_rgb_async: stride %zu below the frame's %zu bytes", dst_stride, size);
-    const size_t es = (size_t)rgb_elem_size(p->dtype);
-    if ((uintptr_t)dst % es || dst_stride % es)
-        return fail(c, -2, "vp8hip_frames_rgb_async: destination %p / stride %zu not aligned to the %zu-byte element", dst, dst_stride, es);
-    if (int rc = vp8hip_check_device_span(c, "vp8hip_frames_rgb_async", dst, dst_stride, size, n)) return rc;
+        return fail(c, -2, "%s: filter %d, matrix %d, layout %d, order %d, dtype %d (four-byte pixels: bytes only)", who, p->filter, p->matrix,
+                    p->layout, p->order, p->dtype);
+    if (int rc = vp8hip_check_dst(c, who, dst, dst_stride, size, (size_t)vp8hip_elem_size(p->dtype, 1), n)) return rc;
 
     const bool from_frames = p->dst_w == c->width && p->dst_h == c->height;
     // the chunk: what the kernel arguments carry, and -- scaled -- what the scratch holds

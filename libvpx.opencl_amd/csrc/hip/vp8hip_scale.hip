@@ -6,11 +6,9 @@
 extern "C" __global__ void vp8_scale_kernel(const uint8_t *raster, size_t fb_stride, const uint8_t *tiles, size_t tile_frame, uint8_t *dst,
                                             size_t dst_stride, ScaleLaunch L);
 
-#define SCALE_MAX_SIZE 16383
-
 extern "C" size_t vp8hip_i420_size(int w, int h)
 {
-    if (w < 1 || h < 1 || w > SCALE_MAX_SIZE || h > SCALE_MAX_SIZE) return 0;
+    if (w < 1 || h < 1 || w > VP8HIP_MAX_OUT_SIZE || h > VP8HIP_MAX_OUT_SIZE) return 0;
     return (size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2);
 }
 
@@ -76,34 +74,6 @@ int vp8hip_scale_plan(const vp8hip_ctx *c, int dw, int dh, int filter, ScaleLaun
     return lds;
 }
 
-// the destination of n frames of `size` bytes, dst_stride apart: device memory of this context's device, inside one allocation
-int vp8hip_check_device_span(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, int n)
-{
-    HIPCHK(c, hipSetDevice(c->device));
-    // the destination: device memory of this context's device, the n frames inside one allocation
-    hipPointerAttribute_t pa;
-    memset(&pa, 0, sizeof pa);
-    if (hipPointerGetAttributes(&pa, dst) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, -2, "%s: the destination is not memory HIP knows", who);
-    }
-    if (pa.type != hipMemoryTypeDevice || pa.device != c->device)
-        return fail(c, -2, "%s: the destination is not device memory of device %d", who, c->device);
-    hipDeviceptr_t abase = nullptr;
-    size_t asize = 0;
-    if (hipMemGetAddressRange(&abase, &asize, (hipDeviceptr_t)dst) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, -2, "%s: no allocation holds the destination", who);
-    }
-    const uintptr_t a0 = (uintptr_t)abase, d0 = (uintptr_t)dst;
-    const bool wraps = dst_stride > (SIZE_MAX - size) / (size_t)n;
-    const size_t span = wraps ? SIZE_MAX : dst_stride * (size_t)(n - 1) + size;
-    if (wraps || d0 < a0 || (d0 - a0) > asize || span > asize - (d0 - a0))
-        return fail(c, -2, "%s: %d frames of %zu bytes, %zu apart, do not fit in the destination's allocation", who, n, size,
-                    dst_stride);
-    return 0;
-}
-
 // m <= SCALE_MAX_FRAMES frames of a planned call on the context's stream; each frame is read in a form it has: raster where it
 // exists, else tiles; never converted
 int vp8hip_scale_enqueue(vp8hip_ctx *c, const int *fbs, int m, ScaleLaunch &L, int lds, void *dst, size_t dst_stride)
@@ -117,14 +87,13 @@ int vp8hip_scale_enqueue(vp8hip_ctx *c, const int *fbs, int m, ScaleLaunch &L, i
 
 extern "C" int vp8hip_frames_scale_async(vp8hip_ctx *c, const int *fbs, int n, int dst_w, int dst_h, int filter, void *dst, size_t dst_stride)
 {
-    if (!c || !fbs || n < 1 || !dst || c->fb.empty()) return fail(c, -2, "vp8hip_frames_scale_async: bad arguments");
-    for (int i = 0; i < n; i++)
-        if (fbs[i] < 0 || fbs[i] >= (int)c->fb.size()) return fail(c, -2, "vp8hip_frames_scale_async: frame buffer %d out of range", fbs[i]);
+    const char *who = "vp8hip_frames_scale_async";
+    if (!c || !fbs || n < 1 || !dst || c->fb.empty()) return fail(c, -2, "%s: bad arguments", who);
+    if (int rc = vp8hip_check_fbs(c, who, fbs, n)) return rc;
     const size_t size = vp8hip_i420_size(dst_w, dst_h);
-    if (!size) return fail(c, -2, "vp8hip_frames_scale_async: size %dx%d outside 1..%d", dst_w, dst_h, SCALE_MAX_SIZE);
-    if (filter < 0 || filter > 2) return fail(c, -2, "vp8hip_frames_scale_async: filter %d (0 none, 1 bilinear, 2 box)", filter);
-    if (dst_stride < size) return fail(c, -2, "vp8hip_frames_scale_async: stride %zu below the frame's %zu bytes", dst_stride, size);
-    if (int rc = vp8hip_check_device_span(c, "vp8hip_frames_scale_async", dst, dst_stride, size, n)) return rc;
+    if (!size) return fail(c, -2, "%s: size %dx%d outside 1..%d", who, dst_w, dst_h, VP8HIP_MAX_OUT_SIZE);
+    if (filter < 0 || filter > 2) return fail(c, -2, "%s: filter %d (0 none, 1 bilinear, 2 box)", who, filter);
+    if (int rc = vp8hip_check_dst(c, who, dst, dst_stride, size, 1, n)) return rc;
 
     ScaleLaunch L;
     const int lds = vp8hip_scale_plan(c, dst_w, dst_h, filter, L);       // (bytes of LDS a workgroup takes)

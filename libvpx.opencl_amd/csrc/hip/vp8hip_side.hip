@@ -10,33 +10,24 @@ extern "C" __global__ void vp8_side_i16_kernel(SIDE_ARGS);
 extern "C" __global__ void vp8_side_f16_kernel(SIDE_ARGS);
 extern "C" __global__ void vp8_side_f32_kernel(SIDE_ARGS);
 
-#define SIDE_MAX_SIZE 16383
 #define SIDE_ALL_PLANES 63u
 #define SIDE_GROUP_LDS 32768                    // records and vectors of a group of macroblock rows: five workgroups to a CU ...
 #define SIDE_GROUP_ROWS 4                       // ... and at most this many rows (small frames: more workgroups)
 #define SIDE_PART_ROWS 64                       // output rows of a workgroup where a grid is much taller than the frame
 
-static int side_elem_size(int dtype) { return dtype == VP8HIP_SIDE_F32 ? 4 : 2; }
 static int side_nplanes(unsigned planes) { return __builtin_popcount(planes); }
 
 // the grid of p on context c (null: sized grids only); false for what the call refuses on p alone
 static bool side_grid(const vp8hip_ctx *c, const vp8hip_side *p, int &gw, int &gh)
 {
     if (!p || p->mv_dtype < 0 || p->mv_dtype > 2 || (p->planes & ~SIDE_ALL_PLANES)) return false;
-    if (p->dst_w == 0 && p->dst_h == 0) {
-        if (!c || !c->width) return false;
-        gw = 4 * c->dg.mb_cols; gh = 4 * c->dg.mb_rows;
-        return true;
-    }
-    if (p->dst_w < 1 || p->dst_h < 1 || p->dst_w > SIDE_MAX_SIZE || p->dst_h > SIDE_MAX_SIZE) return false;
-    gw = p->dst_w; gh = p->dst_h;
-    return true;
+    return vp8hip_out_grid(c, p->dst_w, p->dst_h, 4, gw, gh);
 }
 
 extern "C" size_t vp8hip_side_mv_size(const vp8hip_ctx *c, const vp8hip_side *p)
 {
     int gw, gh;
-    return side_grid(c, p, gw, gh) ? (size_t)2 * gh * gw * side_elem_size(p->mv_dtype) : 0;
+    return side_grid(c, p, gw, gh) ? (size_t)2 * gh * gw * vp8hip_elem_size(p->mv_dtype, 2) : 0;
 }
 
 extern "C" size_t vp8hip_side_info_size(const vp8hip_ctx *c, const vp8hip_side *p)
@@ -45,19 +36,8 @@ extern "C" size_t vp8hip_side_info_size(const vp8hip_ctx *c, const vp8hip_side *
     return side_grid(c, p, gw, gh) ? (size_t)side_nplanes(p->planes) * gh * gw : 0;
 }
 
-// what the kernel needs of a slot's header: the quantiser index of each segment (mb_init_dequantizer, vp8/decoder/decodframe.c)
-// in seven bits each, and bit 28 for a key frame
-static unsigned side_header_bits(const vp8ir_frame_hdr &h)
-{
-    unsigned q = 0;
-    for (int s = 0; s < 4; s++) {
-        int qi = h.base_qindex;
-        if (h.segmentation_enabled) qi = h.mb_segment_abs_delta ? h.segment_quant[s] : qi + h.segment_quant[s];
-        qi = qi < 0 ? 0 : qi > 127 ? 127 : qi;
-        q |= (unsigned)qi << (7 * s);
-    }
-    return q | (h.frame_type == 0 ? 1u << 28 : 0u);
-}
+// what the kernel needs of a slot's header: the quantiser index of each segment, and bit 28 for a key frame
+static unsigned side_header_bits(const vp8ir_frame_hdr &h) { return vp8hip_segment_q_bits(h) | (h.frame_type == 0 ? 1u << 28 : 0u); }
 
 // The launch for a grid of gw x gh: the size it is laid over, the group of macroblock rows a workgroup stages and how many
 // workgroups share a group's output rows.  Returns the LDS a workgroup takes.
@@ -87,31 +67,20 @@ static size_t side_plan(const vp8hip_ctx *c, const vp8hip_side &p, int gw, int g
 extern "C" int vp8hip_frames_side_async(vp8hip_ctx *c, const int *slots, int n, const vp8hip_side *p, void *mv_dst, size_t mv_stride,
                                         void *info_dst, size_t info_stride)
 {
-    if (!c || !slots || n < 1 || !p || (!mv_dst && !info_dst) || c->slots.empty()) return fail(c, -2, "vp8hip_frames_side_async: bad arguments");
-    for (int i = 0; i < n; i++) {
-        if (slots[i] < 0 || slots[i] >= (int)c->slots.size()) return fail(c, -2, "vp8hip_frames_side_async: slot %d out of range", slots[i]);
-        const vp8ir_frame_hdr &h = c->slots[slots[i]].hdr_copy;
-        if (h.mb_cols != c->dg.mb_cols || h.mb_rows != c->dg.mb_rows)
-            return fail(c, -2, "vp8hip_frames_side_async: slot %d holds no frame of the context's size", slots[i]);
-    }
+    const char *who = "vp8hip_frames_side_async";
+    if (!c || !slots || n < 1 || !p || (!mv_dst && !info_dst) || c->slots.empty()) return fail(c, -2, "%s: bad arguments", who);
+    if (int rc = vp8hip_check_slots(c, who, slots, n)) return rc;
     int gw, gh;
     if (!side_grid(c, p, gw, gh))
-        return fail(c, -2, "vp8hip_frames_side_async: grid %dx%d (both 0, or 1..%d each), type %d, planes 0x%x", p->dst_w, p->dst_h, SIDE_MAX_SIZE,
+        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), type %d, planes 0x%x", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE,
                     p->mv_dtype, p->planes);
-    if (info_dst && !p->planes) return fail(c, -2, "vp8hip_frames_side_async: an info tensor of no planes");
-    const size_t es = (size_t)side_elem_size(p->mv_dtype);
+    if (info_dst && !p->planes) return fail(c, -2, "%s: an info tensor of no planes", who);
+    const size_t es = (size_t)vp8hip_elem_size(p->mv_dtype, 2);
     const size_t mv_size = (size_t)2 * gh * gw * es, info_size = (size_t)side_nplanes(p->planes) * gh * gw;
-    if (mv_dst) {
-        if (mv_stride < mv_size) return fail(c, -2, "vp8hip_frames_side_async: mv stride %zu below the frame's %zu bytes", mv_stride, mv_size);
-        if ((uintptr_t)mv_dst % es || mv_stride % es)
-            return fail(c, -2, "vp8hip_frames_side_async: mv destination %p / stride %zu not aligned to the %zu-byte element", mv_dst, mv_stride, es);
-        if (int rc = vp8hip_check_device_span(c, "vp8hip_frames_side_async (mv)", mv_dst, mv_stride, mv_size, n)) return rc;
-    }
-    if (info_dst) {
-        if (info_stride < info_size)
-            return fail(c, -2, "vp8hip_frames_side_async: info stride %zu below the frame's %zu bytes", info_stride, info_size);
-        if (int rc = vp8hip_check_device_span(c, "vp8hip_frames_side_async (info)", info_dst, info_stride, info_size, n)) return rc;
-    }
+    if (mv_dst)
+        if (int rc = vp8hip_check_dst(c, "vp8hip_frames_side_async (mv)", mv_dst, mv_stride, mv_size, es, n)) return rc;
+    if (info_dst)
+        if (int rc = vp8hip_check_dst(c, "vp8hip_frames_side_async (info)", info_dst, info_stride, info_size, 1, n)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
 
     SideLaunch L;

@@ -4,7 +4,8 @@ tensor the call writes.  Every `short` of the reference's C is a wrap to int16 h
 knows how the kernel goes about it, and the product never loads this file."""
 import numpy as np
 
-DTYPES = {"i16": np.int16, "f16": np.float16, "f32": np.float32}
+from tensor_reference import DTYPES, convert, grid_map  # noqa: F401  (the tensor's types; its values; the sample map)
+
 LAYOUTS = {"i420": 0, "planar": 1}
 B_PRED, SPLITMV = 4, 9
 MB_SKIP = 1
@@ -127,12 +128,6 @@ def residual_planes(hdr, mbs, coef, wrap=True):
     return y.astype(t), u.astype(t), v.astype(t)
 
 
-def grid_map(dst, d):
-    """source sample under the centre of each of dst outputs laid over d samples: ((2x + 1) * d) // (2 * dst)"""
-    x = np.arange(dst, dtype=np.int64)
-    return ((2 * x + 1) * d) // (2 * dst)
-
-
 def grid(hdr, dst_w=0, dst_h=0):
     """-> (gw, gh, cw, ch, sx [gw], sy [gh], scx [cw], scy [ch]): the luma and I420 chroma grids and the sample each column / row takes"""
     if dst_w == 0 and dst_h == 0:
@@ -146,17 +141,6 @@ def grid(hdr, dst_w=0, dst_h=0):
 def size(hdr, dst_w=0, dst_h=0, dtype="i16", layout="planar"):
     gw, gh, cw, ch = grid(hdr, dst_w, dst_h)[:4]
     return (3 * gh * gw if layout == "planar" else gh * gw + 2 * ch * cw) * np.dtype(DTYPES[dtype]).itemsize
-
-
-def convert(v, dtype, scale):
-    """int16 -> the tensor's type: the value, or float32(float64(v) * float64(float32(scale))), or that rounded to a half"""
-    if dtype == "i16":
-        return v.astype(np.int16)
-    f = (v.astype(np.float64) * np.float64(np.float32(scale))).astype(np.float32)
-    if dtype == "f32":
-        return f
-    with np.errstate(over="ignore"):             # (beyond the halves' range: infinity)
-        return f.astype(np.float16)
 
 
 def arrange(planes, hdr, dst_w=0, dst_h=0, dtype="i16", layout="planar", scale=(1.0, 1.0, 1.0)):

@@ -3,8 +3,9 @@
 mv [2, gh, gw] and info [C, gh, gw].  Nothing here knows how the kernel goes about it."""
 import numpy as np
 
+from tensor_reference import DTYPES, convert, grid_map  # noqa: F401  (the mv tensor's types; its values by channel; the cell map)
+
 PLANES = {"ref": 1, "mode": 2, "skip": 4, "segment": 8, "qindex": 16, "coded": 32}
-DTYPES = {"i16": np.int16, "f16": np.float16, "f32": np.float32}
 B_PRED, SPLITMV = 4, 9
 MB_SKIP = 1
 # byte offsets in a vp8ir_mb record (include/vp8_ir.h)
@@ -18,12 +19,6 @@ def mask_of(planes):
     for p in planes:
         m |= PLANES[p]
     return m
-
-
-def grid_map(dst, d):
-    """source pixel under the centre of each of dst outputs laid over d pixels: ((2x + 1) * d) // (2 * dst)"""
-    x = np.arange(dst, dtype=np.int64)
-    return ((2 * x + 1) * d) // (2 * dst)
 
 
 def grid(hdr, dst_w=0, dst_h=0):
@@ -83,18 +78,6 @@ def cells(hdr, mbs, mvs):
     info = np.stack([to_grid(per_mb(ref)), to_grid(mode), to_grid(per_mb(mbs[:, O_FLAGS] & MB_SKIP)), to_grid(per_mb(seg)),
                      to_grid(per_mb(qindex_of_segments(hdr)[seg & 3])), to_grid(block_kind(mbs))]).astype(np.uint8)
     return mv, info
-
-
-def convert(v, dtype, scale):
-    """int16 [2, ...] -> the mv tensor's type: the value, or float32(float64(v) * float64(scale[c])), or that rounded to a half"""
-    if dtype == "i16":
-        return v.astype(np.int16)
-    s = np.asarray(scale, np.float32).astype(np.float64).reshape(2, *([1] * (v.ndim - 1)))
-    f = (v.astype(np.float64) * s).astype(np.float32)
-    if dtype == "f32":
-        return f
-    with np.errstate(over="ignore"):             # (beyond the halves' range: infinity)
-        return f.astype(np.float16)
 
 
 def side(hdr, mbs, mvs, dst_w=0, dst_h=0, dtype="i16", planes=0, scale=(1.0, 1.0)):

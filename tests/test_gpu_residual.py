@@ -11,20 +11,15 @@ import numpy as np
 import pytest
 
 from vp8_testlib import ivf_path, synth_ir
+from handover_testlib import (TORCH_DTYPE, Producer, assert_destinations_refused, assert_guards_intact, bits, guarded, later_writers_producer,
+                              write_later_frames)
 import residual_reference as R
 
 pytestmark = pytest.mark.gpu
 
-TORCH_DTYPE = {"i16": torch.int16, "f16": torch.float16, "f32": torch.float32}
-BITS = {"i16": np.uint16, "f16": np.uint16, "f32": np.uint32}
 STREAMS = ["p_split_352x288", "p_arf_176x144", "p_seg_176x144", "p_odd_130x98", "kf_odd_67x45"]
 LAYOUTS = ("planar", "i420")
 B_PRED, SPLITMV = 4, 9
-
-
-def bits(a, dtype):
-    """numpy array -> its bit pattern (floats compared as integers: bit for bit, signed zeros included)"""
-    return np.ascontiguousarray(a).view(BITS[dtype])
 
 
 def call(ctx, slots, dw=0, dh=0, dtype="i16", layout="planar", scale=None, out=None):
@@ -44,47 +39,6 @@ def check(ctx, slot, hdr, planes, dw=0, dh=0, dtype="i16", layout="planar", scal
 def slot_planes(ctx, slot, hdr):
     mbs, coef = ctx.ir_fetch(slot)
     return R.residual_planes(hdr, mbs, coef)
-
-
-class Producer:
-    """a stream's frames, one after the other, into a slot of a context: by the host parser (parse_into_slot_compact) or by the
-    device's entropy decoder (also on a context whose slots take their blocks from a pool)"""
-
-    def __init__(self, P, name, how, nslots=1):
-        self.P, self.how = P, how
-        self.w, self.h, self.frames = P.read_ivf(ivf_path(name))
-        self.ctx = P.Vp8Hip(0)
-        w, h = self.w, self.h
-        if how == "pooled":
-            cols = (w + 15) // 16
-            nmb = cols * ((h + 15) // 16)
-            self.ctx.configure_pooled(w, h, 1, nslots, nslots * nmb * 24 * 32 + (nslots + 3) * 4 * cols * 24 * 32)
-        else:
-            self.ctx.configure(w, h, 1, nslots)
-        self.parser = P.Parser()
-        if how != "host":
-            self.parser.set_device_segmap(True)
-
-    def put(self, i, slot=0):
-        """frame i (in stream order) into `slot`; -> the header the slot now has"""
-        ctx, data = self.ctx, self.frames[i]
-        if self.how == "host":
-            ctx.sync()                                  # (the staging may still be on its way)
-            hdr, _ = ctx.parse_into_slot_compact(self.parser, data, slot)
-            self.parser.swap(hdr)
-            return hdr
-        hdr, _ = self.parser.begin(data)
-        ef = self.parser.export_entropy()
-        assert ef is not None
-        if self.how == "pooled":
-            ctx.pool_reset()
-        assert not ctx.entropy_decode(slot, [ef], [data]).any()
-        self.parser.swap(hdr)
-        return ef.hdr
-
-    def close(self):
-        self.parser.close()
-        self.ctx.close()
 
 
 @pytest.mark.parametrize("how", ["host", "entropy", "pooled"])
@@ -246,8 +200,8 @@ def test_destination_hygiene(pkg):
             es = 4 if dtype == "f32" else 2
             off, pad = off // es * es, pad // es * es                       # (the call refuses what is not aligned to the element)
             size = R.size(hdrs[0], dw, dh, dtype, layout)
-            big = torch.full((n * (size + pad) + 2 * off + 64,), 0xA5, dtype=torch.uint8, device="cuda:0")
-            flat = big[off:off + n * (size + pad)].view(n, size + pad)[:, :size].view(TORCH_DTYPE[dtype])
+            big, flat = guarded(n, size, pad, off)
+            flat = flat.view(TORCH_DTYPE[dtype])
             gw, gh = (dw, dh) if dw else (16 * hdrs[0].mb_cols, 16 * hdrs[0].mb_rows)
             out = flat.unflatten(1, (3, gh, gw)) if layout == "planar" else flat
             got = call(ctx, slots, dw, dh, dtype, layout, (0.25, 0.5, 2.0), out=out)
@@ -256,11 +210,7 @@ def test_destination_hygiene(pkg):
             for k, s in enumerate(slots):
                 want = R.arrange(planes[s], hdrs[s], dw, dh, dtype, layout, (0.25, 0.5, 2.0))
                 assert np.array_equal(bits(g[k], dtype), bits(want, dtype)), (dw, dh, dtype, layout, off, pad, k)
-            a = big.cpu().numpy()
-            mask = np.ones(a.size, bool)
-            for i in range(n):
-                mask[off + i * (size + pad): off + i * (size + pad) + size] = False
-            assert (a[mask] == 0xA5).all(), (dw, dh, dtype, layout, off, pad)
+            assert_guards_intact(big, n, size, pad, off, what=(dw, dh, dtype, layout, off, pad))
     finally:
         prod.close()
 
@@ -271,38 +221,12 @@ def test_ordering_against_later_slot_writers(pkg, how):
     them), then the tensor read on torch's stream: it holds what the slots held at the call"""
     P = pkg
     n = 4
-    prod = Producer(P, "p_split_352x288", "host" if how == "copy" else how, nslots=2 * n)
+    prod, hdrs, staged = later_writers_producer(P, "p_split_352x288", how, n)
     ctx, w, h = prod.ctx, prod.w, prod.h
     try:
-        hdrs = [prod.put(i, i) for i in range(n)]
-        if how == "copy":
-            new_hdrs = [prod.put(n + i, n + i) for i in range(n)]
-            ctx.sync()
         old = [R.arrange(slot_planes(ctx, i, hdrs[i]), hdrs[i], w, h, "f32", "planar", (0.5, 0.5, 0.5)) for i in range(n)]
         out = call(ctx, list(range(n)), w, h, "f32", "planar", 0.5)
-        if how == "host":
-            new_hdrs = []
-            for i in range(n):                          # (no sync: the stagings' earlier uploads have landed, ir_fetch waited)
-                hdr, _ = ctx.parse_into_slot_compact(prod.parser, prod.frames[n + i], i)
-                prod.parser.swap(hdr)
-                new_hdrs.append(hdr)
-        elif how == "copy":
-            for i in range(n):
-                ctx.ir_copy(i, n + i)
-        else:
-            efs = []
-            for i in range(n):
-                hdr, _ = prod.parser.begin(prod.frames[n + i])
-                efs.append(prod.parser.export_entropy())
-                prod.parser.swap(hdr)
-            arr = (P.EntropyFrame * n)()
-            off = 0
-            for i, ef in enumerate(efs):
-                ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(ef), ctypes.sizeof(P.EntropyFrame))
-                arr[i].data_off = off
-                off += len(prod.frames[n + i])
-            blob = b"".join(prod.frames[n:2 * n])
-            ctx._chk(ctx.L.vp8hip_entropy_decode(ctx.h, 0, n, ctypes.byref(arr), blob, len(blob)), "entropy_decode")
+        new_hdrs = write_later_frames(P, prod, how, n, staged)
         g = out.cpu().numpy()                           # .cpu() on torch's current stream
         for i in range(n):
             assert np.array_equal(bits(g[i], "f32"), bits(old[i], "f32")), i
@@ -310,7 +234,7 @@ def test_ordering_against_later_slot_writers(pkg, how):
         # ... and the slots now hold the later frames
         changed = 0
         for i in range(n):
-            hdr = efs[i].hdr if how == "entropy" else new_hdrs[i]
+            hdr = new_hdrs[i]
             planes = slot_planes(ctx, i, hdr)
             check(ctx, i, hdr, planes, w, h, "f32", "planar", 0.5)
             changed += not np.array_equal(R.arrange(planes, hdr, w, h, "f32", "planar", (0.5, 0.5, 0.5)), old[i])
@@ -388,15 +312,6 @@ def test_identity_with_the_decoders_own_pixels(pkg):
         ctx.close()
 
 
-def _hip_range(ptr):
-    """(base, size) of the HIP allocation holding ptr, through the HIP runtime torch and the library share"""
-    hip = ctypes.CDLL("libamdhip64.so.7")
-    hip.hipMemGetAddressRange.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
-    base, size = ctypes.c_void_p(), ctypes.c_size_t()
-    assert hip.hipMemGetAddressRange(ctypes.byref(base), ctypes.byref(size), ctypes.c_void_p(ptr)) == 0
-    return base.value, size.value
-
-
 def test_refusals(pkg):
     P = pkg
     prod = Producer(P, "p_odd_130x98", "host", nslots=4)
@@ -430,33 +345,9 @@ def test_refusals(pkg):
             assert run(slots, 3, prm(dtype=dt), d, 1 << 20) == -2
         for lay in (-1, 2, 77):
             assert run(slots, 3, prm(layout=lay), d, 1 << 20) == -2
-        assert run(slots, 3, prm(), None, size) == -2
-        assert run(slots, 3, prm(), d, size - 2) == -2
         assert run(slots, 3, prm(layout=0), d, (34 * 23 + 2 * 17 * 12) * 2 - 2) == -2
-        # alignment to the element: int16 / halves at an odd address or stride, floats at 2 mod 4
-        assert run(slots, 3, prm(), d + 1, size) == -2
-        assert run(slots, 3, prm(), d, size + 1) == -2
-        assert run(slots, 3, prm(dtype=1), d + 1, size + 2) == -2
-        assert run(slots, 3, prm(dtype=2), d + 2, 2 * size) == -2
-        assert run(slots, 3, prm(dtype=2), d, 2 * size + 2) == -2
-        L.vp8hip_host_alloc.restype = ctypes.c_void_p
-        L.vp8hip_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-        L.vp8hip_host_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        host = L.vp8hip_host_alloc(ctx.h, 3 * size)
-        try:
-            assert run(slots, 3, prm(), host, size) == -2
-        finally:
-            L.vp8hip_host_free(ctx.h, host)
-        pageable = np.zeros(3 * size, np.uint8)
-        assert run(slots, 3, prm(), pageable.ctypes.data, size) == -2
-        base, asize = _hip_range(d)
-        end = base + asize
-        assert run(slots, 1, prm(), end - size + 2, size) == -2             # past the allocation
-        assert run(slots, 3, prm(), end - 3 * size, size + 2) == -2         # the stride carries the last frame past it
-        assert run(slots, 3, prm(), d, (1 << 62)) == -2                      # spans that wrap
-        if torch.cuda.device_count() > 1:
-            other = torch.empty(3 * size, dtype=torch.uint8, device="cuda:1")
-            assert run(slots, 3, prm(), other.data_ptr(), size) == -2
+        for dtype, es in ((0, 2), (1, 2), (2, 4)):          # each type: also the alignment to its element
+            assert_destinations_refused(ctx, lambda n, dst, stride: run(slots, n, prm(dtype=dtype), dst, stride), d, size * es // 2, es)
         ctx.sync()
         torch.cuda.synchronize()
         assert (big.cpu().numpy() == 0x5C).all()                            # nothing was enqueued

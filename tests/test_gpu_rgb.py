@@ -9,24 +9,19 @@ import torch  # noqa: F401  (first: the library then shares torch's HIP runtime)
 import numpy as np
 import pytest
 
-from vp8_testlib import ivf_path, load_package, oracle_decode_ivf
+from vp8_testlib import load_package, oracle_decode_ivf
+from handover_testlib import (TORCH_DTYPE, assert_destinations_refused, assert_guards_intact, bits, decode_stream, equal_on_device, guarded,
+                              large_launch)
 import rgb_reference as R
 import scale_reference as S
 
 pytestmark = pytest.mark.gpu
 
 PY_LAYOUT = {"planar": "nchw", "packed3": "nhwc", "packed4": "nhwc4"}
-TORCH_DTYPE = {"u8": torch.uint8, "f16": torch.float16, "f32": torch.float32}
-BITS = {"u8": np.uint8, "f16": np.uint16, "f32": np.uint32}
 # every matrix x layout x order for bytes; every float type for the planar and the three-channel packed layout
 U8_COMBOS = [(m, l, o, "u8") for m in R.MATRICES for l in R.LAYOUTS for o in R.ORDERS]
 FLOAT_COMBOS = [("bt601", l, o, d) for l, o in (("planar", "rgb"), ("packed3", "bgr")) for d in ("f16", "f32")]
 COMBOS = U8_COMBOS + FLOAT_COMBOS
-
-
-def bits(a, dtype):
-    """numpy array -> its bit pattern (floats compared as integers: bit for bit, signed zeros included)"""
-    return np.ascontiguousarray(a).view(BITS[dtype])
 
 
 def call(ctx, fbs, dw, dh, filt, combo, **kw):
@@ -39,31 +34,6 @@ def want(packed, dw, dh, combo):
     matrix, layout, order, dtype = combo
     scale, bias = R.scale_bias(R.IMAGENET_MEAN, R.IMAGENET_STD) if dtype != "u8" else R.scale_bias()
     return R.convert(packed, dw, dh, matrix, layout, order, dtype, scale, bias)
-
-
-def decode_stream(P, name, form, monkeypatch, extra_fb=0):
-    """every frame of a fixture into a frame buffer of its own, one launch per frame; -> (ctx, frame buffers of the shown frames)"""
-    monkeypatch.setenv("VP8HIP_RECON", "simt" if form == "tiles" else "wave")
-    w, h, frames = P.read_ivf(ivf_path(name))
-    nf = len(frames)
-    ctx = P.Vp8Hip(0)
-    ctx.configure(w, h, nf + 1 + extra_fb, 1)
-    parser = P.Parser()
-    phys, shown = {}, []
-    try:
-        for i, data in enumerate(frames):
-            hdr, _ = ctx.parse_into_slot_compact(parser, data, 0)
-            r = parser.refs
-            ctx.decode([(0, i, tuple(phys.get(k, nf) for k in (r.lst_idx, r.gld_idx, r.alt_idx)))], P.STAGE_ALL)
-            ctx.sync()
-            new = r.new_idx
-            parser.swap(hdr)
-            phys[new] = i
-            if hdr.show_frame:
-                shown.append(phys[parser.refs.show_idx])
-    finally:
-        parser.close()
-    return ctx, shown
 
 
 def shown_buffers(name):
@@ -146,34 +116,6 @@ def test_random_sweep(pkg):
     assert len(seen) == 3 * 2 * 7
 
 
-def _large_launch(P, ctx, name, n, monkeypatch):
-    monkeypatch.setenv("VP8HIP_RECON", "simt")
-    w, h, frames = P.read_ivf(ivf_path(name))
-    ctx.configure(w, h, n + 2, n)
-    parser = P.Parser()
-    for i, data in enumerate(frames[:n]):
-        ctx.sync()
-        hdr, _ = ctx.parse_into_slot_compact(parser, data, i)
-        parser.swap(hdr)
-    parser.close()
-    for i in range(len(frames), n):
-        ctx.ir_copy(i, i % len(frames))
-    ctx.decode([(i, i, None) for i in range(n)], P.STAGE_ALL)
-    return len(frames)
-
-
-def _equal_on_device(out, refs, dtype):
-    """frame i of `out` against refs[i % len(refs)] (numpy), compared on the device as bit patterns; -> indices of differing frames"""
-    view = {"u8": torch.uint8, "f16": torch.int16, "f32": torch.int32}[dtype]
-    np_view = {"u8": np.uint8, "f16": np.int16, "f32": np.int32}[dtype]
-    bad = []
-    for r, ref in enumerate(refs):
-        t = torch.from_numpy(np.ascontiguousarray(ref).view(np_view)).to(out.device)
-        diff = (out[r::len(refs)].view(view) != t).flatten(1).any(1)
-        bad += [r + len(refs) * int(i) for i in diff.nonzero().flatten().tolist()]
-    return sorted(bad)
-
-
 def test_large_launch_batch(pkg, monkeypatch):
     """1024 kf_1920x1080 frames left as tiles by one launch: bytes at the display size, normalised halves at 224x224"""
     P = pkg
@@ -181,12 +123,12 @@ def test_large_launch_batch(pkg, monkeypatch):
     _, kept = oracle_decode_ivf("kf_1920x1080", keep_frames=True)
     ctx = P.Vp8Hip(0)
     try:
-        nsrc = _large_launch(P, ctx, "kf_1920x1080", n, monkeypatch)
+        nsrc = large_launch(P, ctx, "kf_1920x1080", n, monkeypatch)
         for dw, dh, combo in ((1920, 1080, ("bt601", "planar", "rgb", "u8")), (224, 224, ("bt601", "planar", "rgb", "f16"))):
             refs = [want(S.scale_frame(buf, P.geom(hdr.width, hdr.height), hdr.width, hdr.height, dw, dh, 1), dw, dh, combo)
                     for hdr, _, _, _, buf in kept[:nsrc]]
             out = call(ctx, list(range(n)), dw, dh, 1, combo)
-            assert _equal_on_device(out, refs, combo[3]) == [], (dw, dh)
+            assert equal_on_device(out, refs, [i % nsrc for i in range(n)], combo[3]) == [], (dw, dh)
             del out
         assert ctx.memory_usage()["raster_pool"] == 0
     finally:
@@ -200,7 +142,7 @@ def test_tiled_and_raster_frames_in_one_call(pkg, monkeypatch):
     _, kept = oracle_decode_ivf("kf_640x360", keep_frames=True)
     ctx = P.Vp8Hip(0)
     try:
-        _large_launch(P, ctx, "kf_640x360", n, monkeypatch)
+        large_launch(P, ctx, "kf_640x360", n, monkeypatch)
         ctx.sync()
         assert ctx.memory_usage()["raster_pool"] == 0
         g = ctx.g
@@ -234,7 +176,7 @@ def test_more_frames_than_a_chunk_of_the_scratch(pkg):
         combo = ("bt709", "planar", "bgr", "u8")
         refs = [want(S.scale_frame(b, ctx.g, w, h, dw, dh, 0), dw, dh, combo) for b in bufs]
         out = call(ctx, [i % 3 for i in range(n)], dw, dh, 0, combo)
-        assert _equal_on_device(out, refs, "u8") == []
+        assert equal_on_device(out, refs, [i % 3 for i in range(n)], "u8") == []
         assert 0 < ctx.rgb_scratch_bytes() <= 256 * 2 ** 20 and ctx.rgb_scratch_bytes() < n * S.i420_size(dw, dh)
         ctx.release_staging()
         assert ctx.rgb_scratch_bytes() == 0
@@ -260,21 +202,16 @@ def test_destination_hygiene(pkg, monkeypatch, form):
             if (off + pad) % es or off % es:
                 continue
             size = R.frame_size(dw, dh, layout, dtype)
-            stride = size + pad
-            big = torch.full((n * stride + 2 * off + 64,), 0xA5, dtype=torch.uint8, device="cuda:0")
+            big, flat = guarded(n, size, pad, off)
             shape = (3, dh, dw) if layout == "planar" else (dh, dw, 3 if layout == "packed3" else 4)
-            out = big[off:off + n * stride].view(n, stride)[:, :size].view(TORCH_DTYPE[dtype]).unflatten(1, shape)
-            assert out.data_ptr() % 4 == off and out.stride(0) * es == stride
+            out = flat.view(TORCH_DTYPE[dtype]).unflatten(1, shape)
+            assert out.data_ptr() % 4 == off and out.stride(0) * es == size + pad
             r = call(ctx, shown, dw, dh, 1, combo, out=out)
             assert r.data_ptr() == out.data_ptr()
             got = out.cpu().numpy()
             for k, (g, w, h, buf) in enumerate(frames):
                 assert np.array_equal(bits(got[k], dtype), bits(want(S.scale_frame(buf, g, w, h, dw, dh, 1), dw, dh, combo), dtype)), (dw, dh, combo, k)
-            a = big.cpu().numpy()
-            mask = np.ones(a.size, bool)
-            for i in range(n):
-                mask[off + i * stride: off + i * stride + size] = False
-            assert (a[mask] == 0xA5).all(), (dw, dh, combo, off, pad)
+            assert_guards_intact(big, n, size, pad, off, what=(dw, dh, combo, off, pad))
     finally:
         ctx.close()
 
@@ -288,7 +225,7 @@ def test_ordering_against_later_launches(pkg, monkeypatch):
     refs = [want(S.scale_frame(buf, P.geom(640, 360), 640, 360, 240, 135, 1), 240, 135, combo) for _, _, _, _, buf in kept[:n]]
     ctx = P.Vp8Hip(0)
     try:
-        _large_launch(P, ctx, "kf_640x360", n, monkeypatch)
+        large_launch(P, ctx, "kf_640x360", n, monkeypatch)
         out = call(ctx, list(range(n)), 240, 135, 1, combo)
         ctx.decode([(i, (i + 1) % n, None) for i in range(n)], P.STAGE_ALL)     # frame i into frame buffer i + 1
         got = out.cpu().numpy()                           # .cpu() on torch's current stream
@@ -298,15 +235,6 @@ def test_ordering_against_later_launches(pkg, monkeypatch):
         assert all(np.array_equal(got[i], refs[(i - 1) % n]) for i in range(n))
     finally:
         ctx.close()
-
-
-def _hip_range(ptr):
-    """(base, size) of the HIP allocation holding ptr, through the HIP runtime torch and the library share"""
-    hip = ctypes.CDLL("libamdhip64.so.7")
-    hip.hipMemGetAddressRange.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
-    base, size = ctypes.c_void_p(), ctypes.c_size_t()
-    assert hip.hipMemGetAddressRange(ctypes.byref(base), ctypes.byref(size), ctypes.c_void_p(ptr)) == 0
-    return base.value, size.value
 
 
 def test_refusals(pkg, monkeypatch):
@@ -336,30 +264,8 @@ def test_refusals(pkg, monkeypatch):
         for bad in (dict(filt=-1), dict(filt=3), dict(matrix=-1), dict(matrix=3), dict(layout=-1), dict(layout=3), dict(order=-1), dict(order=2),
                     dict(dtype=-1), dict(dtype=3), dict(layout=2, dtype=1), dict(layout=2, dtype=2)):
             assert run(fbs, 3, prm(**bad), d, 1 << 20) == -2, bad
-        assert run(fbs, 3, prm(), d, size - 1) == -2
-        # alignment to the element type: halves at an odd address / an odd stride, floats at 2 mod 4
-        assert run(fbs, 3, prm(dtype=1), d + 1, 2 * size) == -2
-        assert run(fbs, 3, prm(dtype=1), d, 2 * size + 1) == -2
-        assert run(fbs, 3, prm(dtype=2), d + 2, 4 * size) == -2
-        assert run(fbs, 3, prm(dtype=2), d, 4 * size + 2) == -2
-        L.vp8hip_host_alloc.restype = ctypes.c_void_p
-        L.vp8hip_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-        L.vp8hip_host_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        host = L.vp8hip_host_alloc(ctx.h, 3 * size)
-        try:
-            assert run(fbs, 3, prm(), host, size) == -2
-        finally:
-            L.vp8hip_host_free(ctx.h, host)
-        pageable = np.zeros(3 * size, np.uint8)
-        assert run(fbs, 3, prm(), pageable.ctypes.data, size) == -2
-        base, asize = _hip_range(d)
-        end = base + asize
-        assert run(fbs, 1, prm(), end - size + 1, size) == -2           # one byte past the allocation
-        assert run(fbs, 3, prm(), end - 3 * size, size + 1) == -2       # the stride carries the last frame past it
-        assert run(fbs, 3, prm(), d, (1 << 62)) == -2                    # spans that wrap
-        if torch.cuda.device_count() > 1:
-            other = torch.empty(3 * size, dtype=torch.uint8, device="cuda:1")
-            assert run(fbs, 3, prm(), other.data_ptr(), size) == -2
+        for dtype, es in ((0, 1), (1, 2), (2, 4)):          # bytes; halves and floats: also the alignment to the element
+            assert_destinations_refused(ctx, lambda n, dst, stride: run(fbs, n, prm(dtype=dtype), dst, stride), d, size * es, es)
         ctx.sync()
         torch.cuda.synchronize()
         assert (big.cpu().numpy() == 0x5C).all()                          # nothing was enqueued

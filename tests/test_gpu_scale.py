@@ -13,8 +13,9 @@ import torch  # noqa: F401  (first: the library then shares torch's HIP runtime)
 import numpy as np
 import pytest
 
-from vp8_testlib import GOLDEN, ROOT, golden_md5, ivf_path, oracle_decode_ivf, synth_ir
+from vp8_testlib import GOLDEN, ROOT, golden_md5, oracle_decode_ivf, synth_ir
 from vp8_writer import write_key_frame
+from handover_testlib import assert_destinations_refused, assert_guards_intact, decode_stream, guarded, large_launch
 import scale_reference as S
 
 pytestmark = pytest.mark.gpu
@@ -35,31 +36,6 @@ def listings():
 def md5s(t):
     a = t.cpu().numpy()
     return [hashlib.md5(a[i].tobytes()).hexdigest() for i in range(a.shape[0])]
-
-
-def decode_stream(P, name, form, monkeypatch, extra_fb=0):
-    """every frame of a fixture into a frame buffer of its own, one launch per frame; -> (ctx, frame buffers of the shown frames)"""
-    monkeypatch.setenv("VP8HIP_RECON", "simt" if form == "tiles" else "wave")
-    w, h, frames = P.read_ivf(ivf_path(name))
-    nf = len(frames)
-    ctx = P.Vp8Hip(0)
-    ctx.configure(w, h, nf + 1 + extra_fb, 1)
-    parser = P.Parser()
-    phys, shown = {}, []
-    try:
-        for i, data in enumerate(frames):
-            hdr, _ = ctx.parse_into_slot_compact(parser, data, 0)
-            r = parser.refs
-            ctx.decode([(0, i, tuple(phys.get(k, nf) for k in (r.lst_idx, r.gld_idx, r.alt_idx)))], P.STAGE_ALL)
-            ctx.sync()
-            new = r.new_idx
-            parser.swap(hdr)
-            phys[new] = i
-            if hdr.show_frame:
-                shown.append(phys[parser.refs.show_idx])
-    finally:
-        parser.close()
-    return ctx, shown
 
 
 def md5_list(ctx, fbs):
@@ -96,29 +72,13 @@ def test_listings_from_both_forms(pkg, monkeypatch, name, form):
         ctx.close()
 
 
-def _large_launch(P, ctx, name, n, monkeypatch):
-    monkeypatch.setenv("VP8HIP_RECON", "simt")
-    w, h, frames = P.read_ivf(ivf_path(name))
-    ctx.configure(w, h, n + 2, n)
-    parser = P.Parser()
-    for i, data in enumerate(frames[:n]):
-        ctx.sync()
-        hdr, _ = ctx.parse_into_slot_compact(parser, data, i)
-        parser.swap(hdr)
-    parser.close()
-    for i in range(len(frames), n):
-        ctx.ir_copy(i, i % len(frames))
-    ctx.decode([(i, i, None) for i in range(n)], P.STAGE_ALL)
-    return len(frames)
-
-
 def test_large_launch_batch(pkg, monkeypatch):
     P = pkg
     n = 1024
     _, kept = oracle_decode_ivf("kf_1920x1080", keep_frames=True)
     ctx = P.Vp8Hip(0)
     try:
-        nsrc = _large_launch(P, ctx, "kf_1920x1080", n, monkeypatch)
+        nsrc = large_launch(P, ctx, "kf_1920x1080", n, monkeypatch)
         for dw, dh in ((960, 540), (224, 224)):
             want = [hashlib.md5(S.scale_frame(buf, P.geom(hdr.width, hdr.height), hdr.width, hdr.height, dw, dh, 1).tobytes()).hexdigest()
                     for hdr, _, _, _, buf in kept]
@@ -194,7 +154,7 @@ def test_tiled_and_raster_frames_in_one_call(pkg, monkeypatch):
     _, kept = oracle_decode_ivf("kf_640x360", keep_frames=True)
     ctx = P.Vp8Hip(0)
     try:
-        _large_launch(P, ctx, "kf_640x360", n, monkeypatch)
+        large_launch(P, ctx, "kf_640x360", n, monkeypatch)
         ctx.sync()
         assert ctx.memory_usage()["raster_pool"] == 0
         g = ctx.g
@@ -242,19 +202,14 @@ def test_destination_hygiene(pkg, monkeypatch, form):
     try:
         for dw, dh, gold_name in ((67, 45, None), (34, 23, "kf_odd_67x45.scale_34x23_f1.md5"), (200, 150, "kf_odd_67x45.scale_200x150_f1.md5")):
             size = S.i420_size(dw, dh)
-            n, stride, off = len(shown), size + 37, 3
-            big = torch.full((n * stride + 2 * off + 64,), 0xA5, dtype=torch.uint8, device="cuda:0")
-            out = big[off:off + n * stride].view(n, stride)[:, :size]
-            assert out.stride(0) == stride and out.data_ptr() % 2 == 1
+            n, pad, off = len(shown), 37, 3
+            big, out = guarded(n, size, pad, off)
+            assert out.stride(0) == size + pad and out.data_ptr() % 2 == 1
             r = ctx.frames_scaled(shown, dw, dh, 1, out=out)
             assert r.data_ptr() == out.data_ptr()
             want = golden_md5("kf_odd_67x45") if gold_name is None else [l.split()[0] for l in open(os.path.join(GOLDEN, gold_name))]
             assert md5s(out) == want
-            a = big.cpu().numpy()
-            mask = np.ones(a.size, bool)
-            for i in range(n):
-                mask[off + i * stride: off + i * stride + size] = False
-            assert (a[mask] == 0xA5).all(), (dw, dh)
+            assert_guards_intact(big, n, size, pad, off, what=(dw, dh))
     finally:
         ctx.close()
 
@@ -266,7 +221,7 @@ def test_ordering_against_later_launches(pkg, monkeypatch):
     gold = [l.split()[0] for l in open(os.path.join(GOLDEN, "kf_640x360.scale_240x135_f1.md5"))]
     ctx = P.Vp8Hip(0)
     try:
-        _large_launch(P, ctx, "kf_640x360", n, monkeypatch)
+        large_launch(P, ctx, "kf_640x360", n, monkeypatch)
         out = ctx.frames_scaled(list(range(n)), 240, 135, 1)
         ctx.decode([(i, (i + 1) % n, None) for i in range(n)], P.STAGE_ALL)     # frame i into frame buffer i + 1
         assert md5s(out) == gold                          # .cpu() on torch's current stream
@@ -274,15 +229,6 @@ def test_ordering_against_later_launches(pkg, monkeypatch):
         assert md5s(ctx.frames_scaled(list(range(n)), 240, 135, 1)) == [gold[(i - 1) % n] for i in range(n)]
     finally:
         ctx.close()
-
-
-def _hip_range(ptr):
-    """(base, size) of the HIP allocation holding ptr, through the HIP runtime torch and the library share"""
-    hip = ctypes.CDLL("libamdhip64.so.7")
-    hip.hipMemGetAddressRange.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
-    base, size = ctypes.c_void_p(), ctypes.c_size_t()
-    assert hip.hipMemGetAddressRange(ctypes.byref(base), ctypes.byref(size), ctypes.c_void_p(ptr)) == 0
-    return base.value, size.value
 
 
 def test_refusals(pkg, monkeypatch):
@@ -305,25 +251,7 @@ def test_refusals(pkg, monkeypatch):
             assert call(fbs, 3, w, h, 1, d, size) == -2, (w, h)
         for f in (-1, 3, 7):
             assert call(fbs, 3, 34, 23, f, d, size) == -2
-        assert call(fbs, 3, 34, 23, 1, d, size - 1) == -2
-        L.vp8hip_host_alloc.restype = ctypes.c_void_p
-        L.vp8hip_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-        L.vp8hip_host_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        host = L.vp8hip_host_alloc(ctx.h, 3 * size)
-        try:
-            assert call(fbs, 3, 34, 23, 1, host, size) == -2
-        finally:
-            L.vp8hip_host_free(ctx.h, host)
-        pageable = np.zeros(3 * size, np.uint8)
-        assert call(fbs, 3, 34, 23, 1, pageable.ctypes.data, size) == -2
-        base, asize = _hip_range(d)
-        end = base + asize
-        assert call(fbs, 1, 34, 23, 1, end - size + 1, size) == -2           # one byte past the allocation
-        assert call(fbs, 3, 34, 23, 1, end - 3 * size, size + 1) == -2       # the stride carries the last frame past it
-        assert call(fbs, 3, 34, 23, 1, d, (1 << 62)) == -2                    # spans that wrap
-        if torch.cuda.device_count() > 1:
-            other = torch.empty(3 * size, dtype=torch.uint8, device="cuda:1")
-            assert call(fbs, 3, 34, 23, 1, other.data_ptr(), size) == -2
+        assert_destinations_refused(ctx, lambda n, dst, stride: call(fbs, n, 34, 23, 1, dst, stride), d, size, 1)
         ctx.sync()
         torch.cuda.synchronize()
         assert (big.cpu().numpy() == 0x5C).all()                              # nothing was enqueued

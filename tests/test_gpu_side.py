@@ -10,20 +10,15 @@ import numpy as np
 import pytest
 
 from vp8_testlib import ivf_path
+from handover_testlib import (BITS, TORCH_DTYPE, Producer, assert_destinations_refused, assert_guards_intact, bits, equal_on_device, guarded,
+                              later_writers_producer, write_later_frames)
 import side_reference as R
 
 pytestmark = pytest.mark.gpu
 
-TORCH_DTYPE = {"i16": torch.int16, "f16": torch.float16, "f32": torch.float32}
-BITS = {"i16": np.uint16, "f16": np.uint16, "f32": np.uint32, "u8": np.uint8}
 STREAMS = ["p_split_352x288", "p_arf_176x144", "p_seg_176x144", "p_roi_640x360", "p_odd_130x98", "kf_640x360", "kf_odd_67x45", "p_1920x1080"]
 MASKS = [63, 7, 0b101010, 16, 1, 0b110100, 32]
 SCALES = [(1.0, 1.0), (0.125, 0.125), (-1.0 / 3, 1e-3), (3.0e4, 2.0 ** -20)]
-
-
-def bits(a, dtype):
-    """numpy array -> its bit pattern (floats compared as integers: bit for bit, signed zeros included)"""
-    return np.ascontiguousarray(a).view(BITS[dtype])
 
 
 def call(ctx, slots, dw, dh, dtype="i16", planes=63, scale=None, **kw):
@@ -57,47 +52,6 @@ def _targets(w, h, rng):
          (4 * ((w + 15) // 16), 4 * ((h + 15) // 16))]
     c += [(int(rng.integers(1, 2 * w + 2)), int(rng.integers(1, 2 * h + 2))) for _ in range(3)]
     return c
-
-
-class Producer:
-    """a stream's frames, one after the other, into slot 0 of a context: by the host parser (parse_into_slot_compact) or by the
-    device's entropy decoder (also on a context whose slots take their blocks from a pool)"""
-
-    def __init__(self, P, name, how, nslots=1):
-        self.P, self.how = P, how
-        self.w, self.h, self.frames = P.read_ivf(ivf_path(name))
-        self.ctx = P.Vp8Hip(0)
-        w, h = self.w, self.h
-        if how == "pooled":
-            cols = (w + 15) // 16
-            nmb = cols * ((h + 15) // 16)
-            self.ctx.configure_pooled(w, h, 1, nslots, nslots * nmb * 24 * 32 + (nslots + 3) * 4 * cols * 24 * 32)
-        else:
-            self.ctx.configure(w, h, 1, nslots)
-        self.parser = P.Parser()
-        if how != "host":
-            self.parser.set_device_segmap(True)
-
-    def put(self, i, slot=0):
-        """frame i (in stream order) into `slot`; -> the header the slot now has"""
-        ctx, data = self.ctx, self.frames[i]
-        if self.how == "host":
-            ctx.sync()                                  # (the staging may still be on its way)
-            hdr, _ = ctx.parse_into_slot_compact(self.parser, data, slot)
-            self.parser.swap(hdr)
-            return hdr
-        hdr, _ = self.parser.begin(data)
-        ef = self.parser.export_entropy()
-        assert ef is not None
-        if self.how == "pooled":
-            ctx.pool_reset()
-        assert not ctx.entropy_decode(slot, [ef], [data]).any()
-        self.parser.swap(hdr)
-        return ef.hdr
-
-    def close(self):
-        self.parser.close()
-        self.ctx.close()
 
 
 @pytest.mark.parametrize("how", ["host", "entropy", "pooled"])
@@ -259,19 +213,6 @@ def test_stale_vector_area_of_a_key_frame(pkg):
         prod.close()
 
 
-def _equal_on_device(out, refs, which, dtype):
-    """frame i of `out` against refs[which[i]] (numpy), compared on the device as bit patterns; -> indices of differing frames"""
-    view = {"u8": torch.uint8, "i16": torch.int16, "f16": torch.int16, "f32": torch.int32}[dtype]
-    np_view = {"u8": np.uint8, "i16": np.int16, "f16": np.int16, "f32": np.int32}[dtype]
-    t = torch.from_numpy(np.stack([np.ascontiguousarray(r).view(np_view) for r in refs])).to(out.device)
-    idx = torch.as_tensor(which, device=out.device)
-    bad = []
-    for a in range(0, len(which), 512):
-        diff = (out[a:a + 512].view(view) != t[idx[a:a + 512]]).flatten(1).any(1)
-        bad += [a + int(i) for i in diff.nonzero().flatten().tolist()]
-    return bad
-
-
 def test_batch_of_4096_slots(pkg):
     """4096 slots in one call (sixteen launches), a shuffled list with repeats, a list a little longer than one launch carries"""
     P = pkg
@@ -291,8 +232,8 @@ def test_batch_of_4096_slots(pkg):
                 mv, info = call(ctx, slots, dw, dh, dtype, planes, (0.125, 0.125))
                 which = [s % nsrc for s in slots]
                 assert mv.shape[0] == len(slots) and info.shape[0] == len(slots)
-                assert _equal_on_device(mv, [r[0] for r in refs], which, dtype) == [], (dw, dh, dtype, len(slots))
-                assert _equal_on_device(info, [r[1] for r in refs], which, "u8") == [], (dw, dh, planes, len(slots))
+                assert equal_on_device(mv, [r[0] for r in refs], which, dtype) == [], (dw, dh, dtype, len(slots))
+                assert equal_on_device(info, [r[1] for r in refs], which, "u8") == [], (dw, dh, planes, len(slots))
                 del mv, info
     finally:
         prod.close()
@@ -318,10 +259,8 @@ def test_destination_hygiene(pkg):
             nc = bin(planes).count("1")
             msize, isize = 2 * gh * gw * es, nc * gh * gw
             moff, mpad = off // es * es, pad // es * es                     # (the call refuses vectors not aligned to their element)
-            mbig = torch.full((n * (msize + mpad) + 2 * moff + 64,), 0xA5, dtype=torch.uint8, device="cuda:0")
-            ibig = torch.full((n * (isize + pad) + 2 * off + 64,), 0x5A, dtype=torch.uint8, device="cuda:0")
-            out_mv = mbig[moff:moff + n * (msize + mpad)].view(n, msize + mpad)[:, :msize].view(TORCH_DTYPE[dtype]).unflatten(1, (2, gh, gw))
-            out_info = ibig[off:off + n * (isize + pad)].view(n, isize + pad)[:, :isize].unflatten(1, (nc, gh, gw))
+            (mbig, mflat), (ibig, iflat) = guarded(n, msize, mpad, moff), guarded(n, isize, pad, off, 0x5A)
+            out_mv, out_info = mflat.view(TORCH_DTYPE[dtype]).unflatten(1, (2, gh, gw)), iflat.unflatten(1, (nc, gh, gw))
             assert out_mv.data_ptr() % 16 == moff % 16 and out_info.data_ptr() % 16 == off % 16
             mv, info = call(ctx, slots, dw, dh, dtype, planes, (0.25, 0.5), out_mv=out_mv, out_info=out_info)
             assert mv.data_ptr() == out_mv.data_ptr() and info.data_ptr() == out_info.data_ptr()
@@ -329,12 +268,8 @@ def test_destination_hygiene(pkg):
             for k, s in enumerate(slots):
                 wm, wi = R.side(hdrs[s], irs[s][0], irs[s][1], dw, dh, dtype, planes, (0.25, 0.5))
                 assert np.array_equal(bits(gm[k], dtype), bits(wm, dtype)) and np.array_equal(gi[k], wi), (dw, dh, dtype, planes, off, pad, k)
-            for big, o, size, stride, fill in ((mbig, moff, msize, msize + mpad, 0xA5), (ibig, off, isize, isize + pad, 0x5A)):
-                a = big.cpu().numpy()
-                mask = np.ones(a.size, bool)
-                for i in range(n):
-                    mask[o + i * stride: o + i * stride + size] = False
-                assert (a[mask] == fill).all(), (dw, dh, dtype, planes, off, pad)
+            assert_guards_intact(mbig, n, msize, mpad, moff, what=(dw, dh, dtype, planes, off, pad))
+            assert_guards_intact(ibig, n, isize, pad, off, 0x5A, what=(dw, dh, dtype, planes, off, pad))
     finally:
         prod.close()
 
@@ -345,39 +280,13 @@ def test_ordering_against_later_slot_writers(pkg, how):
     them), then the tensors read on torch's stream: they hold what the slots held at the call"""
     P = pkg
     n = 4
-    prod = Producer(P, "p_split_352x288", "host" if how == "copy" else how, nslots=2 * n)
+    prod, hdrs, staged = later_writers_producer(P, "p_split_352x288", how, n)
     ctx, w, h = prod.ctx, prod.w, prod.h
     try:
-        hdrs = [prod.put(i, i) for i in range(n)]
-        if how == "copy":
-            new_hdrs = [prod.put(n + i, n + i) for i in range(n)]
-            ctx.sync()
         irs = [slot_ir(ctx, i) for i in range(n)]
         old = [R.side(hdrs[i], irs[i][0], irs[i][1], w, h, "f32", 63, (0.125, 0.125)) for i in range(n)]
         mv, info = call(ctx, list(range(n)), w, h, "f32", 63, (0.125, 0.125))
-        if how == "host":
-            new_hdrs = []
-            for i in range(n):                          # (no sync: the stagings' earlier uploads have landed, slot_ir waited)
-                hdr, _ = ctx.parse_into_slot_compact(prod.parser, prod.frames[n + i], i)
-                prod.parser.swap(hdr)
-                new_hdrs.append(hdr)
-        elif how == "copy":
-            for i in range(n):
-                ctx.ir_copy(i, n + i)
-        else:
-            efs = []
-            for i in range(n):
-                hdr, _ = prod.parser.begin(prod.frames[n + i])
-                efs.append(prod.parser.export_entropy())
-                prod.parser.swap(hdr)
-            arr = (P.EntropyFrame * n)()
-            off = 0
-            for i, ef in enumerate(efs):
-                ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(ef), ctypes.sizeof(P.EntropyFrame))
-                arr[i].data_off = off
-                off += len(prod.frames[n + i])
-            blob = b"".join(prod.frames[n:2 * n])
-            ctx._chk(ctx.L.vp8hip_entropy_decode(ctx.h, 0, n, ctypes.byref(arr), blob, len(blob)), "entropy_decode")
+        new_hdrs = write_later_frames(P, prod, how, n, staged)
         gm, gi = mv.cpu().numpy(), info.cpu().numpy()   # .cpu() on torch's current stream
         for i in range(n):
             assert np.array_equal(bits(gm[i], "f32"), bits(old[i][0], "f32")) and np.array_equal(gi[i], old[i][1]), i
@@ -386,21 +295,11 @@ def test_ordering_against_later_slot_writers(pkg, how):
         changed = 0
         for i in range(n):
             ir = slot_ir(ctx, i)
-            hdr = efs[i].hdr if how == "entropy" else new_hdrs[i]
-            check(ctx, i, hdr, ir, w, h, "f32", 63, scale=(0.125, 0.125))
+            check(ctx, i, new_hdrs[i], ir, w, h, "f32", 63, scale=(0.125, 0.125))
             changed += not np.array_equal(ir[1], irs[i][1])
         assert changed > 0
     finally:
         prod.close()
-
-
-def _hip_range(ptr):
-    """(base, size) of the HIP allocation holding ptr, through the HIP runtime torch and the library share"""
-    hip = ctypes.CDLL("libamdhip64.so.7")
-    hip.hipMemGetAddressRange.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
-    base, size = ctypes.c_void_p(), ctypes.c_size_t()
-    assert hip.hipMemGetAddressRange(ctypes.byref(base), ctypes.byref(size), ctypes.c_void_p(ptr)) == 0
-    return base.value, size.value
 
 
 def test_refusals(pkg):
@@ -440,39 +339,11 @@ def test_refusals(pkg):
             assert run(slots, 3, prm(planes=planes), d, 1 << 19, d2, 1 << 19) == -2
         assert run(slots, 3, prm(planes=0), d, msize, d2, isize) == -2                 # an info tensor of no planes
         assert run(slots, 3, prm(), None, 0, None, 0) == -2                            # neither destination
-        assert run(slots, 3, prm(), d, msize - 2, None, 0) == -2
-        assert run(slots, 3, prm(), None, 0, d2, isize - 1) == -2
-        assert run(slots, 3, prm(), d, msize, d2, isize - 1) == -2
-        # alignment to the element: int16 / halves at an odd address or stride, floats at 2 mod 4
-        assert run(slots, 3, prm(), d + 1, msize, None, 0) == -2
-        assert run(slots, 3, prm(), d, msize + 1, None, 0) == -2
-        assert run(slots, 3, prm(dtype=1), d + 1, msize + 2, None, 0) == -2
-        assert run(slots, 3, prm(dtype=2), d + 2, 2 * msize, None, 0) == -2
-        assert run(slots, 3, prm(dtype=2), d, 2 * msize + 2, None, 0) == -2
-        L.vp8hip_host_alloc.restype = ctypes.c_void_p
-        L.vp8hip_host_alloc.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-        L.vp8hip_host_free.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        host = L.vp8hip_host_alloc(ctx.h, 3 * msize)
-        try:
-            assert run(slots, 3, prm(), host, msize, None, 0) == -2
-            assert run(slots, 3, prm(), None, 0, host, isize) == -2
-            assert run(slots, 3, prm(), d, msize, host, isize) == -2
-        finally:
-            L.vp8hip_host_free(ctx.h, host)
-        pageable = np.zeros(3 * msize, np.uint8)
-        assert run(slots, 3, prm(), pageable.ctypes.data, msize, None, 0) == -2
-        assert run(slots, 3, prm(), None, 0, pageable.ctypes.data, isize) == -2
-        base, asize = _hip_range(d)
-        end = base + asize
-        assert run(slots, 1, prm(), end - msize + 2, msize, None, 0) == -2           # past the allocation
-        assert run(slots, 1, prm(), None, 0, end - isize + 1, isize) == -2
-        assert run(slots, 3, prm(), end - 3 * msize, msize + 2, None, 0) == -2       # the stride carries the last frame past it
-        assert run(slots, 3, prm(), d, msize, end - 3 * isize, isize + 1) == -2
-        assert run(slots, 3, prm(), d, (1 << 62), None, 0) == -2                      # spans that wrap
-        assert run(slots, 3, prm(), None, 0, d2, (1 << 63) + 8) == -2
-        if torch.cuda.device_count() > 1:
-            other = torch.empty(3 * msize, dtype=torch.uint8, device="cuda:1")
-            assert run(slots, 3, prm(), other.data_ptr(), msize, None, 0) == -2
+        for dtype, es in ((0, 2), (1, 2), (2, 4)):          # the vectors alone, each type: also the alignment to its element
+            assert_destinations_refused(ctx, lambda n, dst, stride: run(slots, n, prm(dtype=dtype), dst, stride, None, 0), d, msize * es // 2, es)
+        assert_destinations_refused(ctx, lambda n, dst, stride: run(slots, n, prm(), None, 0, dst, stride), d2, isize, 1)      # the info tensor alone
+        # ... and beside vectors that would do (no null: that is the vectors alone)
+        assert_destinations_refused(ctx, lambda n, dst, stride: run(slots, n, prm(), d, msize, dst, stride), d2, isize, 1, null=False)
         ctx.sync()
         torch.cuda.synchronize()
         assert (big.cpu().numpy() == 0x5C).all()                                       # nothing was enqueued
