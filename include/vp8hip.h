@@ -454,6 +454,59 @@ typedef struct vp8hip_residual {
 } vp8hip_residual;
 size_t vp8hip_residual_size(const vp8hip_ctx *ctx, const vp8hip_residual *p);
 int  vp8hip_frames_residual_async(vp8hip_ctx *ctx, const int *slots, int n, const vp8hip_residual *p, void *dst, size_t dst_stride);
+/* ACCUMULATED motion, for models that take a P frame's flow and residual relative to one anchor picture (CoViAR's accumulate=True):
+ * every pixel traced back, hop by hop, through the frames it was predicted from to the key frame that started the group.
+ * The TRACE of a frame is d_h * d_w dwords, row-major, over the display-size luma grid d_w x d_h of the context (no other size:
+ * traces must chain exactly): pixel (y, x) holds x' in the low int16 and y' in the high int16, the position in the anchor picture
+ * this pixel descends from -- packed pairs, so that a hop is one dword gather.  vp8hip_trace_size: 4 * d_w * d_h (0: no context, or
+ * one not configured).
+ * Traces live in a POOL in the caller's device memory: pool_frames traces, entry i at pool + i * pool_stride BYTES.  A job is the
+ * vp8hip_job of vp8hip_decode with dst_fb and ref_fb[1..3] read as pool entries (-1: no trace; ref_fb[0] unused): a caller that
+ * numbers pool entries like its frame buffers passes the very jobs it decoded with, and the trace follows vp8_refs' bookkeeping --
+ * hidden frames, golden and altref updates -- with no code of its own.  Jobs of one call are independent, as for vp8hip_decode.
+ * For a job with h = its slot's header as of the call, pixel (y, x), mb = (y >> 4) * mb_cols + (x >> 4), m = the slot's record of mb,
+ * k = ((y >> 2) & 3) * 4 + ((x >> 2) & 3):
+ *     h.frame_type == 0:  T(y, x) = (x, y): the frame is an anchor; its refs are not read.
+ *     otherwise  r = m.ref_frame, v = mvs[mb * 16 + k] as stored (1/8 pel, no sign-bias flip); for an intra macroblock
+ *                (m.ref_frame == 0) r = 1 and v = (0, 0): the pixel is held in place through the last frame.
+ *                ref_fb[r] < 0 (or an m.ref_frame above 3):  T(y, x) = (x, y).
+ *                otherwise, with arithmetic >>,
+ *                    sx = clamp(x + ((v.col + 4) >> 3), 0, d_w - 1)      sy = clamp(y + ((v.row + 4) >> 3), 0, d_h - 1)
+ *                    T(y, x) = pool[ref_fb[r]](sy, sx), the whole dword
+ * -- the nearest whole pixel of the vector (ties up), the clamp standing for the border extension.  A concealed key frame says
+ * inter in its header and is traced as one.  Trace values are data and never addresses: an uninitialised entry yields garbage and
+ * nothing else, and by induction every value of a properly chained pool lies inside the picture.
+ * Enqueued on the context's stream like vp8hip_frames_side_async; it reads the slots' records and vectors, not the blocks (also on a
+ * vp8hip_configure_pooled context), and a later writer of those slots runs behind it.  Only bytes inside [pool + dst * pool_stride,
+ * + size) are written.  No device memory is added and no frame buffer is touched.  Returns -2 with nothing enqueued for n < 1; a
+ * slot out of range or never filled; pool_frames < 1; pool_stride below the size; pool or pool_stride not a multiple of 4; a pool
+ * that is not device memory of the context's device or whose pool_frames entries do not fit its allocation; a dst_fb outside
+ * 0 .. pool_frames - 1; a ref_fb[1..3] neither -1 nor in range; a dst_fb that is a ref of any job of the call or another job's
+ * dst_fb.  Whole 16-byte stores need d_w % 4 == 0 and pool, pool_stride aligned to 16; otherwise dword by dword, each once.
+ *
+ * vp8hip_trace_flow_async: any n pool entries (idx: any order, repeats allowed) as tensors [2][gh][gw] of dtype, frame i at
+ * dst + i * dst_stride BYTES.  dst_w = dst_h = 0: gw x gh = the display size; otherwise 1..16383 each, and output (y, x) takes trace
+ * pixel (sy, sx) = (((2 * y + 1) * d_h) / (2 * gh), ((2 * x + 1) * d_w) / (2 * gw)), the centre map of vp8hip_frames_side_async.
+ * Channel 0 is a = T.x(sy, sx) - sx, channel 1 is a = T.y(sy, sx) - sy: whole display pixels, signed as vp8hip_frames_side_async's
+ * vectors are (after one hop with nothing clamped channel 0 is (v.col + 4) >> 3), so that at a given size the tensor lines up
+ * element for element with vp8hip_frames_rgb_async's and vp8hip_frames_side_async's.  VP8HIP_SIDE_I16: a as an int16;
+ * VP8HIP_SIDE_F32: (float)((double)a * (double)scale[c]); VP8HIP_SIDE_F16: that float rounded to nearest-even.  Same stream, same
+ * promises.  Returns -2 with nothing enqueued for n < 1; what the trace call refuses of a pool; an idx outside the pool; one of dst_w,
+ * dst_h zero and the other not; a size outside 1..16383; a bad dtype; dst_stride below the size; dst / dst_stride not aligned to the
+ * element; a destination that is not device memory of the context's device or that cannot hold n frames.  Whole-piece stores need
+ * gw % 4 == 0 and dst, dst_stride aligned to 8 bytes (int16, halves) or 16 (floats); otherwise element by element, each once.
+ * vp8hip_trace_flow_size: bytes of one frame's tensor, 0 for what the call would refuse on p alone; ctx is read for the display size
+ * only and may be NULL for a sized grid. */
+typedef struct vp8hip_trace_flow {
+    int dst_w, dst_h;          /* both 0: the display size; otherwise 1..16383 each */
+    int dtype;                 /* VP8HIP_SIDE_I16 / F16 / F32 */
+    float scale[2];            /* x, y; read for F16 / F32 only */
+} vp8hip_trace_flow;
+size_t vp8hip_trace_size(const vp8hip_ctx *ctx);
+int  vp8hip_frames_trace_async(vp8hip_ctx *ctx, const vp8hip_job *jobs, int n, void *pool, size_t pool_stride, int pool_frames);
+size_t vp8hip_trace_flow_size(const vp8hip_ctx *ctx, const vp8hip_trace_flow *p);
+int  vp8hip_trace_flow_async(vp8hip_ctx *ctx, const int *idx, int n, const vp8hip_trace_flow *p, const void *pool, size_t pool_stride,
+                             int pool_frames, void *dst, size_t dst_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

@@ -416,6 +416,11 @@ def side_sizes(gw, gh, mv_dtype=SIDE_I16, planes=("ref", "mode", "skip")):
     return int(L.vp8hip_side_mv_size(None, ctypes.byref(p))), int(L.vp8hip_side_info_size(None, ctypes.byref(p)))
 
 
+def trace_size(w, h):
+    """bytes of one trace of Vp8Hip.frames_trace at a display size of w x h (vp8hip_trace_size): a dword per pixel"""
+    return 4 * int(w) * int(h)
+
+
 RES_LAYOUTS = {"i420": 0, "planar": 1}                        # VP8HIP_RES_I420, PLANAR
 RES_I16, RES_F16, RES_F32 = 0, 1, 2
 
@@ -463,6 +468,10 @@ class SideParams(ctypes.Structure):         # vp8hip_side, include/vp8hip.h
 
 class ResidualParams(ctypes.Structure):     # vp8hip_residual, include/vp8hip.h
     _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("layout", c_int), ("dtype", c_int), ("scale", ctypes.c_float * 3)]
+
+
+class TraceFlowParams(ctypes.Structure):    # vp8hip_trace_flow, include/vp8hip.h
+    _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("dtype", c_int), ("scale", ctypes.c_float * 2)]
 
 
 class VisParams(ctypes.Structure):          # vp8hip_vis, include/vp8hip.h
@@ -526,6 +535,13 @@ def load_hip():
         L.vp8hip_residual_size.argtypes = [c_void_p, ctypes.POINTER(ResidualParams)]
         L.vp8hip_residual_size.restype = c_size_t
         L.vp8hip_frames_residual_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(ResidualParams), c_void_p, c_size_t]
+        L.vp8hip_trace_size.argtypes = [c_void_p]
+        L.vp8hip_trace_size.restype = c_size_t
+        L.vp8hip_frames_trace_async.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int]
+        L.vp8hip_trace_flow_size.argtypes = [c_void_p, ctypes.POINTER(TraceFlowParams)]
+        L.vp8hip_trace_flow_size.restype = c_size_t
+        L.vp8hip_trace_flow_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(TraceFlowParams), c_void_p, c_size_t, c_int, c_void_p,
+                                              c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -654,14 +670,20 @@ class Vp8Hip:
     def ir_copy(self, dst, src):
         self._chk(self.L.vp8hip_ir_copy(self.h, dst, src), "vp8hip_ir_copy")
 
-    def decode(self, jobs, stages=STAGE_ALL):
-        """jobs: list of (ir_slot, dst_fb, (last, golden, alt))"""
-        arr = (Job * len(jobs))()
+    @staticmethod
+    def job_array(jobs):
+        """list of (ir_slot, dst_fb, (last, golden, alt) or None) -> a vp8hip_job array (for decode_array, or frames_trace as it is)"""
+        arr = (Job * max(len(jobs), 1))()
         for i, (slot, dst, refs) in enumerate(jobs):
             arr[i].ir_slot, arr[i].dst_fb = slot, dst
             arr[i].ref_fb[0] = -1
             for k in range(3):
                 arr[i].ref_fb[k + 1] = refs[k] if refs is not None else -1
+        return arr
+
+    def decode(self, jobs, stages=STAGE_ALL):
+        """jobs: list of (ir_slot, dst_fb, (last, golden, alt))"""
+        arr = self.job_array(jobs)
         self._jobs_keepalive = arr
         self._chk(self.L.vp8hip_decode(self.h, arr, len(jobs), stages), "vp8hip_decode")
 
@@ -926,6 +948,69 @@ class Vp8Hip:
                               lambda arr_out, stride: self.L.vp8hip_frames_residual_async(
                                   self.h, (c_int * max(n, 1))(*slots), n, ctypes.byref(p), arr_out, stride),
                               "vp8hip_frames_residual_async")[0]
+
+    def trace_pool(self, n):
+        """a pool of n traces for frames_trace on the context's device: a torch.int16 tensor [n, d_h, d_w, 2], (x', y') per pixel of
+        the display-size grid -- the position in the anchor picture the pixel descends from (include/vp8hip.h).  Not initialised."""
+        torch, dev = self._torch_device("trace_pool")
+        return torch.empty((int(n), self.height, self.width, 2), dtype=torch.int16, device=dev)
+
+    def _trace_pool_args(self, who, pool):
+        """-> (dev, pointer, stride in bytes, entries) of a pool as trace_pool makes them (a view is fine: each entry dense)"""
+        torch, dev = self._torch_device(who)
+        if not (torch.is_tensor(pool) and pool.dim() == 4 and pool.shape[0] >= 1
+                and self._dense(pool, torch.int16, (pool.shape[0], self.height, self.width, 2), dev)):
+            raise ValueError(f"{who}: pool must be an int16 tensor [n, {self.height}, {self.width}, 2], each entry dense, on {dev}")
+        return dev, c_void_p(pool.data_ptr()), pool.stride(0) * 2, int(pool.shape[0])
+
+    def frames_trace(self, jobs, pool):
+        """The traces of `jobs` -- a list of (ir_slot, dst, (last, golden, alt)) as decode takes it, dst and the three references read
+        as entries of `pool` (trace_pool; -1 or refs None: no trace) -- written into pool[dst] (vp8hip_frames_trace_async): a key
+        frame's is the identity, an inter frame's follows each pixel's vector, rounded to whole pixels and clamped to the picture,
+        into the trace of the reference its macroblock was predicted from.  A pool numbered like the frame buffers takes the very
+        jobs of decode (a vp8hip_job array made by job_array is taken as it is).  Jobs of one call are independent.  Stream
+        ordering, the `import torch` first rule and the remark on record_stream: as frames_scaled.  Returns pool."""
+        arr, n = (jobs, len(jobs)) if isinstance(jobs, ctypes.Array) else (self.job_array(list(jobs)), len(jobs))
+        dev, ptr, stride, entries = self._trace_pool_args("frames_trace", pool)
+        self._between_stream_waits(dev, lambda: self.L.vp8hip_frames_trace_async(self.h, arr, n, ptr, stride, entries),
+                                   "vp8hip_frames_trace_async")
+        return pool
+
+    def trace_flow(self, pool, idx, width=None, height=None, dtype=None, scale=None, out=None):
+        """Entries `idx` of `pool` (any order, repeats allowed) as flow tensors [n, 2, gh, gw] on the context's device
+        (vp8hip_trace_flow_async): channel 0 = x' - x, channel 1 = y' - y in whole display pixels, signed as frames_side's vectors,
+        at the display size or under each output's centre at width x height (then the tensor lines up with frames_rgb's and
+        frames_side's at that size).  torch.int16 (the default), torch.float16 or torch.float32; float types:
+        float32(float64(a) * scale[c]) with scale = (x, y) float32 numbers (default 1, 1); scale="pixels" is (gw / d_w, gh / d_h),
+        computed in float64 and rounded once: the flow in pixels of the tensor.  `out`: a tensor of that shape and type, each
+        frame dense, stride(0) free.  Stream ordering: as frames_scaled."""
+        import torch
+        idx = [int(i) for i in idx]
+        n = len(idx)
+        native, gw, gh = self._grid("trace_flow", width, height, 16)
+        if native:
+            gw, gh = self.width, self.height
+        dtype = torch.int16 if dtype is None else dtype
+        dt = _elem_dtype(dtype, _INT16_DTYPES)
+        if dt is None:
+            raise ValueError(f"trace_flow: dtype {dtype}")
+        if scale is None:
+            sc = (1.0, 1.0)
+        elif isinstance(scale, str):
+            if scale != "pixels":
+                raise ValueError(f"trace_flow: scale {scale!r}")
+            sc = (gw / self.width, gh / self.height)
+        else:
+            sc = tuple(float(v) for v in scale)
+        p = TraceFlowParams(0 if native else gw, 0 if native else gh, dt)
+        p.scale[0], p.scale[1] = np.float32(sc[0]), np.float32(sc[1])
+        if not self.L.vp8hip_trace_flow_size(self.h, ctypes.byref(p)):
+            raise ValueError(f"trace_flow: grid {gw}x{gh}: refused (sizes 1..16383)")
+        _, pptr, pstride, entries = self._trace_pool_args("trace_flow", pool)
+        return self._to_torch("trace_flow", [("out", out, _INT16_DTYPES[dt], (n, 2, gh, gw))],
+                              lambda arr_out, stride: self.L.vp8hip_trace_flow_async(
+                                  self.h, (c_int * max(n, 1))(*idx), n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
+                              "vp8hip_trace_flow_async")[0]
 
     def rgb_scratch_bytes(self):
         """device bytes of frames_rgb's scratch (vp8hip_rgb_scratch_bytes): a chunk of scaled frames as packed I420; a cache"""

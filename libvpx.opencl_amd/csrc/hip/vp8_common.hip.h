@@ -128,6 +128,34 @@ struct ResLaunch {
     ResSlot s[RES_MAX_FRAMES];
 };
 
+// One launch of vp8hip_frames_trace_async (vp8_trace.hip), as the host's plan (vp8hip_trace.hip) left it
+#define TRACE_MAX_FRAMES 128      // jobs per launch (kernel arguments: 24 bytes each)
+struct TraceJob {                 // a job and its slot's header as of the call
+    int slot;
+    int ref[3];                   // pool entries of last / golden / altref; -1: none
+    int dst;                      // the pool entry written
+    int key;                      // h.frame_type == 0: the identity, nothing read
+};
+struct TraceLaunch {
+    int dw, dh;                   // the display size: the trace's grid
+    int mb_cols, mb_rows;
+    int R;                        // macroblock rows a workgroup stages (a group); LDS = R * mb_cols * 68 bytes
+    int vec;                      // every store of a lane is a whole aligned piece (dw % 4 == 0 and pool, stride aligned to 16)
+    TraceJob j[TRACE_MAX_FRAMES];
+};
+
+// One launch of vp8hip_trace_flow_async (vp8_trace.hip)
+#define FLOW_MAX_FRAMES 512       // pool entries per launch (kernel arguments)
+struct FlowLaunch {
+    int gw, gh;                   // the output grid
+    int dw, dh;                   // the display size it is laid over: the trace's grid
+    int S;                        // workgroups that share a frame's output rows (gridDim.x)
+    int xmode;                    // SIDE_X_DISPLAY (gw is the display width: sx = x) or SIDE_X_ANY
+    int vec;                      // every store of a lane is a whole aligned piece
+    float scale[2];               // x, y; float types
+    int idx[FLOW_MAX_FRAMES];     // pool entry of frame k of the launch
+};
+
 #define WAVE 64
 
 // Macroblock tiles of the one-MB-row-per-lane pipeline (vp8_keyframe_simt.hip has the layout): three 128-byte lines per macroblock.

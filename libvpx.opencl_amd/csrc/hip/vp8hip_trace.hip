@@ -1,0 +1,138 @@
+// vp8hip_frames_trace_async and vp8hip_trace_flow_async (include/vp8hip.h): accumulated motion -- every pixel traced back through
+// the frames it was predicted from to the key frame that started the group -- in a pool in the caller's device memory, and a pool
+// entry as a flow tensor.  The plans and the checks are made here, once per call; the kernels are in vp8_trace.hip.  The trace
+// reads the slots' records and vectors (also on a vp8hip_configure_pooled context) and the pool entries its jobs name; the slots'
+// header bits come with the launch, as of this call: nothing is allocated on the device, copied or synchronised.
+#include "vp8hip_ctx.hip.h"
+
+#define TRACE_ARGS const char *slot_base, size_t slot_bytes, size_t o_mbx, size_t o_mvs, uint8_t *pool, size_t pool_stride, TraceLaunch L
+extern "C" __global__ void vp8_trace_kernel(TRACE_ARGS);
+#define FLOW_ARGS const uint8_t *pool, size_t pool_stride, uint8_t *dst, size_t dst_stride, FlowLaunch L
+extern "C" __global__ void vp8_flow_i16_kernel(FLOW_ARGS);
+extern "C" __global__ void vp8_flow_f16_kernel(FLOW_ARGS);
+extern "C" __global__ void vp8_flow_f32_kernel(FLOW_ARGS);
+
+#define TRACE_GROUP_LDS 32768                   // record dwords and vectors of a group of macroblock rows ...
+#define TRACE_GROUP_ROWS 4                      // ... and at most this many rows
+#define TRACE_MB_LDS 68                         // a macroblock in LDS: the record's first dword, sixteen vectors
+#define FLOW_PART_QUADS 8192                    // groups of four outputs a workgroup of the flow kernel walks
+
+extern "C" size_t vp8hip_trace_size(const vp8hip_ctx *c) { return c && c->width ? (size_t)4 * c->width * c->height : 0; }
+
+// the pool: pool_frames entries of the context's trace size, pool_stride apart, dword-aligned, inside one allocation of the device
+static int trace_check_pool(vp8hip_ctx *c, const char *who, const void *pool, size_t pool_stride, int pool_frames)
+{
+    if (pool_frames < 1) return fail(c, -2, "%s: a pool of %d traces", who, pool_frames);
+    return vp8hip_check_dst(c, who, pool, pool_stride, vp8hip_trace_size(c), 4, pool_frames);
+}
+
+extern "C" int vp8hip_frames_trace_async(vp8hip_ctx *c, const vp8hip_job *jobs, int n, void *pool, size_t pool_stride, int pool_frames)
+{
+    const char *who = "vp8hip_frames_trace_async";
+    if (!c || !jobs || n < 1 || !pool || c->slots.empty() || !c->width) return fail(c, -2, "%s: bad arguments", who);
+    std::vector<int> slots((size_t)n);
+    for (int i = 0; i < n; i++) slots[(size_t)i] = jobs[i].ir_slot;
+    if (int rc = vp8hip_check_slots(c, who, slots.data(), n)) return rc;
+    if (int rc = trace_check_pool(c, "vp8hip_frames_trace_async (pool)", pool, pool_stride, pool_frames)) return rc;
+    // one marker byte per pool entry: 1 a reference of some job, 2 some job's destination
+    std::vector<uint8_t> mark((size_t)pool_frames, 0);
+    for (int i = 0; i < n; i++) {
+        if (jobs[i].dst_fb < 0 || jobs[i].dst_fb >= pool_frames) return fail(c, -2, "%s: job %d: destination %d outside the pool", who, i, jobs[i].dst_fb);
+        for (int r = 1; r < 4; r++) {
+            const int e = jobs[i].ref_fb[r];
+            if (e < -1 || e >= pool_frames) return fail(c, -2, "%s: job %d: reference %d outside the pool", who, i, e);
+            if (e >= 0) mark[(size_t)e] |= 1;
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        uint8_t &m = mark[(size_t)jobs[i].dst_fb];
+        if (m) return fail(c, -2, "%s: job %d: destination %d is %s of the call", who, i, jobs[i].dst_fb, m & 1 ? "a reference" : "another job's destination");
+        m = 2;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+
+    TraceLaunch L;
+    memset(&L, 0, offsetof(TraceLaunch, j));
+    L.dw = c->width; L.dh = c->height;
+    L.mb_cols = c->dg.mb_cols; L.mb_rows = c->dg.mb_rows;
+    const size_t row_bytes = (size_t)L.mb_cols * TRACE_MB_LDS;
+    int R = (int)(TRACE_GROUP_LDS / row_bytes);
+    R = R < 1 ? 1 : R > TRACE_GROUP_ROWS ? TRACE_GROUP_ROWS : R;
+    if (R > L.mb_rows) R = L.mb_rows;
+    L.R = R;
+    const size_t lds = align_up((size_t)R * row_bytes, 16);
+    if (lds > 65536)             // (frames wider than 15408: one macroblock row is all a workgroup stages)
+        HIPCHK(c, hipFuncSetAttribute((const void *)vp8_trace_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    L.vec = L.dw % 4 == 0 && (uintptr_t)pool % 16 == 0 && pool_stride % 16 == 0;
+    const unsigned groups = (unsigned)((L.mb_rows + R - 1) / R);
+    for (int i0 = 0; i0 < n; i0 += TRACE_MAX_FRAMES) {
+        const int m = n - i0 < TRACE_MAX_FRAMES ? n - i0 : TRACE_MAX_FRAMES;
+        for (int k = 0; k < m; k++) {
+            const vp8hip_job &job = jobs[i0 + k];
+            TraceJob &J = L.j[k];
+            J.slot = job.ir_slot; J.dst = job.dst_fb;
+            J.ref[0] = job.ref_fb[1]; J.ref[1] = job.ref_fb[2]; J.ref[2] = job.ref_fb[3];
+            J.key = c->slots[(size_t)job.ir_slot].hdr_copy.frame_type == 0;
+        }
+        hipLaunchKernelGGL(vp8_trace_kernel, dim3(groups, (unsigned)m), dim3(256), (unsigned)lds, c->stream, (const char *)c->slot_block_dev,
+                           c->slot_bytes, c->o_mbx, c->o_mvs, (uint8_t *)pool, pool_stride, L);
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+// the grid of p on context c (null: sized grids only); false for what the call refuses on p alone
+static bool flow_grid(const vp8hip_ctx *c, const vp8hip_trace_flow *p, int &gw, int &gh)
+{
+    if (!p || p->dtype < 0 || p->dtype > 2) return false;
+    if (p->dst_w == 0 && p->dst_h == 0) {        // the display size: the trace's own grid
+        if (!c || !c->width) return false;
+        gw = c->width; gh = c->height;
+        return true;
+    }
+    return vp8hip_out_grid(c, p->dst_w, p->dst_h, 16, gw, gh);
+}
+
+extern "C" size_t vp8hip_trace_flow_size(const vp8hip_ctx *c, const vp8hip_trace_flow *p)
+{
+    int gw, gh;
+    return flow_grid(c, p, gw, gh) ? (size_t)2 * gh * gw * vp8hip_elem_size(p->dtype, 2) : 0;
+}
+
+extern "C" int vp8hip_trace_flow_async(vp8hip_ctx *c, const int *idx, int n, const vp8hip_trace_flow *p, const void *pool, size_t pool_stride,
+                                       int pool_frames, void *dst, size_t dst_stride)
+{
+    const char *who = "vp8hip_trace_flow_async";
+    if (!c || !idx || n < 1 || !p || !pool || !dst || !c->width) return fail(c, -2, "%s: bad arguments", who);
+    int gw, gh;
+    if (!flow_grid(c, p, gw, gh))
+        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), type %d", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE, p->dtype);
+    if (int rc = trace_check_pool(c, "vp8hip_trace_flow_async (pool)", pool, pool_stride, pool_frames)) return rc;
+    for (int i = 0; i < n; i++)
+        if (idx[i] < 0 || idx[i] >= pool_frames) return fail(c, -2, "%s: entry %d outside the pool", who, idx[i]);
+    const size_t es = (size_t)vp8hip_elem_size(p->dtype, 2);
+    const size_t size = (size_t)2 * gh * gw * es;
+    if (int rc = vp8hip_check_dst(c, "vp8hip_trace_flow_async (dst)", dst, dst_stride, size, es, n)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+
+    FlowLaunch L;
+    memset(&L, 0, offsetof(FlowLaunch, idx));
+    L.gw = gw; L.gh = gh;
+    L.dw = c->width; L.dh = c->height;
+    const long long quads = (long long)((gw + 3) >> 2) * gh;
+    L.S = (int)((quads + FLOW_PART_QUADS - 1) / FLOW_PART_QUADS);
+    if (L.S > gh) L.S = gh;
+    L.xmode = gw == c->width ? SIDE_X_DISPLAY : SIDE_X_ANY;
+    const size_t piece = 4 * es;
+    L.vec = gw % 4 == 0 && (uintptr_t)dst % piece == 0 && dst_stride % piece == 0;
+    L.scale[0] = p->scale[0]; L.scale[1] = p->scale[1];
+    void (*const kernels[3])(FLOW_ARGS) = {vp8_flow_i16_kernel, vp8_flow_f16_kernel, vp8_flow_f32_kernel};
+    for (int i0 = 0; i0 < n; i0 += FLOW_MAX_FRAMES) {
+        const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
+        memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
+        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
+                           (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
