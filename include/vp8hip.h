@@ -507,6 +507,52 @@ int  vp8hip_frames_trace_async(vp8hip_ctx *ctx, const vp8hip_job *jobs, int n, v
 size_t vp8hip_trace_flow_size(const vp8hip_ctx *ctx, const vp8hip_trace_flow *p);
 int  vp8hip_trace_flow_async(vp8hip_ctx *ctx, const int *idx, int n, const vp8hip_trace_flow *p, const void *pool, size_t pool_stride,
                              int pool_frames, void *dst, size_t dst_stride);
+/* The ACCUMULATED RESIDUAL, the other half of accumulation: a frame minus its anchor picture gathered at the frame's trace -- the
+ * difference to the group's key frame, not vp8hip_frames_residual_async's residual of one frame against its own prediction.
+ * Any n jobs (any order, repeats allowed; reusable when the call returns), each naming the frame buffer that holds the frame, the pool
+ * entry that holds its trace (vp8hip_frames_trace_async) and the frame buffer that holds the anchor picture, which the caller keeps
+ * for the group (vp8hip_frame_copy after a key frame: vp8_refs hands the key frame's buffer on once golden and altref have moved).
+ * One dense tensor [3][gh][gw] of dtype per job, frame i at dst + i * dst_stride BYTES.  dst_w = dst_h = 0: gw x gh = the display
+ * size; otherwise 1..16383 each.  For output (y, x), with d_w x d_h the display size, in integers:
+ *     sy = ((2 * y + 1) * d_h) / (2 * gh)      sx = ((2 * x + 1) * d_w) / (2 * gw)     (vp8hip_trace_flow_async's centre map; the
+ *                                                                                       identity at the display size)
+ *     t  = pool[trace](sy, sx), the whole dword
+ *     ax = clamp((int16)(t & 0xffff), 0, d_w - 1)      ay = clamp((int16)(t >> 16), 0, d_h - 1)
+ *     C(F, py, px) = the bytes R, G, B vp8hip_frames_rgb_async's convert gives with `matrix` for Y = F.y[py][px], U = F.u[py >> 1][px >> 1],
+ *                    V likewise: element (py, px) of that call's U8 planar tensor of frame buffer F at the display size
+ *     a[c] = C(fb, sy, sx)[c] - C(anchor_fb, ay, ax)[c]                                -255 .. 255
+ * Plane p holds the colour `order` puts at position p (0 = R, G, B; 1 = B, G, R).  VP8HIP_RES_I16: a as an int16; VP8HIP_RES_F32:
+ * (float)((double)a * (double)scale[c]), c by colour, not by position; VP8HIP_RES_F16: that float rounded to nearest-even.  At the
+ * display size this is rgb_u8(fb) - rgb_u8(anchor_fb)[:, ay, ax], and at any size the tensor lines up element for element with
+ * vp8hip_trace_flow_async's and vp8hip_frames_rgb_async's planar one.
+ * THE CLAMP is what it looks like: here, unlike in the trace and flow calls, a trace value becomes an address.  It is applied to every
+ * value before any address is formed, so a pool entry that nobody wrote yields garbage values and never a read outside the anchor's
+ * picture.  A properly chained pool never needs it.
+ * Same rules as its neighbours: enqueued on the context's stream -- a later launch that writes one of the frame buffers runs behind
+ * it, traces written by an earlier vp8hip_frames_trace_async are seen --; each frame buffer read in a form it has (raster where it
+ * exists, else tiles), the frame and the anchor independently of each other, none converted; no device memory added, no raster pool
+ * made for frames left as tiles, no frame buffer and no pool entry written; only bytes inside [dst + i * dst_stride, + size) written.
+ * Returns -2 with nothing enqueued for n < 1; an fb or anchor_fb out of range; what vp8hip_trace_flow_async refuses of a pool; a trace
+ * outside 0 .. pool_frames - 1; one of dst_w, dst_h zero and the other not; a size outside 1..16383; a bad matrix, order or dtype;
+ * dst_stride below the size; dst / dst_stride not aligned to the element; a destination that is not device memory of the context's
+ * device or that cannot hold n frames.  Whole-piece stores need gw % 4 == 0 and dst, dst_stride aligned to 8 bytes (int16, halves) or
+ * 16 (floats); anything else is written element by element, each once.
+ * vp8hip_trace_residual_size: 3 * gh * gw * element size; 0 for what the call would refuse on p alone; ctx is read for the display
+ * size only and may be NULL for a sized grid. */
+typedef struct vp8hip_anchor_job {     /* one output frame */
+    int32_t fb;                /* frame buffer that holds the frame */
+    int32_t trace;             /* pool entry that holds its trace (vp8hip_frames_trace_async) */
+    int32_t anchor_fb;         /* frame buffer that holds the anchor picture, kept by the caller for the group */
+} vp8hip_anchor_job;
+typedef struct vp8hip_trace_residual {
+    int dst_w, dst_h;          /* both 0: the display size; otherwise 1..16383 each */
+    int matrix, order;         /* VP8HIP_RGB_BT601 / _BT601_FULL / _BT709; 0 = R, G, B  1 = B, G, R: vp8hip_frames_rgb_async's */
+    int dtype;                 /* VP8HIP_RES_I16 / F16 / F32 */
+    float scale[3];            /* by colour R, G, B; read for F16 / F32 only */
+} vp8hip_trace_residual;
+size_t vp8hip_trace_residual_size(const vp8hip_ctx *ctx, const vp8hip_trace_residual *p);
+int  vp8hip_trace_residual_async(vp8hip_ctx *ctx, const vp8hip_anchor_job *jobs, int n, const vp8hip_trace_residual *p,
+                                 const void *pool, size_t pool_stride, int pool_frames, void *dst, size_t dst_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

@@ -421,6 +421,17 @@ def trace_size(w, h):
     return 4 * int(w) * int(h)
 
 
+def trace_residual_size(gw, gh, dtype=0):
+    """bytes of one frame's tensor of Vp8Hip.trace_residual on a grid of gw x gh (vp8hip_trace_residual_size): 3 * gh * gw elements;
+    0 for a size outside 1..16383 or an unknown type.  dtype: RES_I16 / RES_F16 / RES_F32 or the torch / numpy type's name.  For the
+    display size pass the display size."""
+    dt = _elem_dtype(dtype, _INT16_DTYPES)
+    if dt is None or gw == 0 or gh == 0:         # (0 x 0 would ask for the display size, which needs a context)
+        return 0
+    p = TraceResidualParams(int(gw), int(gh), 0, 0, dt)
+    return int(load_hip().vp8hip_trace_residual_size(None, ctypes.byref(p)))
+
+
 RES_LAYOUTS = {"i420": 0, "planar": 1}                        # VP8HIP_RES_I420, PLANAR
 RES_I16, RES_F16, RES_F32 = 0, 1, 2
 
@@ -472,6 +483,14 @@ class ResidualParams(ctypes.Structure):     # vp8hip_residual, include/vp8hip.h
 
 class TraceFlowParams(ctypes.Structure):    # vp8hip_trace_flow, include/vp8hip.h
     _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("dtype", c_int), ("scale", ctypes.c_float * 2)]
+
+
+class AnchorJob(ctypes.Structure):          # vp8hip_anchor_job, include/vp8hip.h
+    _fields_ = [("fb", ctypes.c_int32), ("trace", ctypes.c_int32), ("anchor_fb", ctypes.c_int32)]
+
+
+class TraceResidualParams(ctypes.Structure):    # vp8hip_trace_residual, include/vp8hip.h
+    _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("matrix", c_int), ("order", c_int), ("dtype", c_int), ("scale", ctypes.c_float * 3)]
 
 
 class VisParams(ctypes.Structure):          # vp8hip_vis, include/vp8hip.h
@@ -542,6 +561,10 @@ def load_hip():
         L.vp8hip_trace_flow_size.restype = c_size_t
         L.vp8hip_trace_flow_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(TraceFlowParams), c_void_p, c_size_t, c_int, c_void_p,
                                               c_size_t]
+        L.vp8hip_trace_residual_size.argtypes = [c_void_p, ctypes.POINTER(TraceResidualParams)]
+        L.vp8hip_trace_residual_size.restype = c_size_t
+        L.vp8hip_trace_residual_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(TraceResidualParams), c_void_p, c_size_t, c_int,
+                                                  c_void_p, c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1011,6 +1034,50 @@ class Vp8Hip:
                               lambda arr_out, stride: self.L.vp8hip_trace_flow_async(
                                   self.h, (c_int * max(n, 1))(*idx), n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
                               "vp8hip_trace_flow_async")[0]
+
+    def trace_residual(self, pool, jobs, width=None, height=None, dtype=None, matrix="bt601", order="rgb", scale=None, out=None):
+        """The accumulated residual of `jobs` -- a list of (fb, entry, anchor_fb): the frame buffer that holds a frame, the entry of
+        `pool` that holds its trace (frames_trace) and the frame buffer the caller keeps the group's anchor picture in; any order,
+        repeats allowed -- as tensors [n, 3, gh, gw] on the context's device (vp8hip_trace_residual_async): the frame's RGB bytes
+        minus the anchor's at the position the trace names (clamped to the picture), -255 .. 255, converted with `matrix` and in
+        `order` as frames_rgb's "nchw" tensor is, at the display size or under each output's centre at width x height (then the
+        tensor lines up with frames_rgb's and trace_flow's at that size).  torch.int16 (the default), torch.float16 or
+        torch.float32; float types: float32(float64(a) * scale[c]) with scale = one number or (R, G, B), by colour, float32
+        (default 1).  Both frame buffers are read in the form they have; nothing is converted or allocated.  `out`: a tensor of that
+        shape and type, each frame dense, stride(0) free.  Stream ordering: as frames_scaled."""
+        import torch
+        jobs = [tuple(int(v) for v in j) for j in jobs]
+        n = len(jobs)
+        if any(len(j) != 3 for j in jobs):
+            raise ValueError("trace_residual: jobs are (fb, entry, anchor_fb)")
+        native, gw, gh = self._grid("trace_residual", width, height, 16)
+        if native:
+            gw, gh = self.width, self.height
+        dtype = torch.int16 if dtype is None else dtype
+        dt = _elem_dtype(dtype, _INT16_DTYPES)
+        if dt is None or matrix not in RGB_MATRICES or order not in RGB_ORDERS:
+            raise ValueError(f"trace_residual: dtype {dtype}, matrix {matrix!r}, order {order!r}")
+        if scale is None:
+            sc = (1.0, 1.0, 1.0)
+        elif isinstance(scale, str):
+            raise ValueError(f"trace_residual: scale {scale!r}")
+        elif np.ndim(scale) == 0:
+            sc = (float(scale),) * 3
+        else:
+            sc = tuple(float(v) for v in scale)
+            if len(sc) != 3:
+                raise ValueError(f"trace_residual: scale {scale!r}")
+        p = TraceResidualParams(0 if native else gw, 0 if native else gh, RGB_MATRICES[matrix], RGB_ORDERS[order], dt)
+        for c in range(3):
+            p.scale[c] = np.float32(sc[c])
+        if not self.L.vp8hip_trace_residual_size(self.h, ctypes.byref(p)):
+            raise ValueError(f"trace_residual: grid {gw}x{gh}: refused (sizes 1..16383)")
+        _, pptr, pstride, entries = self._trace_pool_args("trace_residual", pool)
+        arr = (AnchorJob * max(n, 1))(*jobs)
+        return self._to_torch("trace_residual", [("out", out, _INT16_DTYPES[dt], (n, 3, gh, gw))],
+                              lambda arr_out, stride: self.L.vp8hip_trace_residual_async(
+                                  self.h, arr, n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
+                              "vp8hip_trace_residual_async")[0]
 
     def rgb_scratch_bytes(self):
         """device bytes of frames_rgb's scratch (vp8hip_rgb_scratch_bytes): a chunk of scaled frames as packed I420; a cache"""

@@ -156,6 +156,28 @@ struct FlowLaunch {
     int idx[FLOW_MAX_FRAMES];     // pool entry of frame k of the launch
 };
 
+// One launch of vp8hip_trace_residual_async (vp8_trace_residual.hip), as the host's plan (vp8hip_trace.hip) left it
+#define ANCHOR_MAX_FRAMES 128     // jobs per launch (kernel arguments: 12 bytes each)
+struct AnchorJob {
+    int fb;                       // the frame: frame buffer << 2 | form (SCALE_FROM_*), as of the call
+    int trace;                    // the pool entry that holds its trace
+    int anchor;                   // the anchor picture: frame buffer << 2 | form
+};
+struct AnchorLaunch {
+    int gw, gh;                   // the output grid
+    int dw, dh;                   // the display size it is laid over: the trace's grid, and what trace values are clamped to
+    int S;                        // workgroups that share a job's output rows (gridDim.x)
+    int xmode;                    // SIDE_X_DISPLAY (gw is the display width: sx = x) or SIDE_X_ANY
+    int vec;                      // every store of a lane is a whole aligned piece
+    int mb_cols;
+    int aw, ah;                   // the aligned area of the luma plane (chroma: half of it)
+    int y_off, u_off, v_off, y_stride, uv_stride;    // the raster form: the planes' origins in a frame buffer and their strides
+    int cy, k0;                   // RgbLaunch's: the byte at POSITION p = clamp255((cy * Y + k0 + cu[p] * (U - 128) + cv[p] * (V - 128)) >> 8)
+    int cu[3], cv[3];
+    float scale[3];               // by position; float types
+    AnchorJob j[ANCHOR_MAX_FRAMES];
+};
+
 #define WAVE 64
 
 // Macroblock tiles of the one-MB-row-per-lane pipeline (vp8_keyframe_simt.hip has the layout): three 128-byte lines per macroblock.

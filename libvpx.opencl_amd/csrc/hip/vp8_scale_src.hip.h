@@ -1,6 +1,6 @@
-// The frame-source side shared by the kernels that read decoded frames row by row (vp8_scale.hip, vp8_rgb.hip): a plane of a frame
-// buffer in either of its forms by coordinate (ScaleSrc), a band of source rows in LDS (ScaleLdsSrc), and the staging of one source
-// row into an LDS slot with 16-byte (chroma: 8-byte) loads (stage_piece).
+// The frame-source side shared by the kernels that read decoded frames (vp8_scale.hip, vp8_rgb.hip row by row, vp8_trace_residual.hip
+// by coordinate): a plane of a frame buffer in either of its forms by coordinate (ScaleSrc), a band of source rows in LDS
+// (ScaleLdsSrc), and the staging of one source row into an LDS slot with 16-byte (chroma: 8-byte) loads (stage_piece).
 #pragma once
 #include "vp8_common.hip.h"
 
@@ -17,21 +17,45 @@ struct ScaleSrc {
 
     __device__ __forceinline__ void row(int, int) {}
 
-    __device__ __forceinline__ int at(int x, int y) const
+    // byte offset of (x, y), clamped to the aligned area
+    __device__ __forceinline__ int off(int x, int y) const
     {
         x = min(max(x, 0), aw1);
         y = min(max(y, 0), ah1);
         if constexpr (FORM == SCALE_FROM_RASTER) {
-            return base[y * stride + x];
+            return y * stride + x;
         } else {
             // rows 0..wr-1 of a tile hold the macroblock's window (columns shifted left by 4), the rest its own columns
             const int m = (1 << lg) - 1;
             const int r = y >> lg, ry = y & m;
             const bool win = ry < wr;
             const int xx = win ? x + 4 : x;
-            const int off = (win ? wbase + (ry << lg) : obase + ((ry - wr) << lg)) + (xx & m);
-            return base[r * stride + (xx >> lg) * VP8_TILE_BYTES + off];
+            const int o = (win ? wbase + (ry << lg) : obase + ((ry - wr) << lg)) + (xx & m);
+            return r * stride + (xx >> lg) * VP8_TILE_BYTES + o;
         }
+    }
+
+    __device__ __forceinline__ int at(int x, int y) const { return base[off(x, y)]; }
+
+    // N = 2 or 4 neighbouring columns of row y from column x as one load, low byte first.  x is a multiple of N and x + N - 1 lies
+    // inside the aligned area: such columns never leave a tile row, the window's shift by 4 included, and the load is aligned
+    template <int N>
+    __device__ __forceinline__ unsigned atN(int x, int y) const
+    {
+        if constexpr (N == 4) return *(g_cu32p)(base + off(x, y));
+        else return *(const GLOBAL_AS unsigned short *)(base + off(x, y));
+    }
+
+    // four neighbouring columns of row y from ANY column x, low byte first: the aligned dword that holds column x and the one that
+    // holds column x + 3 -- the same one, or the next in the row or in the next tile's row; an aligned dword never leaves a row
+    // piece, the window's shift by 4 included --, shifted together.  Both addresses are clamped as at() clamps: a column past the
+    // aligned area yields a byte of the area, never a read outside it.  The same in every lane whatever x is: no lane falls
+    // back to bytes where four columns straddle two tiles
+    __device__ __forceinline__ unsigned at4_any(int x, int y) const
+    {
+        const int o = off(x, y);
+        const unsigned lo = *(g_cu32p)(base + (o & ~3)), hi = *(g_cu32p)(base + (off(x + 3, y) & ~3));
+        return __builtin_amdgcn_alignbyte(hi, lo, (unsigned)o & 3u);
     }
 };
 

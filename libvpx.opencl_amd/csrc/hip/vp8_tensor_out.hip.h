@@ -30,6 +30,28 @@ __device__ __forceinline__ unsigned tensor_value(int v, float scale)
     }
 }
 
+// v[0..3] (int16 each) x one scale as the bits of four elements: tensor_value four times -- but the halves are made two at a time, by
+// the packed conversion.  Asked for one at a time, the compiler may fuse the multiply and the conversion of a half into one
+// v_fma_mixlo_f16, which rounds the exact product once (the definition rounds twice: to a float, then to a half) and gives +0 for -0.
+template <int DTYPE>
+__device__ __forceinline__ void tensor_values4(const int (&v)[4], float scale, unsigned (&e)[4])
+{
+    if constexpr (DTYPE != TENSOR_F16) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) e[i] = tensor_value<DTYPE>(v[i], scale);
+    } else {
+        typedef float f32x2_t __attribute__((ext_vector_type(2)));
+        typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+#pragma unroll
+        for (int i = 0; i < 4; i += 2) {
+            const f32x2_t f = {__fmul_rn((float)v[i], scale), __fmul_rn((float)v[i + 1], scale)};
+            const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(f, f16x2_t));
+            e[i] = u & 0xffffu;
+            e[i + 1] = u >> 16;
+        }
+    }
+}
+
 // the centre map: the sample output i of a grid of g takes, the grid laid over d samples
 __device__ __forceinline__ int tensor_src(int i, int g, int d)
 {

@@ -6,7 +6,8 @@
 //   vp8hip_visualize.hip vp8hip_visualize
 //   vp8hip_scale.hip, vp8hip_rgb.hip, vp8hip_side.hip, vp8hip_residual.hip   vp8hip_frames_scale_async, _rgb_async, _side_async,
 //                       _residual_async: frames, and what the slots hold beside them, as tensors in the caller's device memory
-//   vp8hip_trace.hip    vp8hip_frames_trace_async, vp8hip_trace_flow_async: accumulated motion in a pool in the caller's device memory
+//   vp8hip_trace.hip    vp8hip_frames_trace_async, vp8hip_trace_flow_async, vp8hip_trace_residual_async: accumulated motion in a
+//                       pool in the caller's device memory, and what reads it
 //   vp8hip_handover.hip the checks those calls share
 #pragma once
 #include <hip/hip_runtime.h>
@@ -167,6 +168,8 @@ int vp8hip_check_status(vp8hip_ctx *c);       // after a stream synchronisation:
 // (returns the LDS a workgroup takes), one launch of at most SCALE_MAX_FRAMES frames
 int vp8hip_scale_plan(const vp8hip_ctx *c, int dw, int dh, int filter, ScaleLaunch &L);
 int vp8hip_scale_enqueue(vp8hip_ctx *c, const int *fbs, int m, ScaleLaunch &L, int lds, void *dst, size_t dst_stride);
+// vp8hip_rgb.hip: the conversion's coefficients by position, for the kernels that make RGB bytes (vp8_rgb.hip, vp8_trace_residual.hip)
+void vp8hip_rgb_coeffs(int matrix, int order, int &cy, int &k0, int (&cu)[3], int (&cv)[3]);
 // the form a reader that converts nothing takes a frame buffer in: raster where it exists, else tiles; never written: zeros
 static inline int vp8hip_frame_form(const vp8hip_ctx *c, int fb)
 {
@@ -174,7 +177,7 @@ static inline int vp8hip_frame_form(const vp8hip_ctx *c, int fb)
     return (st & FB_RASTER) && c->fb_block ? SCALE_FROM_RASTER : (st & FB_TILES) ? SCALE_FROM_TILES : SCALE_FROM_ZERO;
 }
 
-// vp8hip_handover.hip: what the four calls that write tensors into the caller's device memory share.  The checks return 0, or -2
+// vp8hip_handover.hip: what the calls that write tensors into the caller's device memory share.  The checks return 0, or -2
 // with the error set (its text begins with `who`); vp8hip_check_dst: stride >= size, destination and stride aligned to the
 // element, then vp8hip_check_device_span: device memory of the context's device, the n frames inside one allocation.
 #define VP8HIP_MAX_OUT_SIZE 16383       // the largest width / height of an output

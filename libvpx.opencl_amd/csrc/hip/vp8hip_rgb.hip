@@ -23,6 +23,20 @@ static const int rgb_matrix[3][6] = {
     {16, 298, 459, -55, -136, 541},             // BT.709, limited range
 };
 
+// the kernels' coefficients of a matrix (VP8HIP_RGB_BT601 ...: 0..2), by POSITION (order 1 swaps the first and the third channel):
+// the byte at position p = clamp255((cy * Y + k0 + cu[p] * (U - 128) + cv[p] * (V - 128)) >> 8)
+void vp8hip_rgb_coeffs(int matrix, int order, int &cy, int &k0, int (&cu)[3], int (&cv)[3])
+{
+    const int *m = rgb_matrix[matrix];
+    cy = m[1];
+    k0 = 128 - m[1] * m[0];
+    const int ucol[3] = {0, m[3], m[5]}, vcol[3] = {m[2], m[4], 0};
+    for (int pos = 0; pos < 3; pos++) {
+        const int col = order ? 2 - pos : pos;
+        cu[pos] = ucol[col]; cv[pos] = vcol[col];
+    }
+}
+
 extern "C" size_t vp8hip_rgb_size(const vp8hip_rgb *p)
 {
     if (!p || p->dst_w < 1 || p->dst_h < 1 || p->dst_w > VP8HIP_MAX_OUT_SIZE || p->dst_h > VP8HIP_MAX_OUT_SIZE) return 0;
@@ -68,13 +82,9 @@ static int rgb_plan(const vp8hip_ctx *c, const vp8hip_rgb &p, bool from_frames, 
     pairs = pairs < 1 ? 1 : pairs > 32 ? 32 : pairs;      // (two rows of the widest frame: 49 KB)
     if (pairs > (h + 1) / 2) pairs = (h + 1) / 2;
     L.br = 2 * pairs;
-    const int *m = rgb_matrix[p.matrix];
-    L.cy = m[1];
-    L.k0 = 128 - m[1] * m[0];
-    const int cu[3] = {0, m[3], m[5]}, cv[3] = {m[2], m[4], 0};
+    vp8hip_rgb_coeffs(p.matrix, p.order, L.cy, L.k0, L.cu, L.cv);
     for (int pos = 0; pos < 3; pos++) {
         const int col = p.order ? 2 - pos : pos;
-        L.cu[pos] = cu[col]; L.cv[pos] = cv[col];
         L.scale[pos] = p.scale[col]; L.bias[pos] = p.bias[col];
     }
     const int es = vp8hip_elem_size(p.dtype, 1);

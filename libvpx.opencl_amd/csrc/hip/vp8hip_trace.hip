@@ -1,6 +1,7 @@
-// vp8hip_frames_trace_async and vp8hip_trace_flow_async (include/vp8hip.h): accumulated motion -- every pixel traced back through
-// the frames it was predicted from to the key frame that started the group -- in a pool in the caller's device memory, and a pool
-// entry as a flow tensor.  The plans and the checks are made here, once per call; the kernels are in vp8_trace.hip.  The trace
+// vp8hip_frames_trace_async, vp8hip_trace_flow_async and vp8hip_trace_residual_async (include/vp8hip.h): accumulated motion -- every
+// pixel traced back through the frames it was predicted from to the key frame that started the group -- in a pool in the caller's
+// device memory, a pool entry as a flow tensor, and a frame minus its anchor picture gathered at its trace as a residual tensor.  The
+// plans and the checks are made here, once per call; the kernels are in vp8_trace.hip and vp8_trace_residual.hip.  The trace
 // reads the slots' records and vectors (also on a vp8hip_configure_pooled context) and the pool entries its jobs name; the slots'
 // header bits come with the launch, as of this call: nothing is allocated on the device, copied or synchronised.
 #include "vp8hip_ctx.hip.h"
@@ -12,10 +13,17 @@ extern "C" __global__ void vp8_flow_i16_kernel(FLOW_ARGS);
 extern "C" __global__ void vp8_flow_f16_kernel(FLOW_ARGS);
 extern "C" __global__ void vp8_flow_f32_kernel(FLOW_ARGS);
 
+#define ANCHOR_ARGS const uint8_t *raster, size_t fb_stride, const uint8_t *tiles, size_t tile_frame, const uint8_t *pool, size_t pool_stride, \
+                    uint8_t *dst, size_t dst_stride, AnchorLaunch L
+extern "C" __global__ void vp8_anchor_i16_kernel(ANCHOR_ARGS);
+extern "C" __global__ void vp8_anchor_f16_kernel(ANCHOR_ARGS);
+extern "C" __global__ void vp8_anchor_f32_kernel(ANCHOR_ARGS);
+
 #define TRACE_GROUP_LDS 32768                   // record dwords and vectors of a group of macroblock rows ...
 #define TRACE_GROUP_ROWS 4                      // ... and at most this many rows
 #define TRACE_MB_LDS 68                         // a macroblock in LDS: the record's first dword, sixteen vectors
 #define FLOW_PART_QUADS 8192                    // groups of four outputs a workgroup of the flow kernel walks
+#define ANCHOR_PART_QUADS 4096                  // ... and of the residual kernel: its loads wait on the trace's, so more waves in flight
 
 extern "C" size_t vp8hip_trace_size(const vp8hip_ctx *c) { return c && c->width ? (size_t)4 * c->width * c->height : 0; }
 
@@ -81,16 +89,21 @@ extern "C" int vp8hip_frames_trace_async(vp8hip_ctx *c, const vp8hip_job *jobs, 
     return 0;
 }
 
-// the grid of p on context c (null: sized grids only); false for what the call refuses on p alone
-static bool flow_grid(const vp8hip_ctx *c, const vp8hip_trace_flow *p, int &gw, int &gh)
+// the grid of dst_w x dst_h on context c (null: sized grids only); false for what the calls refuse
+static bool trace_out_grid(const vp8hip_ctx *c, int dst_w, int dst_h, int &gw, int &gh)
 {
-    if (!p || p->dtype < 0 || p->dtype > 2) return false;
-    if (p->dst_w == 0 && p->dst_h == 0) {        // the display size: the trace's own grid
+    if (dst_w == 0 && dst_h == 0) {              // the display size: the trace's own grid
         if (!c || !c->width) return false;
         gw = c->width; gh = c->height;
         return true;
     }
-    return vp8hip_out_grid(c, p->dst_w, p->dst_h, 16, gw, gh);
+    return vp8hip_out_grid(c, dst_w, dst_h, 16, gw, gh);
+}
+
+// the grid of p on context c; false for what the call refuses on p alone
+static bool flow_grid(const vp8hip_ctx *c, const vp8hip_trace_flow *p, int &gw, int &gh)
+{
+    return p && p->dtype >= 0 && p->dtype <= 2 && trace_out_grid(c, p->dst_w, p->dst_h, gw, gh);
 }
 
 extern "C" size_t vp8hip_trace_flow_size(const vp8hip_ctx *c, const vp8hip_trace_flow *p)
@@ -131,6 +144,74 @@ extern "C" int vp8hip_trace_flow_async(vp8hip_ctx *c, const int *idx, int n, con
         const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
         memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
         hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
+                           (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+// the grid of p on context c; false for what the call refuses on p alone
+static bool anchor_grid(const vp8hip_ctx *c, const vp8hip_trace_residual *p, int &gw, int &gh)
+{
+    return p && p->dtype >= 0 && p->dtype <= 2 && p->matrix >= 0 && p->matrix <= 2 && p->order >= 0 && p->order <= 1 &&
+           trace_out_grid(c, p->dst_w, p->dst_h, gw, gh);
+}
+
+extern "C" size_t vp8hip_trace_residual_size(const vp8hip_ctx *c, const vp8hip_trace_residual *p)
+{
+    int gw, gh;
+    return anchor_grid(c, p, gw, gh) ? (size_t)3 * gh * gw * vp8hip_elem_size(p->dtype, 2) : 0;
+}
+
+extern "C" int vp8hip_trace_residual_async(vp8hip_ctx *c, const vp8hip_anchor_job *jobs, int n, const vp8hip_trace_residual *p, const void *pool,
+                                           size_t pool_stride, int pool_frames, void *dst, size_t dst_stride)
+{
+    const char *who = "vp8hip_trace_residual_async";
+    if (!c || !jobs || n < 1 || !p || !pool || !dst || !c->width || c->fb.empty()) return fail(c, -2, "%s: bad arguments", who);
+    for (int i = 0; i < n; i++) {
+        const int fbs[2] = {jobs[i].fb, jobs[i].anchor_fb};
+        if (int rc = vp8hip_check_fbs(c, who, fbs, 2)) return rc;
+    }
+    int gw, gh;
+    if (!anchor_grid(c, p, gw, gh))
+        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), matrix %d, order %d, type %d", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE,
+                    p->matrix, p->order, p->dtype);
+    if (int rc = trace_check_pool(c, "vp8hip_trace_residual_async (pool)", pool, pool_stride, pool_frames)) return rc;
+    for (int i = 0; i < n; i++)
+        if (jobs[i].trace < 0 || jobs[i].trace >= pool_frames) return fail(c, -2, "%s: job %d: trace %d outside the pool", who, i, jobs[i].trace);
+    const size_t es = (size_t)vp8hip_elem_size(p->dtype, 2);
+    const size_t size = (size_t)3 * gh * gw * es;
+    if (int rc = vp8hip_check_dst(c, "vp8hip_trace_residual_async (dst)", dst, dst_stride, size, es, n)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+
+    AnchorLaunch L;
+    memset(&L, 0, offsetof(AnchorLaunch, j));
+    L.gw = gw; L.gh = gh;
+    L.dw = c->width; L.dh = c->height;
+    const long long quads = (long long)((gw + 3) >> 2) * gh;
+    L.S = (int)((quads + ANCHOR_PART_QUADS - 1) / ANCHOR_PART_QUADS);
+    if (L.S > gh) L.S = gh;
+    L.xmode = gw == c->width ? SIDE_X_DISPLAY : SIDE_X_ANY;
+    const size_t piece = 4 * es;
+    L.vec = gw % 4 == 0 && (uintptr_t)dst % piece == 0 && dst_stride % piece == 0;
+    L.mb_cols = c->dg.mb_cols;
+    L.aw = c->dg.aligned_w; L.ah = c->dg.aligned_h;
+    L.y_off = c->dg.y_off; L.u_off = c->dg.u_off; L.v_off = c->dg.v_off;
+    L.y_stride = c->dg.y_stride; L.uv_stride = c->dg.uv_stride;
+    vp8hip_rgb_coeffs(p->matrix, p->order, L.cy, L.k0, L.cu, L.cv);
+    for (int pos = 0; pos < 3; pos++) L.scale[pos] = p->scale[p->order ? 2 - pos : pos];
+    void (*const kernels[3])(ANCHOR_ARGS) = {vp8_anchor_i16_kernel, vp8_anchor_f16_kernel, vp8_anchor_f32_kernel};
+    for (int i0 = 0; i0 < n; i0 += ANCHOR_MAX_FRAMES) {
+        const int m = n - i0 < ANCHOR_MAX_FRAMES ? n - i0 : ANCHOR_MAX_FRAMES;
+        for (int k = 0; k < m; k++) {
+            const vp8hip_anchor_job &job = jobs[i0 + k];
+            // each frame buffer in a form it has: raster where it exists, else tiles; the two of a job independently
+            L.j[k].fb = job.fb << 2 | vp8hip_frame_form(c, job.fb);
+            L.j[k].trace = job.trace;
+            L.j[k].anchor = job.anchor_fb << 2 | vp8hip_frame_form(c, job.anchor_fb);
+        }
+        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)c->fb_block, c->fb_stride,
+                           (const uint8_t *)c->tile_block, c->tile_frame, (const uint8_t *)pool, pool_stride,
                            (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
         HIPCHK(c, hipGetLastError());
     }
