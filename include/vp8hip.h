@@ -553,6 +553,69 @@ typedef struct vp8hip_trace_residual {
 size_t vp8hip_trace_residual_size(const vp8hip_ctx *ctx, const vp8hip_trace_residual *p);
 int  vp8hip_trace_residual_async(vp8hip_ctx *ctx, const vp8hip_anchor_job *jobs, int n, const vp8hip_trace_residual *p,
                                  const void *pool, size_t pool_stride, int pool_frames, void *dst, size_t dst_stride);
+/* The GATHER ALONG THE TRACE: a tensor of the caller's carried from the anchor picture to a later frame -- what inference with codec
+ * motion does with the result a heavy network gave for the key frame (feature maps of any stride, logits, a label map).  Any n jobs
+ * (any order, repeats allowed; reusable when the call returns), each naming the pool entry that holds a frame's trace
+ * (vp8hip_frames_trace_async) and one of src_frames SOURCE TENSORS, tensor k at src + k * src_stride BYTES; output i at
+ * dst + i * dst_stride BYTES.  Both are the caller's device memory and dense, `channels` elements of `elem` bytes per cell:
+ * VP8HIP_GATHER_PLANAR [C][h][w], VP8HIP_GATHER_CHANNELS_LAST [h][w][C]; the output has the source's layout and element size.  No frame
+ * buffer and no IR slot is read.  With d_w x d_h the display size, sw x sh = src_w x src_h the source grid and gw x gh the output grid
+ * (dst_w = dst_h = 0: the display size; otherwise 1..16383 each), for output (y, x), in integers:
+ *     sy = ((2 * y + 1) * d_h) / (2 * gh)      sx = ((2 * x + 1) * d_w) / (2 * gw)     (vp8hip_trace_flow_async's centre map; the
+ *                                                                                       identity at the display size)
+ *     t  = pool[trace](sy, sx), the whole dword
+ *     ax = clamp((int16)(t & 0xffff), 0, d_w - 1)      ay = clamp((int16)(t >> 16), 0, d_h - 1)
+ *     NEAREST:   cx = ((2 * ax + 1) * sw) / (2 * d_w)      cy = ((2 * ay + 1) * sh) / (2 * d_h)      the cell under the anchor pixel's centre
+ *                out[c](y, x) = src[c](cy, cx), the element's bits, for every c
+ *     BILINEAR:  px = clamp(((2 * ax + 1) * sw * 128) / d_w - 128, 0, (sw - 1) * 256)      (64-bit) the pixel's centre in 1/256 cells,
+ *                x0 = px >> 8, wx = px & 255, x1 = min(x0 + 1, sw - 1); py, y0, wy, y1 likewise       counted from the cells' centres
+ *                R  = (a (256 - wx)(256 - wy) + b wx (256 - wy) + c' (256 - wx) wy + d wx wy) / 65536   in real numbers,
+ *                     a = src(y0, x0), b = src(y0, x1), c' = src(y1, x0), d = src(y1, x1)
+ * With sw = d_w / s for a stride s that divides d_w, cx == ax / s.  cx is monotone in ax; for sw <= d_w it takes every cell 0 .. sw - 1,
+ * and for sw > d_w the d_w pixels name d_w different cells (they cannot name more).  With sw == d_w every wx is 0, so BILINEAR equals
+ * NEAREST bit for bit (likewise sh, wy).  With all four weights on one corner the output is that corner's value exactly, for finite
+ * inputs.
+ * NEAREST moves bits of any meaning.  BILINEAR reads elements of 2 bytes as IEEE halves and of 4 as floats, refuses 1, works in single
+ * precision and delivers a value within a derived bound of R, M = max(|a|, |b|, |c'|, |d|):
+ *     floats:  |out - R| <= 8 * 2^-24 * M                         both natural orders (two lerps then one; four weighted products summed) make at
+ *                                                                 most six roundings of relative error 2^-24 on magnitudes <= M; a third is left over
+ *     halves:  |out - R| <= 8 * 2^-24 * M + 2^-11 * |R| + 2^-25   widened exactly, float arithmetic (the first term), one rounding to the
+ *                                                                 nearest-even half (the second), half the smallest subnormal half (the third)
+ * Non-finite inputs give unspecified values and nothing else.
+ * THE CLAMP: as in vp8hip_trace_residual_async a trace value becomes an address.  Every value is clamped before any address is formed,
+ * and cx < sw, cy < sh, x1 < sw, y1 < sh follow from the formulas: a pool entry nobody wrote yields garbage values and never a read
+ * outside the job's source tensor.
+ * Same rules as its neighbours: enqueued on the context's stream, so traces written by an earlier vp8hip_frames_trace_async are seen;
+ * no device memory added; no pool entry, source tensor or frame buffer written; only bytes inside [dst + i * dst_stride, + size)
+ * written.  Returns -2 with nothing enqueued for n < 1; what vp8hip_trace_flow_async refuses of a pool; a trace outside
+ * 0 .. pool_frames - 1 or a src outside 0 .. src_frames - 1; one of dst_w, dst_h zero and the other not; a size outside 1..16383;
+ * src_w or src_h outside 1..16383; channels outside 1..4096; an elem other than 1, 2, 4; a bad layout or filter; BILINEAR with
+ * elem == 1; src_stride or dst_stride below its tensor's size; src, dst or their strides not aligned to the element; src or dst that
+ * is not device memory of the context's device or whose frames do not fit the allocation; [src, + src_frames * src_stride)
+ * overlapping [dst, + n * dst_stride).  Whole-piece stores: PLANAR needs gw % 4 == 0 and dst, dst_stride aligned to 4 * elem;
+ * CHANNELS_LAST needs channels * elem, dst, dst_stride, src and src_stride to be multiples of 16; anything else is written element by
+ * element, each once.
+ * The source is checked by the code that checks destinations: an error text that begins "vp8hip_trace_gather_async (src)" and speaks of
+ * "the destination" means src and src_stride.
+ * vp8hip_trace_gather_size: channels * gh * gw * elem, the bytes of one output; 0 for what the call would refuse on p alone; ctx is
+ * read for the display size only and may be NULL for a sized grid. */
+typedef struct vp8hip_gather_job {     /* one output */
+    int32_t trace;             /* pool entry that holds the frame's trace (vp8hip_frames_trace_async) */
+    int32_t src;               /* index of the source tensor */
+} vp8hip_gather_job;
+enum { VP8HIP_GATHER_NEAREST = 0, VP8HIP_GATHER_BILINEAR = 1 };
+enum { VP8HIP_GATHER_PLANAR = 0, VP8HIP_GATHER_CHANNELS_LAST = 1 };
+typedef struct vp8hip_trace_gather {
+    int dst_w, dst_h;          /* both 0: the display size; otherwise 1..16383 each */
+    int src_w, src_h;          /* the source tensors' grid, 1..16383 each: a feature map of any stride, or the picture's size */
+    int channels;              /* 1..4096 */
+    int elem;                  /* bytes of an element: 1, 2 or 4.  NEAREST moves bits; BILINEAR reads 2 as IEEE halves, 4 as floats, refuses 1 */
+    int layout, filter;        /* VP8HIP_GATHER_PLANAR / _CHANNELS_LAST; VP8HIP_GATHER_NEAREST / _BILINEAR */
+} vp8hip_trace_gather;
+size_t vp8hip_trace_gather_size(const vp8hip_ctx *ctx, const vp8hip_trace_gather *p);
+int  vp8hip_trace_gather_async(vp8hip_ctx *ctx, const vp8hip_gather_job *jobs, int n, const vp8hip_trace_gather *p,
+                               const void *pool, size_t pool_stride, int pool_frames,
+                               const void *src, size_t src_stride, int src_frames, void *dst, size_t dst_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

@@ -432,6 +432,20 @@ def trace_residual_size(gw, gh, dtype=0):
     return int(load_hip().vp8hip_trace_residual_size(None, ctypes.byref(p)))
 
 
+GATHER_FILTERS = {"nearest": 0, "bilinear": 1}               # VP8HIP_GATHER_NEAREST, BILINEAR
+GATHER_LAYOUTS = {"planar": 0, "channels_last": 1}            # VP8HIP_GATHER_PLANAR, CHANNELS_LAST
+
+
+def trace_gather_size(gw, gh, channels, elem, src_w=1, src_h=1, layout="planar", filter="nearest"):
+    """bytes of one output of Vp8Hip.trace_gather on a grid of gw x gh (vp8hip_trace_gather_size): channels * gh * gw * elem; 0 for a
+    size or a source grid outside 1..16383, channels outside 1..4096, an element size other than 1, 2 or 4, an unknown layout or filter,
+    or "bilinear" on 1-byte elements.  For the display size pass the display size."""
+    if layout not in GATHER_LAYOUTS or filter not in GATHER_FILTERS or gw == 0 or gh == 0:     # (0 x 0 would ask for the display size)
+        return 0
+    p = TraceGatherParams(int(gw), int(gh), int(src_w), int(src_h), int(channels), int(elem), GATHER_LAYOUTS[layout], GATHER_FILTERS[filter])
+    return int(load_hip().vp8hip_trace_gather_size(None, ctypes.byref(p)))
+
+
 RES_LAYOUTS = {"i420": 0, "planar": 1}                        # VP8HIP_RES_I420, PLANAR
 RES_I16, RES_F16, RES_F32 = 0, 1, 2
 
@@ -491,6 +505,15 @@ class AnchorJob(ctypes.Structure):          # vp8hip_anchor_job, include/vp8hip.
 
 class TraceResidualParams(ctypes.Structure):    # vp8hip_trace_residual, include/vp8hip.h
     _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("matrix", c_int), ("order", c_int), ("dtype", c_int), ("scale", ctypes.c_float * 3)]
+
+
+class GatherJob(ctypes.Structure):          # vp8hip_gather_job, include/vp8hip.h
+    _fields_ = [("trace", ctypes.c_int32), ("src", ctypes.c_int32)]
+
+
+class TraceGatherParams(ctypes.Structure):  # vp8hip_trace_gather, include/vp8hip.h
+    _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("src_w", c_int), ("src_h", c_int), ("channels", c_int), ("elem", c_int),
+                ("layout", c_int), ("filter", c_int)]
 
 
 class VisParams(ctypes.Structure):          # vp8hip_vis, include/vp8hip.h
@@ -565,6 +588,10 @@ def load_hip():
         L.vp8hip_trace_residual_size.restype = c_size_t
         L.vp8hip_trace_residual_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(TraceResidualParams), c_void_p, c_size_t, c_int,
                                                   c_void_p, c_size_t]
+        L.vp8hip_trace_gather_size.argtypes = [c_void_p, ctypes.POINTER(TraceGatherParams)]
+        L.vp8hip_trace_gather_size.restype = c_size_t
+        L.vp8hip_trace_gather_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(TraceGatherParams), c_void_p, c_size_t, c_int,
+                                                c_void_p, c_size_t, c_int, c_void_p, c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1078,6 +1105,64 @@ class Vp8Hip:
                               lambda arr_out, stride: self.L.vp8hip_trace_residual_async(
                                   self.h, arr, n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
                               "vp8hip_trace_residual_async")[0]
+
+    def trace_gather(self, pool, jobs, src, width=None, height=None, filter="nearest", out=None):
+        """`src` -- tensors [m, C, sh, sw] a model made of anchor pictures: feature maps of any stride, logits, a label map -- carried
+        to later frames along their traces (vp8hip_trace_gather_async).  `jobs`: a list of (entry, k): the entry of `pool` that
+        holds a frame's trace (frames_trace) and the source tensor src[k]; any order, repeats allowed.  Returns [n, C, gh, gw] of
+        src's type and memory format, at the display size or under each output's centre at width x height: "nearest" the cell
+        under the anchor position the trace names (clamped to the picture), the element's bits, for any type of 1, 2 or 4 bytes;
+        "bilinear" the four cells around it weighted in 1/256 steps, in single precision, torch.float16 / torch.float32 only,
+        within the bound include/vp8hip.h derives.  A contiguous src is read as planar [C][h][w], a channels_last one as
+        [h][w][C]; each tensor dense, stride(0) free; anything else is refused.  A src that is both -- one channel, or a grid of
+        one cell -- is read as planar, unless `out` is given and is channels_last only.  `out`: a tensor of that shape, type and
+        format, each frame dense, stride(0) free, not overlapping src.  Stream ordering: as frames_scaled -- the wait on torch's
+        current stream also covers src, which the model has just produced there."""
+        torch, dev = self._torch_device("trace_gather")
+        jobs = [tuple(int(v) for v in j) for j in jobs]
+        n = len(jobs)
+        if any(len(j) != 2 for j in jobs):
+            raise ValueError("trace_gather: jobs are (entry, source tensor)")
+        if filter not in GATHER_FILTERS:
+            raise ValueError(f"trace_gather: filter {filter!r}")
+        if not (torch.is_tensor(src) and src.dim() == 4 and src.shape[0] >= 1 and src.device == dev):
+            raise ValueError(f"trace_gather: src must be a tensor [m, C, sh, sw] on {dev}")
+        m, C, sh, sw = (int(v) for v in src.shape)
+
+        def planar(t):
+            return t[0].is_contiguous()
+
+        def channels_last(t):
+            return t[0].permute(1, 2, 0).is_contiguous()
+        if not planar(src) and not channels_last(src):
+            raise ValueError("trace_gather: src must be contiguous (planar) or channels_last, each tensor dense")
+        layout = "planar" if planar(src) else "channels_last"
+        if planar(src) and channels_last(src) and torch.is_tensor(out) and out.dim() == 4 and out.shape[0] and not planar(out):
+            layout = "channels_last"
+        is_fmt = planar if layout == "planar" else channels_last
+        es = src.element_size()
+        if es not in (1, 2, 4) or (filter == "bilinear" and src.dtype not in (torch.float16, torch.float32)):
+            raise ValueError(f"trace_gather: {src.dtype} with filter {filter!r} (any type of 1, 2 or 4 bytes; bilinear: float16 / float32)")
+        native, gw, gh = self._grid("trace_gather", width, height, 16)
+        if native:
+            gw, gh = self.width, self.height
+        p = TraceGatherParams(0 if native else gw, 0 if native else gh, sw, sh, C, es, GATHER_LAYOUTS[layout], GATHER_FILTERS[filter])
+        if not self.L.vp8hip_trace_gather_size(self.h, ctypes.byref(p)):
+            raise ValueError(f"trace_gather: grid {gw}x{gh}, source [{C}, {sh}, {sw}]: refused (sizes 1..16383, channels 1..4096)")
+        _, pptr, pstride, entries = self._trace_pool_args("trace_gather", pool)
+        arr = (GatherJob * max(n, 1))(*jobs)
+        if out is None:
+            out = torch.empty((n, C, gh, gw), dtype=src.dtype, device=dev,
+                              memory_format=torch.contiguous_format if layout == "planar" else torch.channels_last)
+        src_stride = (src.stride(0) if m > 1 else C * sh * sw) * es      # (of one tensor torch keeps any stride(0): the dense size)
+
+        def fits(t, dtype, shape, d):
+            return t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.device == d and (shape[0] == 0 or is_fmt(t))
+        return self._to_torch("trace_gather", [("out", out, str(src.dtype).split(".")[-1], (n, C, gh, gw))],
+                              lambda arr_out, stride: self.L.vp8hip_trace_gather_async(
+                                  self.h, arr, n, ctypes.byref(p), pptr, pstride, entries, c_void_p(src.data_ptr()), src_stride, m,
+                                  arr_out, stride),
+                              "vp8hip_trace_gather_async", ok=fits, how=f"{layout}, each frame dense")[0]
 
     def rgb_scratch_bytes(self):
         """device bytes of frames_rgb's scratch (vp8hip_rgb_scratch_bytes): a chunk of scaled frames as packed I420; a cache"""

@@ -178,6 +178,29 @@ struct AnchorLaunch {
     AnchorJob j[ANCHOR_MAX_FRAMES];
 };
 
+// One launch of vp8hip_trace_gather_async (vp8_trace_gather.hip), as the host's plan (vp8hip_trace.hip) left it
+#define GATHER_MAX_JOBS 256       // jobs per launch (kernel arguments: 8 bytes each)
+#define GATHER_PLANAR 0           // VP8HIP_GATHER_PLANAR, _CHANNELS_LAST
+#define GATHER_CHANNELS_LAST 1
+#define GATHER_NEAREST 0          // VP8HIP_GATHER_NEAREST, _BILINEAR
+#define GATHER_BILINEAR 1
+#define GATHER_RUN 256            // CHANNELS_LAST: outputs a workgroup takes, one lane each for the offsets
+struct GatherJob {
+    int trace;                    // the pool entry that holds the trace
+    int src;                      // the source tensor
+};
+struct GatherLaunch {
+    int gw, gh;                   // the output grid
+    int dw, dh;                   // the display size it is laid over: the trace's grid, and what trace values are clamped to
+    int sw, sh;                   // the source tensors' grid
+    int C;                        // channels
+    int S;                        // PLANAR: workgroups that share a job's output rows; CHANNELS_LAST: runs of GATHER_RUN outputs (gridDim.x)
+    int cgroup;                   // PLANAR: channels a workgroup makes (gridDim.z groups of them)
+    int xmode;                    // SIDE_X_DISPLAY (gw is the display width: sx = x) or SIDE_X_ANY
+    int vec;                      // every store of a lane is a whole aligned piece (CHANNELS_LAST: every load too)
+    GatherJob j[GATHER_MAX_JOBS];
+};
+
 #define WAVE 64
 
 // Macroblock tiles of the one-MB-row-per-lane pipeline (vp8_keyframe_simt.hip has the layout): three 128-byte lines per macroblock.

@@ -181,6 +181,7 @@ static inline int vp8hip_frame_form(const vp8hip_ctx *c, int fb)
 // with the error set (its text begins with `who`); vp8hip_check_dst: stride >= size, destination and stride aligned to the
 // element, then vp8hip_check_device_span: device memory of the context's device, the n frames inside one allocation.
 #define VP8HIP_MAX_OUT_SIZE 16383       // the largest width / height of an output
+#define VP8HIP_GATHER_MAX_CHANNELS 4096 // the most channels of a tensor vp8hip_trace_gather_async moves
 int vp8hip_check_fbs(vp8hip_ctx *c, const char *who, const int *fbs, int n);
 int vp8hip_check_slots(vp8hip_ctx *c, const char *who, const int *slots, int n);
 bool vp8hip_out_grid(const vp8hip_ctx *c, int dst_w, int dst_h, int cells, int &gw, int &gh);

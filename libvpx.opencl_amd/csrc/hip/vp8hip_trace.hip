@@ -1,7 +1,8 @@
-// vp8hip_frames_trace_async, vp8hip_trace_flow_async and vp8hip_trace_residual_async (include/vp8hip.h): accumulated motion -- every
-// pixel traced back through the frames it was predicted from to the key frame that started the group -- in a pool in the caller's
-// device memory, a pool entry as a flow tensor, and a frame minus its anchor picture gathered at its trace as a residual tensor.  The
-// plans and the checks are made here, once per call; the kernels are in vp8_trace.hip and vp8_trace_residual.hip.  The trace
+// vp8hip_frames_trace_async, vp8hip_trace_flow_async, vp8hip_trace_residual_async and vp8hip_trace_gather_async (include/vp8hip.h):
+// accumulated motion -- every pixel traced back through the frames it was predicted from to the key frame that started the group -- in
+// a pool in the caller's device memory, a pool entry as a flow tensor, a frame minus its anchor picture gathered at its trace as a
+// residual tensor, and a tensor of the caller's gathered at a trace.  The plans and the checks are made here, once per call; the
+// kernels are in vp8_trace.hip, vp8_trace_residual.hip and vp8_trace_gather.hip.  The trace
 // reads the slots' records and vectors (also on a vp8hip_configure_pooled context) and the pool entries its jobs name; the slots'
 // header bits come with the launch, as of this call: nothing is allocated on the device, copied or synchronised.
 #include "vp8hip_ctx.hip.h"
@@ -19,11 +20,25 @@ extern "C" __global__ void vp8_anchor_i16_kernel(ANCHOR_ARGS);
 extern "C" __global__ void vp8_anchor_f16_kernel(ANCHOR_ARGS);
 extern "C" __global__ void vp8_anchor_f32_kernel(ANCHOR_ARGS);
 
+#define GATHER_ARGS const uint8_t *pool, size_t pool_stride, const uint8_t *src, size_t src_stride, uint8_t *dst, size_t dst_stride, GatherLaunch L
+extern "C" __global__ void vp8_gather_planar_nearest_1_kernel(GATHER_ARGS);
+extern "C" __global__ void vp8_gather_planar_nearest_2_kernel(GATHER_ARGS);
+extern "C" __global__ void vp8_gather_planar_nearest_4_kernel(GATHER_ARGS);
+extern "C" __global__ void vp8_gather_rows_nearest_1_kernel(GATHER_ARGS);
+extern "C" __global__ void vp8_gather_rows_nearest_2_kernel(GATHER_ARGS);
+extern "C" __global__ void vp8_gather_rows_nearest_4_kernel(GATHER_ARGS);
+extern "C" __global__ void vp8_gather_planar_bilinear_2_kernel(GATHER_ARGS);
+extern "C" __global__ void vp8_gather_planar_bilinear_4_kernel(GATHER_ARGS);
+extern "C" __global__ void vp8_gather_rows_bilinear_2_kernel(GATHER_ARGS);
+extern "C" __global__ void vp8_gather_rows_bilinear_4_kernel(GATHER_ARGS);
+
 #define TRACE_GROUP_LDS 32768                   // record dwords and vectors of a group of macroblock rows ...
 #define TRACE_GROUP_ROWS 4                      // ... and at most this many rows
 #define TRACE_MB_LDS 68                         // a macroblock in LDS: the record's first dword, sixteen vectors
 #define FLOW_PART_QUADS 8192                    // groups of four outputs a workgroup of the flow kernel walks
 #define ANCHOR_PART_QUADS 4096                  // ... and of the residual kernel: its loads wait on the trace's, so more waves in flight
+#define GATHER_PART_QUADS 2048                  // ... and of the planar gather kernels, which make GATHER_GROUP_CH channels of each
+#define GATHER_GROUP_CH 8                       // channels a workgroup of the planar gather kernels makes
 
 extern "C" size_t vp8hip_trace_size(const vp8hip_ctx *c) { return c && c->width ? (size_t)4 * c->width * c->height : 0; }
 
@@ -213,6 +228,90 @@ extern "C" int vp8hip_trace_residual_async(vp8hip_ctx *c, const vp8hip_anchor_jo
         hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)c->fb_block, c->fb_stride,
                            (const uint8_t *)c->tile_block, c->tile_frame, (const uint8_t *)pool, pool_stride,
                            (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+// the grids of p on context c; false for what the call refuses on p alone
+static bool gather_grid(const vp8hip_ctx *c, const vp8hip_trace_gather *p, int &gw, int &gh)
+{
+    return p && p->src_w >= 1 && p->src_w <= VP8HIP_MAX_OUT_SIZE && p->src_h >= 1 && p->src_h <= VP8HIP_MAX_OUT_SIZE && p->channels >= 1 &&
+           p->channels <= VP8HIP_GATHER_MAX_CHANNELS && (p->elem == 1 || p->elem == 2 || p->elem == 4) &&
+           (p->layout == VP8HIP_GATHER_PLANAR || p->layout == VP8HIP_GATHER_CHANNELS_LAST) &&
+           (p->filter == VP8HIP_GATHER_NEAREST || (p->filter == VP8HIP_GATHER_BILINEAR && p->elem != 1)) &&
+           trace_out_grid(c, p->dst_w, p->dst_h, gw, gh);
+}
+
+extern "C" size_t vp8hip_trace_gather_size(const vp8hip_ctx *c, const vp8hip_trace_gather *p)
+{
+    int gw, gh;
+    return gather_grid(c, p, gw, gh) ? (size_t)p->channels * gh * gw * (size_t)p->elem : 0;
+}
+
+extern "C" int vp8hip_trace_gather_async(vp8hip_ctx *c, const vp8hip_gather_job *jobs, int n, const vp8hip_trace_gather *p, const void *pool,
+                                         size_t pool_stride, int pool_frames, const void *src, size_t src_stride, int src_frames, void *dst,
+                                         size_t dst_stride)
+{
+    const char *who = "vp8hip_trace_gather_async";
+    if (!c || !jobs || n < 1 || !p || !pool || !src || !dst || !c->width) return fail(c, -2, "%s: bad arguments", who);
+    int gw, gh;
+    if (!gather_grid(c, p, gw, gh))
+        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), source grid %dx%d (1..%d each), %d channels (1..%d), element %d, layout %d, filter %d",
+                    who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE, p->src_w, p->src_h, VP8HIP_MAX_OUT_SIZE, p->channels, VP8HIP_GATHER_MAX_CHANNELS,
+                    p->elem, p->layout, p->filter);
+    if (int rc = trace_check_pool(c, "vp8hip_trace_gather_async (pool)", pool, pool_stride, pool_frames)) return rc;
+    if (src_frames < 1) return fail(c, -2, "%s: %d source tensors", who, src_frames);
+    for (int i = 0; i < n; i++) {
+        if (jobs[i].trace < 0 || jobs[i].trace >= pool_frames) return fail(c, -2, "%s: job %d: trace %d outside the pool", who, i, jobs[i].trace);
+        if (jobs[i].src < 0 || jobs[i].src >= src_frames) return fail(c, -2, "%s: job %d: source tensor %d out of range", who, i, jobs[i].src);
+    }
+    const size_t es = (size_t)p->elem;
+    const size_t ssize = (size_t)p->channels * p->src_h * p->src_w * es, size = (size_t)p->channels * gh * gw * es;
+    if (int rc = vp8hip_check_dst(c, "vp8hip_trace_gather_async (src)", src, src_stride, ssize, es, src_frames)) return rc;
+    if (int rc = vp8hip_check_dst(c, "vp8hip_trace_gather_async (dst)", dst, dst_stride, size, es, n)) return rc;
+    // (the span checks have bounded both products: neither wraps, the ends saturate)
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    const size_t slen = src_stride * (size_t)src_frames, dlen = dst_stride * (size_t)n;
+    const uintptr_t s1 = s0 + slen < s0 ? UINTPTR_MAX : s0 + slen, d1 = d0 + dlen < d0 ? UINTPTR_MAX : d0 + dlen;
+    if (s0 < d1 && d0 < s1) return fail(c, -2, "%s: the source tensors and the destination overlap", who);
+    HIPCHK(c, hipSetDevice(c->device));
+
+    GatherLaunch L;
+    memset(&L, 0, offsetof(GatherLaunch, j));
+    L.gw = gw; L.gh = gh;
+    L.dw = c->width; L.dh = c->height;
+    L.sw = p->src_w; L.sh = p->src_h;
+    L.C = p->channels;
+    L.xmode = gw == c->width ? SIDE_X_DISPLAY : SIDE_X_ANY;
+    unsigned gz = 1;
+    if (p->layout == VP8HIP_GATHER_PLANAR) {
+        const long long quads = (long long)((gw + 3) >> 2) * gh;
+        L.S = (int)((quads + GATHER_PART_QUADS - 1) / GATHER_PART_QUADS);
+        if (L.S > gh) L.S = gh;
+        L.cgroup = GATHER_GROUP_CH;
+        gz = (unsigned)((L.C + L.cgroup - 1) / L.cgroup);
+        const size_t piece = 4 * es;
+        L.vec = gw % 4 == 0 && (uintptr_t)dst % piece == 0 && dst_stride % piece == 0;
+    } else {
+        L.S = (int)(((long long)gw * gh + GATHER_RUN - 1) / GATHER_RUN);
+        L.vec = ((size_t)L.C * es) % 16 == 0 && d0 % 16 == 0 && dst_stride % 16 == 0 && s0 % 16 == 0 && src_stride % 16 == 0;
+    }
+    // by filter, layout and element size (1, 2, 4)
+    void (*const kernels[2][2][3])(GATHER_ARGS) = {
+        {{vp8_gather_planar_nearest_1_kernel, vp8_gather_planar_nearest_2_kernel, vp8_gather_planar_nearest_4_kernel},
+         {vp8_gather_rows_nearest_1_kernel, vp8_gather_rows_nearest_2_kernel, vp8_gather_rows_nearest_4_kernel}},
+        {{nullptr, vp8_gather_planar_bilinear_2_kernel, vp8_gather_planar_bilinear_4_kernel},
+         {nullptr, vp8_gather_rows_bilinear_2_kernel, vp8_gather_rows_bilinear_4_kernel}}};
+    void (*const kernel)(GATHER_ARGS) = kernels[p->filter][p->layout][p->elem >> 1];
+    for (int i0 = 0; i0 < n; i0 += GATHER_MAX_JOBS) {
+        const int m = n - i0 < GATHER_MAX_JOBS ? n - i0 : GATHER_MAX_JOBS;
+        for (int k = 0; k < m; k++) {
+            L.j[k].trace = jobs[i0 + k].trace;
+            L.j[k].src = jobs[i0 + k].src;
+        }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)L.S, (unsigned)m, gz), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
+                           (const uint8_t *)src, src_stride, (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
         HIPCHK(c, hipGetLastError());
     }
     return 0;
