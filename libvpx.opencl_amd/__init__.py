@@ -858,6 +858,19 @@ class Vp8Hip:
             return True, cells * (self.g.aligned_w // 16), cells * (self.g.aligned_h // 16)
         return False, int(width), int(height)
 
+    def _trace_grid(self, who, width, height):
+        """-> (dst_w, dst_h, gw, gh) of a call that reads a trace pool; with no size 0, 0 and the display size, the trace's own grid"""
+        native, gw, gh = self._grid(who, width, height, 16)
+        return (0, 0, self.width, self.height) if native else (gw, gh, gw, gh)
+
+    @staticmethod
+    def _trace_jobs(who, jobs, struct, fields):
+        """-> (the jobs of a call that reads a trace pool, tuples of ints, as an array of `struct`; how many)"""
+        jobs = [tuple(int(v) for v in j) for j in jobs]
+        if any(len(j) != len(struct._fields_) for j in jobs):
+            raise ValueError(f"{who}: jobs are {fields}")
+        return (struct * max(len(jobs), 1))(*jobs), len(jobs)
+
     def _torch_device(self, who):
         """-> (torch, the context's device as torch names it); refuses when torch came after the library"""
         import torch
@@ -1037,9 +1050,7 @@ class Vp8Hip:
         import torch
         idx = [int(i) for i in idx]
         n = len(idx)
-        native, gw, gh = self._grid("trace_flow", width, height, 16)
-        if native:
-            gw, gh = self.width, self.height
+        dst_w, dst_h, gw, gh = self._trace_grid("trace_flow", width, height)
         dtype = torch.int16 if dtype is None else dtype
         dt = _elem_dtype(dtype, _INT16_DTYPES)
         if dt is None:
@@ -1052,7 +1063,7 @@ class Vp8Hip:
             sc = (gw / self.width, gh / self.height)
         else:
             sc = tuple(float(v) for v in scale)
-        p = TraceFlowParams(0 if native else gw, 0 if native else gh, dt)
+        p = TraceFlowParams(dst_w, dst_h, dt)
         p.scale[0], p.scale[1] = np.float32(sc[0]), np.float32(sc[1])
         if not self.L.vp8hip_trace_flow_size(self.h, ctypes.byref(p)):
             raise ValueError(f"trace_flow: grid {gw}x{gh}: refused (sizes 1..16383)")
@@ -1073,13 +1084,8 @@ class Vp8Hip:
         (default 1).  Both frame buffers are read in the form they have; nothing is converted or allocated.  `out`: a tensor of that
         shape and type, each frame dense, stride(0) free.  Stream ordering: as frames_scaled."""
         import torch
-        jobs = [tuple(int(v) for v in j) for j in jobs]
-        n = len(jobs)
-        if any(len(j) != 3 for j in jobs):
-            raise ValueError("trace_residual: jobs are (fb, entry, anchor_fb)")
-        native, gw, gh = self._grid("trace_residual", width, height, 16)
-        if native:
-            gw, gh = self.width, self.height
+        arr, n = self._trace_jobs("trace_residual", jobs, AnchorJob, "(fb, entry, anchor_fb)")
+        dst_w, dst_h, gw, gh = self._trace_grid("trace_residual", width, height)
         dtype = torch.int16 if dtype is None else dtype
         dt = _elem_dtype(dtype, _INT16_DTYPES)
         if dt is None or matrix not in RGB_MATRICES or order not in RGB_ORDERS:
@@ -1094,13 +1100,12 @@ class Vp8Hip:
             sc = tuple(float(v) for v in scale)
             if len(sc) != 3:
                 raise ValueError(f"trace_residual: scale {scale!r}")
-        p = TraceResidualParams(0 if native else gw, 0 if native else gh, RGB_MATRICES[matrix], RGB_ORDERS[order], dt)
+        p = TraceResidualParams(dst_w, dst_h, RGB_MATRICES[matrix], RGB_ORDERS[order], dt)
         for c in range(3):
             p.scale[c] = np.float32(sc[c])
         if not self.L.vp8hip_trace_residual_size(self.h, ctypes.byref(p)):
             raise ValueError(f"trace_residual: grid {gw}x{gh}: refused (sizes 1..16383)")
         _, pptr, pstride, entries = self._trace_pool_args("trace_residual", pool)
-        arr = (AnchorJob * max(n, 1))(*jobs)
         return self._to_torch("trace_residual", [("out", out, _INT16_DTYPES[dt], (n, 3, gh, gw))],
                               lambda arr_out, stride: self.L.vp8hip_trace_residual_async(
                                   self.h, arr, n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
@@ -1119,10 +1124,7 @@ class Vp8Hip:
         format, each frame dense, stride(0) free, not overlapping src.  Stream ordering: as frames_scaled -- the wait on torch's
         current stream also covers src, which the model has just produced there."""
         torch, dev = self._torch_device("trace_gather")
-        jobs = [tuple(int(v) for v in j) for j in jobs]
-        n = len(jobs)
-        if any(len(j) != 2 for j in jobs):
-            raise ValueError("trace_gather: jobs are (entry, source tensor)")
+        arr, n = self._trace_jobs("trace_gather", jobs, GatherJob, "(entry, source tensor)")
         if filter not in GATHER_FILTERS:
             raise ValueError(f"trace_gather: filter {filter!r}")
         if not (torch.is_tensor(src) and src.dim() == 4 and src.shape[0] >= 1 and src.device == dev):
@@ -1143,14 +1145,11 @@ class Vp8Hip:
         es = src.element_size()
         if es not in (1, 2, 4) or (filter == "bilinear" and src.dtype not in (torch.float16, torch.float32)):
             raise ValueError(f"trace_gather: {src.dtype} with filter {filter!r} (any type of 1, 2 or 4 bytes; bilinear: float16 / float32)")
-        native, gw, gh = self._grid("trace_gather", width, height, 16)
-        if native:
-            gw, gh = self.width, self.height
-        p = TraceGatherParams(0 if native else gw, 0 if native else gh, sw, sh, C, es, GATHER_LAYOUTS[layout], GATHER_FILTERS[filter])
+        dst_w, dst_h, gw, gh = self._trace_grid("trace_gather", width, height)
+        p = TraceGatherParams(dst_w, dst_h, sw, sh, C, es, GATHER_LAYOUTS[layout], GATHER_FILTERS[filter])
         if not self.L.vp8hip_trace_gather_size(self.h, ctypes.byref(p)):
             raise ValueError(f"trace_gather: grid {gw}x{gh}, source [{C}, {sh}, {sw}]: refused (sizes 1..16383, channels 1..4096)")
         _, pptr, pstride, entries = self._trace_pool_args("trace_gather", pool)
-        arr = (GatherJob * max(n, 1))(*jobs)
         if out is None:
             out = torch.empty((n, C, gh, gw), dtype=src.dtype, device=dev,
                               memory_format=torch.contiguous_format if layout == "planar" else torch.channels_last)

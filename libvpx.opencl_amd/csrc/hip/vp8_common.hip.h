@@ -144,14 +144,19 @@ struct TraceLaunch {
     TraceJob j[TRACE_MAX_FRAMES];
 };
 
+// What the readers of a trace pool share of a launch (vp8_trace_read.hip.h), as the host's plan (vp8hip_trace.hip: trace_grid) left it
+struct TraceGrid {
+    int gw, gh;                   // the output grid
+    int S;                        // workgroups that share a frame's or job's output rows (gridDim.x)
+    int dw, dh;                   // the display size it is laid over: the trace's grid, and what trace values are clamped to
+    int vec;                      // every store of a lane is a whole aligned piece
+    int xmode;                    // SIDE_X_DISPLAY (gw is the display width: sx = x) or SIDE_X_ANY
+};
+
 // One launch of vp8hip_trace_flow_async (vp8_trace.hip)
 #define FLOW_MAX_FRAMES 512       // pool entries per launch (kernel arguments)
 struct FlowLaunch {
-    int gw, gh;                   // the output grid
-    int dw, dh;                   // the display size it is laid over: the trace's grid
-    int S;                        // workgroups that share a frame's output rows (gridDim.x)
-    int xmode;                    // SIDE_X_DISPLAY (gw is the display width: sx = x) or SIDE_X_ANY
-    int vec;                      // every store of a lane is a whole aligned piece
+    TraceGrid g;
     float scale[2];               // x, y; float types
     int idx[FLOW_MAX_FRAMES];     // pool entry of frame k of the launch
 };
@@ -164,11 +169,7 @@ struct AnchorJob {
     int anchor;                   // the anchor picture: frame buffer << 2 | form
 };
 struct AnchorLaunch {
-    int gw, gh;                   // the output grid
-    int dw, dh;                   // the display size it is laid over: the trace's grid, and what trace values are clamped to
-    int S;                        // workgroups that share a job's output rows (gridDim.x)
-    int xmode;                    // SIDE_X_DISPLAY (gw is the display width: sx = x) or SIDE_X_ANY
-    int vec;                      // every store of a lane is a whole aligned piece
+    TraceGrid g;
     int mb_cols;
     int aw, ah;                   // the aligned area of the luma plane (chroma: half of it)
     int y_off, u_off, v_off, y_stride, uv_stride;    // the raster form: the planes' origins in a frame buffer and their strides
@@ -190,14 +191,10 @@ struct GatherJob {
     int src;                      // the source tensor
 };
 struct GatherLaunch {
-    int gw, gh;                   // the output grid
-    int dw, dh;                   // the display size it is laid over: the trace's grid, and what trace values are clamped to
+    TraceGrid g;                  // CHANNELS_LAST: S = runs of GATHER_RUN outputs (gridDim.x), vec = every store AND load is a whole piece
     int sw, sh;                   // the source tensors' grid
     int C;                        // channels
-    int S;                        // PLANAR: workgroups that share a job's output rows; CHANNELS_LAST: runs of GATHER_RUN outputs (gridDim.x)
     int cgroup;                   // PLANAR: channels a workgroup makes (gridDim.z groups of them)
-    int xmode;                    // SIDE_X_DISPLAY (gw is the display width: sx = x) or SIDE_X_ANY
-    int vec;                      // every store of a lane is a whole aligned piece (CHANNELS_LAST: every load too)
     GatherJob j[GATHER_MAX_JOBS];
 };
 

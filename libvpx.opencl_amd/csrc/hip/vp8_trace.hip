@@ -15,22 +15,8 @@
 // vp8_flow_*_kernel.  A pool entry as a tensor [2][gh][gw]: output (y, x) takes trace pixel (sy, sx) by the centre map and holds
 // T.x - sx, T.y - sy, converted as the side tensors are.
 // Integer and conversion arithmetic only; trace values are data and never become addresses.
-#include "vp8_tensor_out.hip.h"
+#include "vp8_trace_read.hip.h"
 #include "vp8hip.h"
-
-// Four neighbouring dwords at a dword-aligned address: one global_load_dwordx4 (gfx950 under HSA takes it at any dword; the
-// compiler emits it for a vector type of alignment 4), or with -DTRACE_GATHER_DWORDS four global_load_dword -- the variant
-// DESIGN 4.13's measurement compares it with.
-#ifdef TRACE_GATHER_DWORDS
-__device__ __forceinline__ u32x4_t load4_dword_aligned(const GLOBAL_AS unsigned *p)
-{
-    const volatile GLOBAL_AS unsigned *q = p;
-    return u32x4_t{q[0], q[1], q[2], q[3]};
-}
-#else
-typedef u32x4_t u32x4_dword_t __attribute__((aligned(4)));
-__device__ __forceinline__ u32x4_t load4_dword_aligned(const GLOBAL_AS unsigned *p) { return *(const GLOBAL_AS u32x4_dword_t *)p; }
-#endif
 
 // grid: x = the groups of macroblock rows of a frame, y = the jobs of the launch.  slot_base: IR slot 0, slot_bytes apart, records
 // at o_mbx and vectors at o_mvs inside; pool: entry 0, pool_stride apart.
@@ -99,9 +85,9 @@ __device__ __forceinline__ void flow_body(const uint8_t *__restrict__ pool, size
     typedef typename TensorElem<DTYPE>::T elem_t;
     constexpr int ES = (int)sizeof(elem_t);
     const int f = (int)blockIdx.y;
-    const int gw = L.gw, gh = L.gh, dw = L.dw;
+    const int gw = L.g.gw, gh = L.g.gh;
     int y0, y1;
-    tensor_share(0, gh, L.S, (int)blockIdx.x, y0, y1);
+    tensor_share(0, gh, L.g.S, (int)blockIdx.x, y0, y1);
     const uint8_t *src = pool + pool_stride * (size_t)L.idx[f];
     uint8_t *D = dst + dst_stride * f;
     const size_t plane = (size_t)gh * gw;
@@ -109,34 +95,18 @@ __device__ __forceinline__ void flow_body(const uint8_t *__restrict__ pool, size
 #pragma unroll 1
     for (TensorWalk t((gw + 3) >> 2); t.row < nrows; t.next()) {
         const int y = y0 + t.row, x = t.col << 2;
-        const int sy = tensor_src(y, gh, L.dh);
-        const GLOBAL_AS unsigned *row = (const GLOBAL_AS unsigned *)src + (size_t)sy * dw;
-        int sx[4];
-        unsigned T[4];
-        if (L.xmode == SIDE_X_DISPLAY && x + 3 < gw) {
-            const u32x4_t g = load4_dword_aligned(row + x);
-            T[0] = g.x; T[1] = g.y; T[2] = g.z; T[3] = g.w;
-#pragma unroll
-            for (int i = 0; i < 4; i++) sx[i] = x + i;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int xi = min(x + i, gw - 1);
-                sx[i] = L.xmode == SIDE_X_DISPLAY ? xi : tensor_src(xi, gw, dw);
-                T[i] = row[sx[i]];
-            }
-        }
+        const TraceQuad q = trace_read4(src, L.g, y, x);
         const size_t pix = (size_t)y * gw + x;
 #pragma unroll
         for (int ch = 0; ch < 2; ch++) {
             unsigned e[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const int a = ch == 0 ? (int)(short)(T[i] & 0xffffu) - sx[i] : ((int)T[i] >> 16) - sy;
+                const int a = ch == 0 ? trace_x(q.T[i]) - q.sx[i] : trace_y(q.T[i]) - q.sy;
                 e[i] = tensor_value<DTYPE>(a, L.scale[ch]);
             }
             uint8_t *o = D + ((size_t)ch * plane + pix) * ES;
-            if (L.vec) tensor_store4<ES>(o, e);
+            if (L.g.vec) tensor_store4<ES>(o, e);
             else {
 #pragma unroll
                 for (int i = 0; i < 4; i++)
@@ -146,7 +116,7 @@ __device__ __forceinline__ void flow_body(const uint8_t *__restrict__ pool, size
     }
 }
 
-// grid: x = the workgroups that share a frame's output rows (L.S), y = the frames of the launch.  pool: entry 0; dst: the launch's
+// grid: x = the workgroups that share a frame's output rows (L.g.S), y = the frames of the launch.  pool: entry 0; dst: the launch's
 // first frame.
 #define FLOW_KERNEL(NAME, DTYPE)                                                                                                          \
     extern "C" __global__ void __launch_bounds__(256)                                                                                     \

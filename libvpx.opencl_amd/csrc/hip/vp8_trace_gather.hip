@@ -19,13 +19,10 @@
 // consecutive bytes of the destination, each piece read from the row its output gathers (BILINEAR: from the four rows).  Tensors that
 // do not take whole pieces are walked as (output, element) pairs the same way.
 //
-// THE CLAMP.  A trace value becomes an address here, as in vp8_trace_residual.hip: every value is clamped to the picture before
-// anything is formed from it (gather_tap), and the maps below take a position inside the picture to a cell inside the source grid.
-// So a pool entry nobody wrote yields garbage values and never a read outside the job's source tensor.
+// THE CLAMP (vp8_trace_read.hip.h).  A trace value becomes an address here: gather_cell takes every one through trace_clamp, and the
+// maps below take a position inside the picture to a cell inside the source grid, so no read falls outside the job's source tensor.
 // Single precision only; no doubles, no atomics; offsets in size_t (C * gh * gw passes 2^32).
-#include "vp8_tensor_out.hip.h"
-
-typedef u32x4_t u32x4_dword_t __attribute__((aligned(4)));
+#include "vp8_trace_read.hip.h"
 
 #ifndef GATHER_UNROLL_NEAREST
 #define GATHER_UNROLL_NEAREST 4    // PLANAR: channels whose loads are in flight together: 16 loads a lane ...
@@ -61,18 +58,17 @@ __device__ __forceinline__ int gather_pos256(int a, int s, int d)
     return min(max(p, 0), (s - 1) * 256);
 }
 
-// trace dword -> the offset of its first cell, and for BILINEAR the steps dx (0 / 1) and dy (0 / sw) to the other three and wx, wy.
-// Nothing of t that was not clamped here becomes an address.
+// trace dword -> the offset of its first cell, and for BILINEAR the steps dx (0 / 1) and dy (0 / sw) to the other three and wx, wy
 template <int FILTER>
 __device__ __forceinline__ int gather_cell(unsigned t, const GatherLaunch &L, int &dx, int &dy, int &wx, int &wy)
 {
-    const int ax = min(max((int)(short)(t & 0xffffu), 0), L.dw - 1);
-    const int ay = min(max((int)t >> 16, 0), L.dh - 1);
+    int ax, ay;
+    trace_clamp(t, L.g.dw, L.g.dh, ax, ay);
     if constexpr (FILTER == GATHER_NEAREST) {
         dx = dy = wx = wy = 0;
-        return tensor_src(ay, L.dh, L.sh) * L.sw + tensor_src(ax, L.dw, L.sw);        // the cell under the pixel's centre
+        return tensor_src(ay, L.g.dh, L.sh) * L.sw + tensor_src(ax, L.g.dw, L.sw);    // the cell under the pixel's centre
     } else {
-        const int px = gather_pos256(ax, L.sw, L.dw), py = gather_pos256(ay, L.sh, L.dh);
+        const int px = gather_pos256(ax, L.sw, L.g.dw), py = gather_pos256(ay, L.sh, L.g.dh);
         const int x0 = px >> 8, y0 = py >> 8;
         wx = px & 255; wy = py & 255;
         dx = x0 + 1 < L.sw;
@@ -160,9 +156,9 @@ __device__ __forceinline__ void gather_planar(const uint8_t *__restrict__ pool, 
     constexpr int UN = FILTER == GATHER_NEAREST ? GATHER_UNROLL_NEAREST : GATHER_UNROLL_BILINEAR;
     const int f = (int)blockIdx.y;
     const GatherJob J = L.j[f];
-    const int gw = L.gw, gh = L.gh, dw = L.dw;
+    const int gw = L.g.gw, gh = L.g.gh;
     int y0, y1;
-    tensor_share(0, gh, L.S, (int)blockIdx.x, y0, y1);
+    tensor_share(0, gh, L.g.S, (int)blockIdx.x, y0, y1);
     const int c0 = (int)blockIdx.z * L.cgroup, c1 = min(L.C, c0 + L.cgroup);
     const uint8_t *trace = pool + pool_stride * (size_t)J.trace;
     const GLOBAL_AS elem_t *sp = (const GLOBAL_AS elem_t *)(src + src_stride * (size_t)J.src);
@@ -172,28 +168,16 @@ __device__ __forceinline__ void gather_planar(const uint8_t *__restrict__ pool, 
 #pragma unroll 1
     for (TensorWalk t((gw + 3) >> 2); t.row < nrows; t.next()) {
         const int y = y0 + t.row, x = t.col << 2;
-        const int sy = tensor_src(y, gh, L.dh);
-        const GLOBAL_AS unsigned *row = (const GLOBAL_AS unsigned *)trace + (size_t)sy * dw;
-        unsigned T[4];
-        if (L.xmode == SIDE_X_DISPLAY && x + 3 < gw) {
-            const u32x4_t g = *(const GLOBAL_AS u32x4_dword_t *)(row + x);
-            T[0] = g.x; T[1] = g.y; T[2] = g.z; T[3] = g.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int xi = min(x + i, gw - 1);
-                T[i] = row[L.xmode == SIDE_X_DISPLAY ? xi : tensor_src(xi, gw, dw)];
-            }
-        }
+        const TraceQuad q = trace_read4(trace, L.g, y, x);
         GatherTap<FILTER> tap[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) gather_tap<FILTER>(T[i], L, tap[i]);
+        for (int i = 0; i < 4; i++) gather_tap<FILTER>(q.T[i], L, tap[i]);
         const size_t pix = (size_t)y * gw + x;
         int c = c0;
 #pragma unroll 1
-        for (; c + UN <= c1; c += UN) gather_planar_channels<ES, FILTER, UN>(sp, splane, D, gplane, pix, c, tap, x, gw, L.vec);
+        for (; c + UN <= c1; c += UN) gather_planar_channels<ES, FILTER, UN>(sp, splane, D, gplane, pix, c, tap, x, gw, L.g.vec);
 #pragma unroll 1
-        for (; c < c1; c++) gather_planar_channels<ES, FILTER, 1>(sp, splane, D, gplane, pix, c, tap, x, gw, L.vec);
+        for (; c < c1; c++) gather_planar_channels<ES, FILTER, 1>(sp, splane, D, gplane, pix, c, tap, x, gw, L.g.vec);
     }
 }
 
@@ -234,13 +218,13 @@ __device__ __forceinline__ void gather_rows(const uint8_t *__restrict__ pool, si
     __shared__ unsigned s_w[FILTER == GATHER_BILINEAR ? GATHER_RUN : 1];
     const int f = (int)blockIdx.y;
     const GatherJob J = L.j[f];
-    const int gw = L.gw, total = L.gh * gw;                  // (below 2^28)
+    const int gw = L.g.gw, total = L.g.gh * gw;              // (below 2^28)
     const int first = (int)blockIdx.x * GATHER_RUN, tid = (int)threadIdx.x;
     const int nout = min(GATHER_RUN, total - first);
     if (tid < nout) {
         const int o = first + tid, y = o / gw, x = o - y * gw;
-        const int sy = tensor_src(y, L.gh, L.dh), sx = L.xmode == SIDE_X_DISPLAY ? x : tensor_src(x, gw, L.dw);
-        const unsigned t = ((const GLOBAL_AS unsigned *)(pool + pool_stride * (size_t)J.trace))[(size_t)sy * L.dw + sx];
+        const int sy = tensor_src(y, L.g.gh, L.g.dh), sx = trace_col(L.g, x);
+        const unsigned t = ((const GLOBAL_AS unsigned *)(pool + pool_stride * (size_t)J.trace))[(size_t)sy * L.g.dw + sx];
         int dx, dy, wx, wy;
         s_o[tid] = (unsigned)gather_cell<FILTER>(t, L, dx, dy, wx, wy);
         if constexpr (FILTER == GATHER_BILINEAR) s_w[tid] = (unsigned)wx | (unsigned)wy << 8 | (unsigned)dx << 16 | (dy ? 1u << 17 : 0u);
@@ -249,7 +233,7 @@ __device__ __forceinline__ void gather_rows(const uint8_t *__restrict__ pool, si
     const size_t rowb = (size_t)L.C * ES;                    // an output's bytes, a cell's bytes
     const uint8_t *S = src + src_stride * (size_t)J.src;
     uint8_t *D = dst + dst_stride * (size_t)f + (size_t)first * rowb;
-    if (L.vec) {
+    if (L.g.vec) {
         // (output, 16-byte piece): UN pairs a lane in flight
         constexpr int UN = FILTER == GATHER_NEAREST ? 4 : 2;
         constexpr int TAPS = FILTER == GATHER_NEAREST ? 1 : 4;
@@ -297,7 +281,7 @@ __device__ __forceinline__ void gather_rows(const uint8_t *__restrict__ pool, si
     }
 }
 
-// PLANAR: grid x = the workgroups that share a job's output rows (L.S), y = the jobs of the launch, z = the groups of channels.
+// PLANAR: grid x = the workgroups that share a job's output rows (L.g.S), y = the jobs of the launch, z = the groups of channels.
 // CHANNELS_LAST: grid x = the runs of GATHER_RUN outputs, y = the jobs.  pool: entry 0; src: source tensor 0; dst: the launch's first output.
 #define GATHER_KERNEL(NAME, ES, LAYOUT, FILTER)                                                                                           \
     extern "C" __global__ void __launch_bounds__(256)                                                                                     \

@@ -12,13 +12,10 @@
 // straddle two tiles) and its chroma the same per plane.  Anything else goes byte by byte, by coordinate.
 // Stores as in vp8_trace.hip: whole pieces where the tensor allows, else element by element.
 //
-// THE CLAMP.  Here, unlike in vp8_trace.hip, a trace value becomes an address.  Every value is clamped to the picture (anchor_pos)
-// before any address is formed from it, so a pool entry nobody wrote yields garbage values and never a read outside the anchor's
-// picture; ScaleSrc clamps to the aligned area once more.  Integer and conversion arithmetic only; no LDS.
+// THE CLAMP (vp8_trace_read.hip.h).  Here a trace value becomes an address: anchor_pos takes every one through trace_clamp, so no read
+// falls outside the anchor's picture; ScaleSrc clamps to the aligned area once more.  Integer and conversion arithmetic only; no LDS.
 #include "vp8_scale_src.hip.h"
-#include "vp8_tensor_out.hip.h"
-
-typedef u32x4_t u32x4_dword_t __attribute__((aligned(4)));
+#include "vp8_trace_read.hip.h"
 
 // a frame buffer by coordinate in the form the job names (wave-uniform): plane 0 luma, 1 U, 2 V.  A frame buffer never written reads
 // as zeros and no address is formed.
@@ -63,12 +60,8 @@ __device__ __forceinline__ unsigned anchor_read(const AnchorFrame &F, const Anch
     return 0u;
 }
 
-// the position a trace dword names, clamped to the picture: nothing that was not clamped here becomes an address
-__device__ __forceinline__ void anchor_pos(unsigned t, const AnchorLaunch &L, int &ax, int &ay)
-{
-    ax = min(max((int)(short)(t & 0xffffu), 0), L.dw - 1);
-    ay = min(max((int)t >> 16, 0), L.dh - 1);
-}
+// the position of the anchor a trace dword names
+__device__ __forceinline__ void anchor_pos(unsigned t, const AnchorLaunch &L, int &ax, int &ay) { trace_clamp(t, L.g.dw, L.g.dh, ax, ay); }
 
 // vp8_rgb.hip's conversion: the bytes at positions 0..2 of a pixel (the coefficients come by position, vp8hip_rgb_coeffs)
 __device__ __forceinline__ void anchor_rgb(const AnchorLaunch &L, int Y, int U, int V, int (&c)[3])
@@ -88,9 +81,9 @@ __device__ __forceinline__ void anchor_body(const uint8_t *__restrict__ raster, 
     constexpr int ES = (int)sizeof(elem_t);
     const int f = (int)blockIdx.y;
     const AnchorJob J = L.j[f];
-    const int gw = L.gw, gh = L.gh, dw = L.dw;
+    const int gw = L.g.gw, gh = L.g.gh;
     int y0, y1;
-    tensor_share(0, gh, L.S, (int)blockIdx.x, y0, y1);
+    tensor_share(0, gh, L.g.S, (int)blockIdx.x, y0, y1);
     const AnchorFrame C{raster + fb_stride * (size_t)(J.fb >> 2), tiles + tile_frame * (size_t)(J.fb >> 2), J.fb & 3};
     const AnchorFrame A{raster + fb_stride * (size_t)(J.anchor >> 2), tiles + tile_frame * (size_t)(J.anchor >> 2), J.anchor & 3};
     const uint8_t *src = pool + pool_stride * (size_t)J.trace;
@@ -100,14 +93,15 @@ __device__ __forceinline__ void anchor_body(const uint8_t *__restrict__ raster, 
 #pragma unroll 1
     for (TensorWalk t((gw + 3) >> 2); t.row < nrows; t.next()) {
         const int y = y0 + t.row, x = t.col << 2;
-        const int sy = tensor_src(y, gh, L.dh);
-        const GLOBAL_AS unsigned *row = (const GLOBAL_AS unsigned *)src + (size_t)sy * dw;
+        // trace_read4's two paths, written out: the frame is read between the trace's loads, differently on each
+        const int sy = tensor_src(y, gh, L.g.dh);
+        const GLOBAL_AS unsigned *row = (const GLOBAL_AS unsigned *)src + (size_t)sy * L.g.dw;
         unsigned T[4];
         int cur[4][3], anc[4][3];
         int ax[4], ay[4];
-        if (L.xmode == SIDE_X_DISPLAY && x + 3 < gw) {
+        if (trace_whole(L.g, x)) {
             // the display size (sy = y, sx = x + i): four trace dwords, the luma dword, two chroma bytes a plane, a chroma term per pair
-            const u32x4_t g = *(const GLOBAL_AS u32x4_dword_t *)(row + x);
+            const u32x4_t g = load4_dword_aligned(row + x);
             T[0] = g.x; T[1] = g.y; T[2] = g.z; T[3] = g.w;
             const unsigned yw = anchor_read<0, 4>(C, L, x, sy);
             const unsigned ub = anchor_read<1, 2>(C, L, x >> 1, sy >> 1), vb = anchor_read<2, 2>(C, L, x >> 1, sy >> 1);
@@ -119,8 +113,7 @@ __device__ __forceinline__ void anchor_body(const uint8_t *__restrict__ raster, 
         } else {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const int xi = min(x + i, gw - 1);
-                const int sx = L.xmode == SIDE_X_DISPLAY ? xi : tensor_src(xi, gw, dw);
+                const int sx = trace_col(L.g, min(x + i, gw - 1));
                 T[i] = row[sx];
                 anchor_rgb(L, (int)anchor_read<0, 0>(C, L, sx, sy), (int)anchor_read<1, 0>(C, L, sx >> 1, sy >> 1),
                            (int)anchor_read<2, 0>(C, L, sx >> 1, sy >> 1), cur[i]);
@@ -151,7 +144,7 @@ __device__ __forceinline__ void anchor_body(const uint8_t *__restrict__ raster, 
             unsigned e[4];
             tensor_values4<DTYPE>(a, L.scale[p], e);
             uint8_t *o = D + ((size_t)p * plane + pix) * ES;
-            if (L.vec) tensor_store4<ES>(o, e);
+            if (L.g.vec) tensor_store4<ES>(o, e);
             else {
 #pragma unroll
                 for (int i = 0; i < 4; i++)
@@ -161,7 +154,7 @@ __device__ __forceinline__ void anchor_body(const uint8_t *__restrict__ raster, 
     }
 }
 
-// grid: x = the workgroups that share a job's output rows (L.S), y = the jobs of the launch.  raster / tiles: frame buffer 0 in its two
+// grid: x = the workgroups that share a job's output rows (L.g.S), y = the jobs of the launch.  raster / tiles: frame buffer 0 in its two
 // forms (vp8_scale_kernel's); pool: entry 0; dst: the launch's first frame.
 #define ANCHOR_KERNEL(NAME, DTYPE)                                                                                                        \
     extern "C" __global__ void __launch_bounds__(256)                                                                                     \

@@ -6,8 +6,9 @@
 //   vp8hip_visualize.hip vp8hip_visualize
 //   vp8hip_scale.hip, vp8hip_rgb.hip, vp8hip_side.hip, vp8hip_residual.hip   vp8hip_frames_scale_async, _rgb_async, _side_async,
 //                       _residual_async: frames, and what the slots hold beside them, as tensors in the caller's device memory
-//   vp8hip_trace.hip    vp8hip_frames_trace_async, vp8hip_trace_flow_async, vp8hip_trace_residual_async: accumulated motion in a
-//                       pool in the caller's device memory, and what reads it
+//   vp8hip_trace.hip    vp8hip_frames_trace_async: accumulated motion in a pool in the caller's device memory (vp8_trace.hip), and
+//                       the pool's readers vp8hip_trace_flow_async (vp8_trace.hip), vp8hip_trace_residual_async
+//                       (vp8_trace_residual.hip) and vp8hip_trace_gather_async (vp8_trace_gather.hip)
 //   vp8hip_handover.hip the checks those calls share
 #pragma once
 #include <hip/hip_runtime.h>

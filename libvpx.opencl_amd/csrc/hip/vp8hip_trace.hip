@@ -43,6 +43,7 @@ extern "C" __global__ void vp8_gather_rows_bilinear_4_kernel(GATHER_ARGS);
 extern "C" size_t vp8hip_trace_size(const vp8hip_ctx *c) { return c && c->width ? (size_t)4 * c->width * c->height : 0; }
 
 // the pool: pool_frames entries of the context's trace size, pool_stride apart, dword-aligned, inside one allocation of the device
+// (that the entries a call names lie inside it is the call's to check: they sit in different structs and the texts differ)
 static int trace_check_pool(vp8hip_ctx *c, const char *who, const void *pool, size_t pool_stride, int pool_frames)
 {
     if (pool_frames < 1) return fail(c, -2, "%s: a pool of %d traces", who, pool_frames);
@@ -115,6 +116,21 @@ static bool trace_out_grid(const vp8hip_ctx *c, int dst_w, int dst_h, int &gw, i
     return vp8hip_out_grid(c, dst_w, dst_h, 16, gw, gh);
 }
 
+// What the three readers' plans share: the grid gw x gh laid over the display size and shared by workgroups of part_quads groups of
+// four outputs each, and whether the tensors at dst, dst_stride apart, of elements of es bytes take every group as one aligned piece
+static TraceGrid trace_grid(const vp8hip_ctx *c, int gw, int gh, size_t es, int part_quads, const void *dst, size_t dst_stride)
+{
+    TraceGrid G;
+    G.gw = gw; G.gh = gh; G.dw = c->width; G.dh = c->height;
+    const long long quads = (long long)((gw + 3) >> 2) * gh;
+    G.S = (int)((quads + part_quads - 1) / part_quads);
+    if (G.S > gh) G.S = gh;
+    G.xmode = gw == c->width ? SIDE_X_DISPLAY : SIDE_X_ANY;
+    const size_t piece = 4 * es;
+    G.vec = gw % 4 == 0 && (uintptr_t)dst % piece == 0 && dst_stride % piece == 0;
+    return G;
+}
+
 // the grid of p on context c; false for what the call refuses on p alone
 static bool flow_grid(const vp8hip_ctx *c, const vp8hip_trace_flow *p, int &gw, int &gh)
 {
@@ -145,20 +161,13 @@ extern "C" int vp8hip_trace_flow_async(vp8hip_ctx *c, const int *idx, int n, con
 
     FlowLaunch L;
     memset(&L, 0, offsetof(FlowLaunch, idx));
-    L.gw = gw; L.gh = gh;
-    L.dw = c->width; L.dh = c->height;
-    const long long quads = (long long)((gw + 3) >> 2) * gh;
-    L.S = (int)((quads + FLOW_PART_QUADS - 1) / FLOW_PART_QUADS);
-    if (L.S > gh) L.S = gh;
-    L.xmode = gw == c->width ? SIDE_X_DISPLAY : SIDE_X_ANY;
-    const size_t piece = 4 * es;
-    L.vec = gw % 4 == 0 && (uintptr_t)dst % piece == 0 && dst_stride % piece == 0;
+    L.g = trace_grid(c, gw, gh, es, FLOW_PART_QUADS, dst, dst_stride);
     L.scale[0] = p->scale[0]; L.scale[1] = p->scale[1];
     void (*const kernels[3])(FLOW_ARGS) = {vp8_flow_i16_kernel, vp8_flow_f16_kernel, vp8_flow_f32_kernel};
     for (int i0 = 0; i0 < n; i0 += FLOW_MAX_FRAMES) {
         const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
         memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
-        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
+        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.g.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
                            (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
         HIPCHK(c, hipGetLastError());
     }
@@ -201,14 +210,7 @@ extern "C" int vp8hip_trace_residual_async(vp8hip_ctx *c, const vp8hip_anchor_jo
 
     AnchorLaunch L;
     memset(&L, 0, offsetof(AnchorLaunch, j));
-    L.gw = gw; L.gh = gh;
-    L.dw = c->width; L.dh = c->height;
-    const long long quads = (long long)((gw + 3) >> 2) * gh;
-    L.S = (int)((quads + ANCHOR_PART_QUADS - 1) / ANCHOR_PART_QUADS);
-    if (L.S > gh) L.S = gh;
-    L.xmode = gw == c->width ? SIDE_X_DISPLAY : SIDE_X_ANY;
-    const size_t piece = 4 * es;
-    L.vec = gw % 4 == 0 && (uintptr_t)dst % piece == 0 && dst_stride % piece == 0;
+    L.g = trace_grid(c, gw, gh, es, ANCHOR_PART_QUADS, dst, dst_stride);
     L.mb_cols = c->dg.mb_cols;
     L.aw = c->dg.aligned_w; L.ah = c->dg.aligned_h;
     L.y_off = c->dg.y_off; L.u_off = c->dg.u_off; L.v_off = c->dg.v_off;
@@ -225,7 +227,7 @@ extern "C" int vp8hip_trace_residual_async(vp8hip_ctx *c, const vp8hip_anchor_jo
             L.j[k].trace = job.trace;
             L.j[k].anchor = job.anchor_fb << 2 | vp8hip_frame_form(c, job.anchor_fb);
         }
-        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)c->fb_block, c->fb_stride,
+        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.g.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)c->fb_block, c->fb_stride,
                            (const uint8_t *)c->tile_block, c->tile_frame, (const uint8_t *)pool, pool_stride,
                            (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
         HIPCHK(c, hipGetLastError());
@@ -279,23 +281,16 @@ extern "C" int vp8hip_trace_gather_async(vp8hip_ctx *c, const vp8hip_gather_job 
 
     GatherLaunch L;
     memset(&L, 0, offsetof(GatherLaunch, j));
-    L.gw = gw; L.gh = gh;
-    L.dw = c->width; L.dh = c->height;
+    L.g = trace_grid(c, gw, gh, es, GATHER_PART_QUADS, dst, dst_stride);
     L.sw = p->src_w; L.sh = p->src_h;
     L.C = p->channels;
-    L.xmode = gw == c->width ? SIDE_X_DISPLAY : SIDE_X_ANY;
     unsigned gz = 1;
     if (p->layout == VP8HIP_GATHER_PLANAR) {
-        const long long quads = (long long)((gw + 3) >> 2) * gh;
-        L.S = (int)((quads + GATHER_PART_QUADS - 1) / GATHER_PART_QUADS);
-        if (L.S > gh) L.S = gh;
         L.cgroup = GATHER_GROUP_CH;
         gz = (unsigned)((L.C + L.cgroup - 1) / L.cgroup);
-        const size_t piece = 4 * es;
-        L.vec = gw % 4 == 0 && (uintptr_t)dst % piece == 0 && dst_stride % piece == 0;
     } else {
-        L.S = (int)(((long long)gw * gh + GATHER_RUN - 1) / GATHER_RUN);
-        L.vec = ((size_t)L.C * es) % 16 == 0 && d0 % 16 == 0 && dst_stride % 16 == 0 && s0 % 16 == 0 && src_stride % 16 == 0;
+        L.g.S = (int)(((long long)gw * gh + GATHER_RUN - 1) / GATHER_RUN);
+        L.g.vec = ((size_t)L.C * es) % 16 == 0 && d0 % 16 == 0 && dst_stride % 16 == 0 && s0 % 16 == 0 && src_stride % 16 == 0;
     }
     // by filter, layout and element size (1, 2, 4)
     void (*const kernels[2][2][3])(GATHER_ARGS) = {
@@ -310,7 +305,7 @@ extern "C" int vp8hip_trace_gather_async(vp8hip_ctx *c, const vp8hip_gather_job 
             L.j[k].trace = jobs[i0 + k].trace;
             L.j[k].src = jobs[i0 + k].src;
         }
-        hipLaunchKernelGGL(kernel, dim3((unsigned)L.S, (unsigned)m, gz), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
+        hipLaunchKernelGGL(kernel, dim3((unsigned)L.g.S, (unsigned)m, gz), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
                            (const uint8_t *)src, src_stride, (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
         HIPCHK(c, hipGetLastError());
     }

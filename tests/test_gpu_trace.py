@@ -14,30 +14,11 @@ from vp8_testlib import ivf_path
 from handover_testlib import (TORCH_DTYPE, Producer, assert_destinations_refused, assert_guards_intact, bits, equal_on_device, guarded,
                               later_writers_producer, write_later_frames)
 import trace_reference as R
+from trace_testlib import dwords, random_trace, slot_ir, to_pool
 
 pytestmark = pytest.mark.gpu
 
 SCALES = [(1.0, 1.0), "pixels", (0.125, -3.0), (-1.0 / 3, 1e-3)]
-
-
-def slot_ir(ctx, slot):
-    return ctx.ir_fetch(slot)[0], ctx.mvs_fetch(slot)
-
-
-def dwords(t):
-    """int16 [..., h, w, 2] on the device -> numpy uint32 [..., h, w]"""
-    a = np.ascontiguousarray(t.cpu().numpy())
-    return a.view(np.uint32).reshape(a.shape[:-1])
-
-
-def to_pool(a):
-    """numpy uint32 [h, w] -> int16 [h, w, 2] on the device"""
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int16).reshape(a.shape + (2,))).to("cuda:0")
-
-
-def random_trace(rng, w, h):
-    """seeded random positions inside the picture"""
-    return R.pack(rng.integers(0, w, (h, w)), rng.integers(0, h, (h, w)))
 
 
 def refs_as_the_parser_numbers_them(prod):

@@ -14,7 +14,7 @@ from vp8_testlib import ivf_path
 from handover_testlib import assert_destinations_refused, assert_guards_intact, guarded
 import trace_reference as T
 import trace_gather_reference as G
-from test_gpu_trace import dwords, random_trace, slot_ir, to_pool
+from trace_testlib import dwords, random_trace, to_pool, traced_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -72,43 +72,6 @@ def check(ctx, pool, jobs, src_t, src_np, traces, size=(0, 0), filt="nearest", o
             excess = G.bilinear_excess(got[k], *ref)
             assert np.isfinite(got[k]).all() and excess <= 0.0, (what, k, size, filt, excess)
     return got_t
-
-
-def traced_stream(P, name, form, monkeypatch):
-    """every frame of a fixture into a frame buffer of its own and traced into the pool entry of that number, one launch per frame;
-    -> (ctx, pool, traces by trace_reference over the slot's IR, shown frames, frame types)"""
-    monkeypatch.setenv("VP8HIP_RECON", "simt" if form == "tiles" else "wave")
-    w, h, frames = P.read_ivf(ivf_path(name))
-    nf = len(frames)
-    ctx = P.Vp8Hip(0)
-    parser = P.Parser()
-    try:
-        ctx.configure(w, h, nf + 1, 1)
-        pool = ctx.trace_pool(nf + 1)
-        pool.zero_()
-        mine = [None] * nf + [np.zeros((h, w), np.uint32)]
-        phys, shown, types = {}, [], []
-        for i, data in enumerate(frames):
-            hdr, _ = ctx.parse_into_slot_compact(parser, data, 0)
-            r = parser.refs
-            refs = tuple(phys.get(k, nf) for k in (r.lst_idx, r.gld_idx, r.alt_idx))
-            ctx.decode([(0, i, refs)], P.STAGE_ALL)
-            ctx.frames_trace([(0, i, refs)], pool)
-            ctx.sync()
-            mbs, mvs = slot_ir(ctx, 0)
-            mine[i] = T.trace(hdr, mbs, mvs, [mine[k] for k in refs])
-            new = r.new_idx
-            parser.swap(hdr)
-            phys[new] = i
-            types.append(hdr.frame_type)
-            if hdr.show_frame:
-                shown.append(phys[parser.refs.show_idx])
-    except BaseException:
-        ctx.close()
-        raise
-    finally:
-        parser.close()
-    return ctx, pool, mine, shown, types
 
 
 @pytest.mark.parametrize("form", ["tiles", "raster"])

@@ -14,7 +14,7 @@ from handover_testlib import TORCH_DTYPE, assert_destinations_refused, assert_gu
 import scale_reference as S
 import trace_reference as T
 import trace_residual_reference as R
-from test_gpu_trace import dwords, random_trace, to_pool
+from trace_testlib import dwords, random_trace, to_pool, traced_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -79,28 +79,9 @@ def test_streams_end_to_end(pkg, name, form, monkeypatch):
     """every frame of a stream into a frame buffer of its own, the pool numbered like the frame buffers and traced with the decode
     jobs; then every frame against frame 0's buffer, the parameters in rotation.  Expected values from planes downloaded AFTER the
     calls: a download gives a tiled frame its raster form, which the reader would then take"""
-    P = pkg
-    monkeypatch.setenv("VP8HIP_RECON", "simt" if form == "tiles" else "wave")
-    w, h, frames = P.read_ivf(ivf_path(name))
-    nf = len(frames)
-    ctx = P.Vp8Hip(0)
-    parser = P.Parser()
+    ctx, pool, _, _, types = traced_stream(pkg, name, form, monkeypatch)
     try:
-        ctx.configure(w, h, nf + 1, 1)
-        pool = ctx.trace_pool(nf + 1)
-        pool.zero_()
-        phys, types = {}, []
-        for i, data in enumerate(frames):
-            hdr, _ = ctx.parse_into_slot_compact(parser, data, 0)
-            r = parser.refs
-            job = (0, i, tuple(phys.get(k, nf) for k in (r.lst_idx, r.gld_idx, r.alt_idx)))
-            ctx.decode([job], P.STAGE_ALL)
-            ctx.frames_trace([job], pool)
-            ctx.sync()
-            new = r.new_idx
-            parser.swap(hdr)
-            phys[new] = i
-            types.append(hdr.frame_type)
+        w, h, nf = ctx.width, ctx.height, len(types)
         assert types[0] == 0 and sum(types) > 0
         outs = [call(ctx, pool, [(i, i, 0)], **combo(i, w, h)) for i in range(nf)]
         ctx.sync()
@@ -117,7 +98,6 @@ def test_streams_end_to_end(pkg, name, form, monkeypatch):
             nonzero += bool(ref.any())
         assert not want(packed[0], packed[0], traces[0], w, h).any() and nonzero > nf // 2
     finally:
-        parser.close()
         ctx.close()
 
 

@@ -7,51 +7,11 @@ import ctypes
 import numpy as np
 import pytest
 
-from vp8_testlib import ivf_path, oracle_decode
+from vp8_testlib import oracle_decode
 import side_reference as S
 import trace_reference as R
+from trace_testlib import NEWMV, chain, frames_of, luma, make_hdr, whole_pixel_frame
 
-NEARESTMV, NEARMV, ZEROMV, NEWMV, SPLITMV = 5, 6, 7, 8, 9
-
-
-def make_hdr(P, w, h, frame_type=1):
-    hdr = P.FrameHdr()
-    hdr.width, hdr.height, hdr.mb_cols, hdr.mb_rows, hdr.frame_type = w, h, (w + 15) // 16, (h + 15) // 16, frame_type
-    hdr.show_frame = 1
-    return hdr
-
-
-def _luma(buf, g, h, w, border=0):
-    o = g.y_off - border * g.y_stride - border
-    return np.lib.stride_tricks.as_strided(buf[o:], shape=(h + 2 * border, w + 2 * border), strides=(g.y_stride, 1))
-
-
-def _whole_pixel_frame(P, w, h, rng):
-    """every macroblock inter and skipped, references 1..3 mixed, whole-pixel vectors that take a block at most 24 pixels past any
-    edge of the coded area, a third of the macroblocks SPLITMV (all four partitionings)"""
-    hdr = make_hdr(P, w, h)
-    cols, rows = hdr.mb_cols, hdr.mb_rows
-    nmb = cols * rows
-    mbs = np.zeros((nmb, 64), np.uint8)
-    mvs = np.zeros((nmb, 16, 2), np.int16)
-    mbs[:, 3] = 1                                # skipped: no residual
-    split = [np.repeat(np.arange(2), 8), np.tile(np.repeat(np.arange(2), 2), 4), (np.arange(16) // 8) * 2 + (np.arange(16) % 4) // 2, np.arange(16)]
-    for i in range(nmb):
-        r, c = divmod(i, cols)
-        mbs[i, 2] = rng.integers(1, 4)
-        lo_x, hi_x = max(-24 - 16 * c, -48), min(16 * (cols - 1 - c) + 24, 48)
-        lo_y, hi_y = max(-24 - 16 * r, -48), min(16 * (rows - 1 - r) + 24, 48)
-
-        def vec(n):
-            return np.stack([rng.integers(lo_y, hi_y + 1, n), rng.integers(lo_x, hi_x + 1, n)], 1) * 8
-        if i % 3 == 0:
-            part = 3 if nmb == 1 else int(rng.integers(0, 4))          # (a lone macroblock: sixteen vectors)
-            mbs[i, 0], mbs[i, 5] = SPLITMV, part
-            mvs[i] = vec(16)[split[part]]
-        else:
-            mbs[i, 0] = NEWMV
-            mvs[i] = vec(1)
-    return hdr, mbs, mvs
 
 
 @pytest.mark.parametrize("size", [(16, 16), (67, 45), (176, 144)])
@@ -62,12 +22,12 @@ def test_oracle_pins_axis_order_sign_and_clamp(pkg, size):
     w, h = size
     rng = np.random.default_rng(w * 131 + h)
     g = P.geom(w, h)
-    hdr, mbs, mvs = _whole_pixel_frame(P, w, h, rng)
+    hdr, mbs, mvs = whole_pixel_frame(P, w, h, rng)
     pics, bufs = [], []
     for _ in range(3):
         pic = rng.integers(0, 256, (h, w)).astype(np.uint8)
         buf = np.zeros(g.frame_size, np.uint8)
-        _luma(buf, g, g.aligned_h, g.aligned_w, 32)[:] = np.pad(pic, ((32, g.aligned_h - h + 32), (32, g.aligned_w - w + 32)), "edge")
+        luma(buf, g, g.aligned_h, g.aligned_w, 32)[:] = np.pad(pic, ((32, g.aligned_h - h + 32), (32, g.aligned_w - w + 32)), "edge")
         pics.append(pic)
         bufs.append(buf)
     dst = np.zeros(g.frame_size, np.uint8)
@@ -77,7 +37,7 @@ def test_oracle_pins_axis_order_sign_and_clamp(pkg, size):
     want = np.zeros((h, w), np.uint8)
     for q in (1, 2, 3):
         want[r == q] = pics[q - 1][sy[r == q], sx[r == q]]
-    got = _luma(dst, g, h, w)
+    got = luma(dst, g, h, w)
     assert np.array_equal(got, want), (size, int((got != want).sum()))
     # the frame does what the test is about: vectors both ways on both axes, and sources that the clamp moved
     ys, xs = np.mgrid[0:h, 0:w]
@@ -90,38 +50,9 @@ def test_oracle_pins_axis_order_sign_and_clamp(pkg, size):
     assert np.array_equal(tx, sx) and np.array_equal(ty, sy)
 
 
-def _frames(P, name):
-    """every frame of a fixture through the host parser: (hdr, mbs, mvs, (new, last, golden, alt) as vp8_refs numbers them)"""
-    _, _, frames = P.read_ivf(ivf_path(name))
-    parser = P.Parser()
-    out = []
-    try:
-        for data in frames:
-            hdr, _, mbs, _, mvs = P.parse_to_numpy(parser, data)
-            r = parser.refs
-            out.append((hdr, mbs, mvs, (r.new_idx, r.lst_idx, r.gld_idx, r.alt_idx)))
-            parser.swap(hdr)
-    finally:
-        parser.close()
-    return out
-
-
-def _chain(frames, last_only=False):
-    """the trace of every frame, the pool numbered like the frame buffers; last_only: every macroblock follows the last frame"""
-    pool, out = {}, []
-    for hdr, mbs, mvs, (new, lst, gld, alt) in frames:
-        if last_only:
-            mbs = mbs.copy()
-            mbs[:, R.O_REF] = np.minimum(mbs[:, R.O_REF], 1)
-            gld = alt = None
-        pool[new] = R.trace(hdr, mbs, mvs, [pool.get(lst), pool.get(gld), pool.get(alt)])
-        out.append(pool[new])
-    return out
-
-
 def test_one_hop_agrees_with_the_side_tensors(pkg):
     P = pkg
-    frames = _frames(P, "p_odd_130x98")
+    frames = frames_of(P, "p_odd_130x98")
     hdr0, hdr, mbs, mvs = frames[0][0], *frames[1][:3]
     assert hdr0.frame_type == 0 and hdr.frame_type == 1
     w, h = hdr.width, hdr.height
@@ -144,8 +75,8 @@ def test_the_chain_discriminates(pkg, name):
     """following the reference each macroblock names differs from following the frame before on more than half of all pixel-frames;
     every value stays inside the picture"""
     P = pkg
-    frames = _frames(P, name)
-    full, last = _chain(frames), _chain(frames, last_only=True)
+    frames = frames_of(P, name)
+    full, last = chain(frames), chain(frames, last_only=True)
     differ = sum(int((a != b).sum()) for a, b in zip(full, last))
     total = sum(a.size for a in full)
     assert 2 * differ > total, (name, differ, total)
@@ -162,7 +93,7 @@ def test_key_frames_intra_macroblocks_and_missing_references(pkg):
     P = pkg
     w, h = 67, 45
     rng = np.random.default_rng(3)
-    hdr, mbs, mvs = _whole_pixel_frame(P, w, h, rng)
+    hdr, mbs, mvs = whole_pixel_frame(P, w, h, rng)
     mvs += rng.integers(-7, 8, mvs.shape).astype(np.int16)          # sub-pixel parts
     ident = R.identity(w, h)
     junk = [rng.integers(0, 2 ** 32, (h, w), dtype=np.uint32) for _ in range(3)]

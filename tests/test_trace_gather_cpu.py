@@ -15,7 +15,7 @@ import scale_reference as S
 import trace_reference as T
 import trace_residual_reference as R
 import trace_gather_reference as G
-from test_trace_cpu import _chain, _frames
+from trace_testlib import chain, frames_of
 
 HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "vp8hip.h")
 
@@ -32,7 +32,7 @@ def test_display_size_is_fancy_indexing(size):
     for dtype, C in ((np.uint8, 1), (np.int16, 5), (np.float32, 3)):
         src = rng.integers(0, 200, (C, h, w)).astype(dtype)
         for t in (T.pack(rng.integers(0, w, (h, w)), rng.integers(0, h, (h, w))), wild_trace(rng, w, h), T.identity(w, h)):
-            ax, ay = R.clamped(t, w, h)
+            ax, ay = T.clamped(t, w, h)
             got = G.nearest(src, t, w, h)
             assert got.dtype == src.dtype and got.shape == (C, h, w) and np.array_equal(got, src[:, ay, ax])
             # another output size: the display-size result under each output's centre
@@ -101,8 +101,8 @@ def test_pinned_to_the_accumulated_residual(pkg, name):
     """every frame of a stream as the oracle decodes it, its trace by trace_reference over the parsed IR: the anchor's RGB bytes
     gathered at the trace are the frame's RGB bytes minus the accumulated residual, element for element"""
     P = pkg
-    frames = _frames(P, name)
-    traces = _chain(frames)
+    frames = frames_of(P, name)
+    traces = chain(frames)
     _, kept = oracle_decode_ivf(name, keep_frames=True)
     assert len(kept) == len(frames)
     w, h = frames[0][0].width, frames[0][0].height

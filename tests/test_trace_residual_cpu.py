@@ -12,7 +12,7 @@ import rgb_reference as RGB
 import scale_reference as S
 import trace_reference as T
 import trace_residual_reference as R
-from test_trace_cpu import _luma, _whole_pixel_frame
+from trace_testlib import luma, whole_pixel_frame
 
 SIZES = [(16, 16), (17, 33), (67, 45)]
 
@@ -70,12 +70,12 @@ def test_oracle_pins_axis_order_and_sign(pkg, size):
     w, h = size
     rng = np.random.default_rng(w * 131 + h + 1)
     g = P.geom(w, h)
-    hdr, mbs, mvs = _whole_pixel_frame(P, w, h, rng)
+    hdr, mbs, mvs = whole_pixel_frame(P, w, h, rng)
     mvs = ((mvs >> 4) << 4).astype(np.int16)             # an even number of pixels: the chroma vectors are whole too
     mbs[:, T.O_REF] = 1                                 # one reference: the anchor
     pic = rng.integers(0, 256, (h, w)).astype(np.uint8)
     ref = np.full(g.frame_size, 128, np.uint8)
-    _luma(ref, g, g.aligned_h, g.aligned_w, 32)[:] = np.pad(pic, ((32, g.aligned_h - h + 32), (32, g.aligned_w - w + 32)), "edge")
+    luma(ref, g, g.aligned_h, g.aligned_w, 32)[:] = np.pad(pic, ((32, g.aligned_h - h + 32), (32, g.aligned_w - w + 32)), "edge")
     dst = np.zeros(g.frame_size, np.uint8)
     oracle_decode(hdr, mbs, np.zeros((len(mbs), 400), np.int16), mvs, dst, [ref, ref, ref], stages=1)
     cur, anc = S.scale_frame(dst, g, w, h, w, h, 0), S.scale_frame(ref, g, w, h, w, h, 0)
@@ -126,7 +126,7 @@ def test_clamp_against_a_loop():
                 want[ch, y, x] = c[ch, y, x] - a[ch, ay, ax]
     assert moved > h * w // 2
     assert np.array_equal(R.residual(cur, anc, t, w, h, matrix="bt709"), want)
-    ax, ay = R.clamped(t, w, h)
+    ax, ay = T.clamped(t, w, h)
     assert ax.min() == 0 and ax.max() == w - 1 and ay.min() == 0 and ay.max() == h - 1
 
 

@@ -8,7 +8,7 @@ the kernels go about it."""
 import numpy as np
 
 from tensor_reference import grid_map
-from trace_residual_reference import clamped
+from trace_reference import clamped
 
 
 def size(w, h, channels, elem, dst_w=0, dst_h=0):

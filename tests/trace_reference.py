@@ -20,6 +20,12 @@ def unpack(t):
     return (t & 0xffff).astype(np.uint16).view(np.int16), (t >> 16).astype(np.uint16).view(np.int16)
 
 
+def clamped(t, w, h):
+    """the position a trace names, clamped to the picture: (ax, ay) as int64"""
+    tx, ty = unpack(t)
+    return np.clip(tx.astype(np.int64), 0, w - 1), np.clip(ty.astype(np.int64), 0, h - 1)
+
+
 def identity(w, h):
     ys, xs = np.mgrid[0:h, 0:w]
     return pack(xs, ys)

@@ -6,7 +6,7 @@ import numpy as np
 
 import rgb_reference as RGB
 from tensor_reference import DTYPES, convert, grid_map
-from trace_reference import unpack
+from trace_reference import clamped
 
 
 def size(w, h, dst_w=0, dst_h=0, dtype="i16"):
@@ -17,12 +17,6 @@ def size(w, h, dst_w=0, dst_h=0, dtype="i16"):
 def pack_i420(y, u, v):
     """three planes -> the packed image"""
     return np.concatenate([np.asarray(p, np.uint8).ravel() for p in (y, u, v)])
-
-
-def clamped(t, w, h):
-    """the position a trace names, clamped to the picture: (ax, ay) as int64"""
-    tx, ty = unpack(t)
-    return np.clip(tx.astype(np.int64), 0, w - 1), np.clip(ty.astype(np.int64), 0, h - 1)
 
 
 def residual(cur, anchor, t, w, h, dst_w=0, dst_h=0, dtype="i16", matrix="bt601", order="rgb", scale=(1.0, 1.0, 1.0)):
