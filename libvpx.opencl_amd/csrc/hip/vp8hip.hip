@@ -63,35 +63,16 @@ int vp8hip_fail(vp8hip_ctx *c, int code, const char *fmt, ...)
 
 extern "C" const char *vp8hip_last_error(const vp8hip_ctx *ctx) { return ctx ? ctx->err : g_create_error; }
 
+// what a (re)configuration gives back (vp8hip_ctx.hip.h: what survives one); the slots take their host stagings with them
 static void free_pools(vp8hip_ctx *c)
 {
-    if (c->fb_block) (void)hipFree(c->fb_block);
-    if (c->tile_alloc) (void)hipFree(c->tile_alloc);
-    c->tile_block = c->tile_alloc = nullptr;
-    if (c->slot_block_dev) (void)hipFree(c->slot_block_dev);
-    if (c->pool) (void)hipFree(c->pool);
-    if (c->d_pool_ctr) (void)hipFree(c->d_pool_ctr);
-    c->pool = nullptr; c->d_pool_ctr = nullptr; c->pool_chunks = c->chunk_blocks = 0;
-    if (c->gran_recon) (void)hipFree(c->gran_recon);
-    if (c->gran_lf) (void)hipFree(c->gran_lf);
-    if (c->d_intra_flags) (void)hipFree(c->d_intra_flags);
-    c->d_intra_flags = nullptr; c->intra_flags_cap = 0;
-    c->gran_recon = c->gran_lf = nullptr; c->gran_recon_cap = c->gran_lf_cap = 0;
-    for (Slot &s : c->slots) {
-        if (s.h_block) (void)hipHostFree(s.h_block);
-        free(s.h_dense);
-    }
-    c->fb_block = nullptr; c->slot_block_dev = nullptr;
+    c->fb_block.reset(); c->tile_alloc.reset(); c->slot_block_dev.reset();
+    c->tile_block = nullptr;
+    c->pool.reset(); c->d_pool_ctr.reset();
+    c->pool_chunks = c->chunk_blocks = 0;
+    c->gran_recon.reset(); c->gran_lf.reset(); c->d_intra_flags.reset();
     c->fb.clear(); c->fb_tiles.clear(); c->fb_state.clear(); c->slots.clear();
 }
-
-static void destroy_events(vp8hip_ctx *c)
-{
-    for (int r = 0; r < VP8HIP_STATS_RING; r++) for (int i = 0; i < 6; i++) if (c->evr[r][i]) (void)hipEventDestroy(c->evr[r][i]);
-    for (int k = 0; k < VP8HIP_NBUF; k++) if (c->ev_jobs2[k]) (void)hipEventDestroy(c->ev_jobs2[k]);
-    if (c->ev_conv) (void)hipEventDestroy(c->ev_conv);
-}
-
 
 extern "C" int vp8hip_create(int device, vp8hip_ctx **out)
 {
@@ -112,37 +93,21 @@ extern "C" int vp8hip_create(int device, vp8hip_ctx **out)
     if (!strstr(prop.gcnArchName, "gfx950"))
         return fail(nullptr, -1, "device %d is %s; this library carries gfx950 (MI355X) code only", device,
                     prop.gcnArchName);
-    vp8hip_ctx *c = new vp8hip_ctx();
-    memset(c->err, 0, sizeof c->err);
+    vp8hip_ctx *c = new vp8hip_ctx;
     c->device = device;
     c->num_cu = prop.multiProcessorCount;
     c->max_lds = 160 * 1024;
-    c->fb_block = nullptr; c->slot_block_dev = nullptr;
     read_knobs(c->knobs);
-    c->tile_block = c->tile_alloc = nullptr; c->tile_frame = 0;
-    c->d_jobs = nullptr; c->h_jobs = nullptr; c->jobs_cap = 0;
-    for (int k = 0; k < VP8HIP_NBUF; k++) { c->d_jobs2[k] = nullptr; c->h_jobs2[k] = nullptr; c->ev_jobs2[k] = nullptr; }
-    c->parity = 0;
-    c->d_md5 = nullptr; c->md5_cap = 0;
-    c->width = c->height = 0;
-    c->ncalls = 0;
-    c->gran_recon = c->gran_lf = nullptr; c->gran_recon_cap = c->gran_lf_cap = 0; c->epoch = 0;
-    c->h_status = c->d_status = nullptr;
-    memset(&c->stats, 0, sizeof c->stats);
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) {
+    if ((e = hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking)) != hipSuccess) {
         fail(nullptr, -1, "hipStreamCreate: %s", hipGetErrorString(e));
         delete c;
         return -1;
     }
-    c->stream_d2h = nullptr; c->ev_d2h_from = c->ev_d2h_done = nullptr; c->d2h_first = c->d2h_count = 0; c->fb_stride = 0;
-    // events: every creation is checked; on failure whatever exists is destroyed again (null handles are skipped)
-    for (int r = 0; r < VP8HIP_STATS_RING; r++) for (int i = 0; i < 6; i++) c->evr[r][i] = nullptr;
-    c->ev_conv = nullptr;
-    e = hipSuccess;
+    // events: every creation is checked; on failure the context goes, and whatever exists with it
     for (int r = 0; r < VP8HIP_STATS_RING && e == hipSuccess; r++)
-        for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipEventCreate(&c->evr[r][i]);
-    for (int k = 0; k < VP8HIP_NBUF && e == hipSuccess; k++) e = hipEventCreateWithFlags(&c->ev_jobs2[k], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_conv, hipEventDisableTiming);
+        for (int i = 0; i < 6 && e == hipSuccess; i++) e = c->evr[r][i].ensure(hipEventDefault);
+    for (int k = 0; k < VP8HIP_NBUF && e == hipSuccess; k++) e = c->ev_jobs2[k].ensure();
+    if (e == hipSuccess) e = c->ev_conv.ensure();
     const char *what = "hipEventCreate";
     const void *big_lds[6] = { (const void *)vp8_recon_kernel, (const void *)vp8_recon_xcu_kernel,
                                (const void *)vp8_loopfilter_xcu_kernel, (const void *)vp8_loopfilter_kernel,
@@ -153,8 +118,6 @@ extern "C" int vp8hip_create(int device, vp8hip_ctx **out)
     }
     if (e != hipSuccess) {
         fail(nullptr, -1, "%s: %s", what, hipGetErrorString(e));
-        destroy_events(c);
-        (void)hipStreamDestroy(c->stream);
         delete c;
         return -1;
     }
@@ -168,49 +131,8 @@ extern "C" void vp8hip_destroy(vp8hip_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    free_pools(c);
-    if (c->d_conv_jobs) (void)hipFree(c->d_conv_jobs);
-    if (c->h_conv_jobs) (void)hipHostFree(c->h_conv_jobs);
-    for (int k = 0; k < VP8HIP_NBUF; k++) if (c->d_jobs2[k]) (void)hipFree(c->d_jobs2[k]);
-    for (int k = 0; k < VP8HIP_NBUF; k++) if (c->h_jobs2[k]) (void)hipHostFree(c->h_jobs2[k]);
-    if (c->h_status) (void)hipHostFree(c->h_status);
-    if (c->d_sched) (void)hipFree(c->d_sched);
-    // the post-processing tables outlive reconfigurations: the caller's noise state does too (vp8/common/postproc.c keeps
-    // postproc_state.noise across vp8_alloc_frame_buffers) and only sends the noise table again when q changes
-    if (c->d_pp) (void)hipFree(c->d_pp);
-    if (c->d_md5) (void)hipFree(c->d_md5);
-    if (c->d_md5_idx) (void)hipFree(c->d_md5_idx);
-    if (c->h_md5_idx) (void)hipHostFree(c->h_md5_idx);
-    if (c->h_pp) (void)hipHostFree(c->h_pp);
-    if (c->ev_pp) (void)hipEventDestroy(c->ev_pp);
-    for (int k = 0; k < 2; k++) {
-        if (c->d_ent_frames2[k]) (void)hipFree(c->d_ent_frames2[k]);
-        if (c->d_ent_data2[k]) (void)hipFree(c->d_ent_data2[k]);
-        if (c->ev_ent_in[k]) (void)hipEventDestroy(c->ev_ent_in[k]);
-        if (c->ev_ent_out[k]) (void)hipEventDestroy(c->ev_ent_out[k]);
-    }
-    if (c->stream_h2d) (void)hipStreamDestroy(c->stream_h2d);
-    if (c->d_i420) (void)hipFree(c->d_i420);
-    if (c->d_rgb) (void)hipFree(c->d_rgb);
-    if (c->ev_pack) (void)hipEventDestroy(c->ev_pack);
-    for (int k = 0; k < 3; k++) {
-        if (c->stream_d2h_more[k]) (void)hipStreamDestroy(c->stream_d2h_more[k]);
-        if (c->ev_d2h_more[k]) (void)hipEventDestroy(c->ev_d2h_more[k]);
-    }
-    if (c->d_ent_scratch) (void)hipFree(c->d_ent_scratch);
-    if (c->d_ent_status) (void)hipFree(c->d_ent_status);
-    if (c->d_mfqe) (void)hipFree(c->d_mfqe);
-    if (c->h_mfqe) (void)hipHostFree(c->h_mfqe);
-    if (c->ev_mfqe) (void)hipEventDestroy(c->ev_mfqe);
-    if (c->d_vis) (void)hipFree(c->d_vis);
-    if (c->h_vis) (void)hipHostFree(c->h_vis);
-    if (c->ev_vis) (void)hipEventDestroy(c->ev_vis);
-    destroy_events(c);
-    if (c->stream_d2h) { (void)hipStreamSynchronize(c->stream_d2h); (void)hipStreamDestroy(c->stream_d2h); }
-    if (c->ev_d2h_from) (void)hipEventDestroy(c->ev_d2h_from);
-    if (c->ev_d2h_done) (void)hipEventDestroy(c->ev_d2h_done);
-    (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c->stream_d2h) (void)hipStreamSynchronize(c->stream_d2h);
+    delete c;           // the members give back what they own: buffers and events first, the streams last (vp8hip_ctx.hip.h)
 }
 
 // per-wave LDS footprints; must match the kernels (WaveLds 2080 B + line slot, LfWaveLds 768 B)
@@ -219,25 +141,26 @@ static size_t lf_lds_bytes(int nw) { return 256 + (size_t)nw * 2 * 4096; }   // 
 
 static int configure_pools(vp8hip_ctx *c, int width, int height, int num_fb, int num_slots, size_t pool_bytes);
 
-extern "C" int vp8hip_configure(vp8hip_ctx *c, int width, int height, int num_fb, int num_slots)
+// a failed (re)configuration leaves an UNconfigured context, not a half-allocated one
+static int configure(vp8hip_ctx *c, int width, int height, int num_fb, int num_slots, size_t pool_bytes)
 {
-    const int rc = configure_pools(c, width, height, num_fb, num_slots, 0);
-    if (rc && c) {               // a failed (re)configuration leaves an UNconfigured context, not a half-allocated one
+    const int rc = configure_pools(c, width, height, num_fb, num_slots, pool_bytes);
+    if (rc && c) {
         free_pools(c);
         c->width = c->height = 0;
     }
     return rc;
 }
 
+extern "C" int vp8hip_configure(vp8hip_ctx *c, int width, int height, int num_fb, int num_slots)
+{
+    return configure(c, width, height, num_fb, num_slots, 0);
+}
+
 extern "C" int vp8hip_configure_pooled(vp8hip_ctx *c, int width, int height, int num_fb, int num_slots, size_t pool_bytes)
 {
     if (!c || !pool_bytes) return fail(c, -2, "vp8hip_configure_pooled: bad arguments");
-    const int rc = configure_pools(c, width, height, num_fb, num_slots, pool_bytes);
-    if (rc) {
-        free_pools(c);
-        c->width = c->height = 0;
-    }
-    return rc;
+    return configure(c, width, height, num_fb, num_slots, pool_bytes);
 }
 
 extern "C" int vp8hip_pool_reset(vp8hip_ctx *c)
@@ -317,23 +240,19 @@ static int configure_pools(vp8hip_ctx *c, int width, int height, int num_fb, int
         if (pool_bytes / chunk_bytes < 2 || pool_bytes / chunk_bytes > 0xffffffffull / c->chunk_blocks)
             return fail(c, -2, "vp8hip_configure_pooled: a pool of %zu bytes (chunks of %zu; at most 2^32 blocks)", pool_bytes, chunk_bytes);
         c->pool_chunks = (unsigned)(pool_bytes / chunk_bytes) - 1;              // (the last chunk takes what no longer fits)
-        HIPCHK(c, hipMalloc((void **)&c->pool, ((size_t)c->pool_chunks + 1) * chunk_bytes + 8192));
-        HIPCHK(c, hipMalloc((void **)&c->d_pool_ctr, 256));
+        HIPCHK(c, c->pool.grow(((size_t)c->pool_chunks + 1) * chunk_bytes + 8192));
+        HIPCHK(c, c->d_pool_ctr.grow(64));
         HIPCHK(c, hipMemsetAsync(c->d_pool_ctr, 0, 256, c->stream));
     }
     const size_t o_mvs = align_up(o_blocks + c->cap_blocks * 32, 256);
     const size_t slotsz = align_up(o_mvs + (size_t)c->nmb * 16 * sizeof(vp8ir_mv), 256);
-    HIPCHK(c, hipMalloc((void **)&c->slot_block_dev, slotsz * num_slots + 4096));   // + room for prefetches past the last macroblock
+    HIPCHK(c, c->slot_block_dev.grow(slotsz * num_slots + 4096));   // + room for prefetches past the last macroblock
     c->slot_bytes = slotsz; c->o_mbx = o_mbx; c->o_blocks = o_blocks; c->o_mvs = o_mvs;
-    c->slots.resize(num_slots);
+    c->slots = std::vector<Slot>((size_t)num_slots);
     for (int i = 0; i < num_slots; i++) {
         char *d = c->slot_block_dev + slotsz * i;
         Slot &s = c->slots[i];
-        s.d_mbx = (vp8ir_mbx *)(d + o_mbx); s.d_blocks = c->pool ? (int16_t *)c->pool : (int16_t *)(d + o_blocks); s.d_mvs = (vp8ir_mv *)(d + o_mvs);
-        s.h_block = nullptr; s.h_hdr = nullptr; s.h_mbx = nullptr; s.h_blocks = nullptr; s.h_mvs = nullptr;
-        s.h_dense = nullptr; s.h_mbs = nullptr; s.h_coef = nullptr;
-        s.nblocks = 0;
-        memset(&s.hdr_copy, 0, sizeof s.hdr_copy);
+        s.d_mbx = (vp8ir_mbx *)(d + o_mbx); s.d_blocks = c->pool ? (int16_t *)c->pool.p : (int16_t *)(d + o_blocks); s.d_mvs = (vp8ir_mv *)(d + o_mvs);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -346,15 +265,13 @@ int vp8hip_drop_staging(vp8hip_ctx *c)
     int freed = 0;
     if (c->d_rgb) {              // the scratch of vp8hip_frames_rgb_async (vp8hip_rgb.hip): read and written on the main stream
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_rgb);
-        c->d_rgb = nullptr; c->rgb_cap = 0;
+        c->d_rgb.reset();
         freed = 1;
     }
     if (!c->d_i420) return freed;
     if (c->stream_d2h) HIPCHK(c, hipStreamSynchronize(c->stream_d2h));
     for (int k = 0; k < 3; k++) if (c->stream_d2h_more[k]) HIPCHK(c, hipStreamSynchronize(c->stream_d2h_more[k]));
-    (void)hipFree(c->d_i420);
-    c->d_i420 = nullptr; c->i420_cap = 0;
+    c->d_i420.reset();
     return 1;
 }
 extern "C" int vp8hip_release_staging(vp8hip_ctx *c)
@@ -369,13 +286,10 @@ int vp8hip_raster_pool(vp8hip_ctx *c)
     if (c->fb_block || c->fb.empty()) return 0;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = c->fb.size();
-    hipError_t e = hipMalloc((void **)&c->fb_block, c->fb_stride * n);
-    if (e != hipSuccess && vp8hip_drop_staging(c) == 1) { (void)hipGetLastError(); e = hipMalloc((void **)&c->fb_block, c->fb_stride * n); }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        c->fb_block = nullptr;
+    hipError_t e = c->fb_block.grow(c->fb_stride * n);
+    if (e != hipSuccess && vp8hip_drop_staging(c) == 1) e = c->fb_block.grow(c->fb_stride * n);
+    if (e != hipSuccess)
         return fail(c, -1, "no device memory for the raster form of %zu frame buffers (%zu MB)", n, c->fb_stride * n >> 20);
-    }
     HIPCHK(c, hipMemsetAsync(c->fb_block, 0, c->fb_stride * n, c->stream));
     for (size_t i = 0; i < n; i++) c->fb[i] = c->fb_block + c->fb_stride * i;
     return 0;
@@ -388,8 +302,8 @@ extern "C" int vp8hip_memory_usage(const vp8hip_ctx *c, vp8hip_memory *out)
     out->tile_pool = c->tile_block ? c->tile_frame * c->fb.size() + 8192 + VP8HIP_TILE_FRONT : 0;
     out->slots = c->slot_block_dev ? c->slot_bytes * c->slots.size() + 4096 : 0;
     out->block_pool = c->pool ? ((size_t)c->pool_chunks + 1) * c->chunk_blocks * 32 + 8192 : 0;
-    out->entropy_input = c->ent_frames_cap2[0] + c->ent_frames_cap2[1] + c->ent_data_cap2[0] + c->ent_data_cap2[1];
-    out->packed_staging = c->i420_cap;
+    out->entropy_input = c->d_ent_frames2[0].cap + c->d_ent_frames2[1].cap + c->d_ent_data2[0].cap + c->d_ent_data2[1].cap;
+    out->packed_staging = c->d_i420.cap;
     return 0;
 }
 
@@ -407,9 +321,9 @@ static int map_staging(vp8hip_ctx *c, Slot &s)
         return fail(c, -2, "a context with a block pool (vp8hip_configure_pooled) takes its IR from the device's entropy decoder only");
     if (s.h_block) return 0;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipHostMalloc((void **)&s.h_block, c->slot_bytes, hipHostMallocDefault));
+    HIPCHK(c, s.h_block.grow(c->slot_bytes));
     memset(s.h_block, 0, c->o_blocks);
-    s.h_hdr = (vp8ir_frame_hdr *)s.h_block; s.h_mbx = (vp8ir_mbx *)(s.h_block + c->o_mbx);
+    s.h_hdr = (vp8ir_frame_hdr *)s.h_block.p; s.h_mbx = (vp8ir_mbx *)(s.h_block + c->o_mbx);
     s.h_blocks = (int16_t *)(s.h_block + c->o_blocks); s.h_mvs = (vp8ir_mv *)(s.h_block + c->o_mvs);
     return 0;
 }
@@ -456,9 +370,8 @@ extern "C" int vp8hip_ir_map(vp8hip_ctx *c, int slot, vp8ir_frame_hdr **hdr, vp8
     if (map_staging(c, s)) return -1;
     if (!s.h_dense) {
         const size_t mb_bytes = (size_t)c->nmb * sizeof(vp8ir_mb);
-        s.h_dense = (char *)calloc(1, mb_bytes + (size_t)c->nmb * VP8IR_COEF_PER_MB * sizeof(int16_t));
-        if (!s.h_dense) return fail(c, -1, "vp8hip_ir_map: out of host memory");
-        s.h_mbs = (vp8ir_mb *)s.h_dense; s.h_coef = (int16_t *)(s.h_dense + mb_bytes);
+        if (s.h_dense.grow(mb_bytes + (size_t)c->nmb * VP8IR_COEF_PER_MB * sizeof(int16_t)) != hipSuccess) return fail(c, -1, "vp8hip_ir_map: out of host memory");
+        s.h_mbs = (vp8ir_mb *)s.h_dense.p; s.h_coef = (int16_t *)(s.h_dense + mb_bytes);
     }
     if (hdr) *hdr = s.h_hdr;
     if (mbs) *mbs = s.h_mbs;
@@ -526,7 +439,7 @@ extern "C" int vp8hip_get_stats_at(vp8hip_ctx *c, int back, vp8hip_stats *st)
     if (!c || !st || back < 0 || back >= VP8HIP_STATS_RING) return -2;
     if (back >= c->ncalls) { memset(st, 0, sizeof *st); return c->ncalls ? fail(c, -2, "vp8hip_get_stats_at: only %ld launches so far", c->ncalls) : 0; }
     const int r = (int)((c->ncalls - 1 - back) % VP8HIP_STATS_RING);
-    hipEvent_t *ev = c->evr[r];
+    const Event *ev = c->evr[r];
     vp8hip_stats out = c->evr_stats[r];
     HIPCHK(c, hipEventSynchronize(ev[3]));
     (void)hipEventElapsedTime(&out.recon_ms, ev[0], ev[1]);
@@ -639,6 +552,124 @@ extern "C" size_t vp8hip_i420_bytes(const vp8hip_ctx *c)
     return c && c->width ? (size_t)c->width * c->height + 2 * (size_t)((c->width + 1) / 2) * ((c->height + 1) / 2) : 0;
 }
 
+// ---- The steps of a batch download (fetch_impl, vp8hip_frames_md5_list_async), one function each.  They return 0, or -1 with
+// the error set.
+
+// a row is whole MD5 blocks (vp8_md5.hip): the hash reads tiles or raster frames; other widths: raster form, vp8_md5_any_kernel
+static bool md5_whole_blocks(const vp8hip_ctx *c) { return (c->width & 127) == 0; }
+
+// the download stream exists, with the events that order it against the main stream
+static int d2h_stream(vp8hip_ctx *c)
+{
+    if (!c->stream_d2h) {
+        // (a stream of another priority class than the context's: the runtime then gives it a hardware queue of its own, and what
+        // it carries -- a pass that waits on PCIe for a third of a second per 4096 frames -- runs BESIDE the main stream's kernels)
+        int prio_least = 0, prio_greatest = 0;
+        HIPCHK(c, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+        HIPCHK(c, c->stream_d2h.ensure(c->knobs.d2h_prio ? prio_least : 0));
+    }
+    HIPCHK(c, c->ev_d2h_from.ensure());
+    HIPCHK(c, c->ev_d2h_done.ensure());
+    return 0;
+}
+
+// side stream k exists, with its event
+static int d2h_side_stream(vp8hip_ctx *c, int k)
+{
+    HIPCHK(c, c->stream_d2h_more[k].ensure());
+    HIPCHK(c, c->ev_d2h_more[k].ensure());
+    return 0;
+}
+
+// `count` units of `unit` bytes from src to dst, once `after` has happened.  (A copy is one copy engine's work: 25-33 GB/s; in
+// pieces on streams of their own the link's other engines take part.)  The download stream carries the first piece and waits for
+// the others.
+static int d2h_copy(vp8hip_ctx *c, uint8_t *dst, const uint8_t *src, size_t unit, int count, hipEvent_t after)
+{
+    const int pieces = count >= 64 ? c->knobs.d2h_streams : 1;
+    const int per = (count + pieces - 1) / pieces;
+    for (int k = 1; k < pieces; k++) {
+        if (d2h_side_stream(c, k - 1)) return -1;
+        const int at = k * per, n = count - at < per ? count - at : per;
+        if (n < 1) break;
+        hipStream_t s = c->stream_d2h_more[k - 1];
+        HIPCHK(c, hipStreamWaitEvent(s, after, 0));
+        HIPCHK(c, hipMemcpyAsync(dst + unit * (size_t)at, src + unit * (size_t)at, unit * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(c->ev_d2h_more[k - 1], s));
+    }
+    HIPCHK(c, hipMemcpyAsync(dst, src, unit * (size_t)(per < count ? per : count), hipMemcpyDeviceToHost, c->stream_d2h));
+    for (int k = 1; k < pieces && k * per < count; k++) HIPCHK(c, hipStreamWaitEvent(c->stream_d2h, c->ev_d2h_more[k - 1], 0));
+    return 0;
+}
+
+// the packed staging holds `count` frames (and 256 bytes more).  required: no room is an error; else the caller looks at the
+// capacity and does without
+static int packed_staging(vp8hip_ctx *c, int count, bool required)
+{
+    const size_t bytes = vp8hip_i420_bytes(c) * (size_t)count;
+    if (bytes <= c->d_i420.cap) return 0;
+    HIPCHK(c, hipStreamSynchronize(c->stream_d2h));
+    if (c->d_i420.grow(bytes, bytes + 256) != hipSuccess && required)
+        return fail(c, -1, "no device memory for %d packed frames (%zu MB)", count, bytes >> 20);
+    return 0;
+}
+
+// frame buffers first_fb .. first_fb + count - 1, tiled or raster, as packed I420 in the staging, on stream s
+static int pack_frames(vp8hip_ctx *c, int first_fb, int count, bool tiled, hipStream_t s)
+{
+    const size_t fbytes = vp8hip_i420_bytes(c);
+    long units = (long)count * (tiled ? c->dg.mb_rows : c->height + 2 * ((c->height + 1) / 2));
+    if (units > 16L * c->num_cu) units = 16L * c->num_cu;
+    if (tiled)
+        hipLaunchKernelGGL(vp8_pack_i420_tiles_kernel, dim3((unsigned)units), dim3(256), 0, s, (const uint8_t *)c->fb_tiles[(size_t)first_fb],
+                           c->tile_frame, c->d_i420.p, fbytes, count, c->dg, c->width, c->height);
+    else
+        hipLaunchKernelGGL(vp8_pack_i420_raster_kernel, dim3((unsigned)units), dim3(256), 0, s, (const uint8_t *)c->fb_block, c->fb_stride,
+                           first_fb, c->d_i420.p, fbytes, count, c->dg, c->width, c->height);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// the digest buffer holds n, and -- listed: a fetch by list -- so do the index list and its staging (one wait for what the
+// download stream still reads, whichever of them grow)
+static int digest_room(vp8hip_ctx *c, int n, bool listed)
+{
+    if ((size_t)n <= c->d_md5.cap && (!listed || (size_t)n <= vp8hip_cap(c->d_md5_idx, c->h_md5_idx))) return 0;
+    HIPCHK(c, hipStreamSynchronize(c->stream_d2h));
+    const size_t cap = n < 64 ? 64 : (size_t)n;
+    HIPCHK(c, c->d_md5.grow(cap, 16 * cap));
+    if (listed) {
+        HIPCHK(c, c->d_md5_idx.grow(cap));
+        HIPCHK(c, c->h_md5_idx.grow(cap));
+    }
+    return 0;
+}
+
+// The digests of n frame buffers -- those `index` (device memory) lists, or first .. first + n - 1 -- on stream s, and on their
+// way to the caller: from the tiles, the raster form (whichever kernel the width allows) or the first n frames of the packed
+// staging (the raster reader over a geometry without borders).
+enum HashFrom { HASH_TILES, HASH_RASTER, HASH_PACKED };
+static int hash_frames(vp8hip_ctx *c, HashFrom from, const int *index, int first, int n, uint8_t *digests, hipStream_t s)
+{
+    const dim3 grid((unsigned)((n + 63) / 64));
+    if (from == HASH_PACKED) {
+        DevGeom pg = c->dg;
+        const int cw = c->width / 2, ch = (c->height + 1) / 2;
+        pg.y_off = 0; pg.y_stride = c->width; pg.uv_stride = cw;
+        pg.u_off = c->width * c->height; pg.v_off = pg.u_off + cw * ch;
+        hipLaunchKernelGGL(vp8_md5_kernel, grid, dim3(64), 0, s, (const uint8_t *)c->d_i420, vp8hip_i420_bytes(c), (const int *)nullptr, 0, n, pg,
+                           c->width, c->height, c->d_md5.p);
+    } else if (from == HASH_TILES)
+        hipLaunchKernelGGL(vp8_md5_tiles_kernel, grid, dim3(64), 0, s, (const uint8_t *)c->tile_block, c->tile_frame, index, first, n, c->dg,
+                           c->width, c->height, c->d_md5.p);
+    else
+        hipLaunchKernelGGL(md5_whole_blocks(c) ? vp8_md5_kernel : vp8_md5_any_kernel, grid, dim3(64), 0, s, (const uint8_t *)c->fb_block,
+                           c->fb_stride, index, first, n, c->dg, c->width, c->height, c->d_md5.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(digests, c->d_md5, 16 * (size_t)n, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 static int fetch_impl(vp8hip_ctx *c, int first_fb, int count, uint8_t *dst, uint8_t *digests, bool packed);
 extern "C" int vp8hip_frames_fetch_async(vp8hip_ctx *c, int first_fb, int count, uint8_t *dst, uint8_t *digests)
 {
@@ -663,7 +694,7 @@ static int fetch_impl(vp8hip_ctx *c, int first_fb, int count, uint8_t *dst, uint
     // 25-33).  The default is the plain way -- raster form in HBM first (vp8hip_need_raster), then the copy engines -- because a
     // pass that waits on PCIe occupies wave slots beside whatever else runs: with the entropy decoder on the device the pipeline
     // of bin/batch_md5 does 9.6 k 1080p frames/s the plain way and 6.5-8.5 k with direct downloads (gpurun_out/r4e).
-    const bool whole_blocks = (c->width & 127) == 0;        // a row is whole MD5 blocks (vp8_md5.hip); other widths: raster form, vp8_md5_any_kernel
+    const bool whole_blocks = md5_whole_blocks(c);
     bool tiled = c->tile_block != nullptr && (whole_blocks || !digests);
     for (int i = 0; i < count && tiled; i++) tiled = c->fb_state[(size_t)(first_fb + i)] == FB_TILES;
     if (tiled && dst && !packed && !c->knobs.direct_download) tiled = false;
@@ -673,104 +704,37 @@ static int fetch_impl(vp8hip_ctx *c, int first_fb, int count, uint8_t *dst, uint
         else tiled = at.type == hipMemoryTypeHost;
     }
     if (!tiled && (vp8hip_raster_pool(c) || vp8hip_need_raster(c, first_fb, count))) return -1;
-    if (!c->stream_d2h) {
-        // (a stream of another priority class than the context's: the runtime then gives it a hardware queue of its own, and what
-        // it carries -- a pass that waits on PCIe for a third of a second per 4096 frames -- runs BESIDE the main stream's kernels)
-        int prio_least = 0, prio_greatest = 0;
-        HIPCHK(c, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-        HIPCHK(c, hipStreamCreateWithPriority(&c->stream_d2h, hipStreamNonBlocking, c->knobs.d2h_prio ? prio_least : 0));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2h_from, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2h_done, hipEventDisableTiming));
-    }
+    if (d2h_stream(c)) return -1;
     if (c->d2h_count) HIPCHK(c, hipEventSynchronize(c->ev_d2h_done));  // one copy in flight at a time
     HIPCHK(c, hipEventRecord(c->ev_d2h_from, c->stream));             // everything queued so far: the frames' kernels
     HIPCHK(c, hipStreamWaitEvent(c->stream_d2h, c->ev_d2h_from, 0));
+    const size_t fbytes = vp8hip_i420_bytes(c);
     if (dst && packed) {
         // packed I420: a pass from whichever form the frames are in into a staging buffer on the device, then the copy engines, in
         // pieces on streams of their own -- a tenth less over the link than whole frame buffers
-        const size_t fbytes = vp8hip_i420_bytes(c);
-        if (fbytes * (size_t)count > c->i420_cap) {
-            HIPCHK(c, hipStreamSynchronize(c->stream_d2h));
-            if (c->d_i420) (void)hipFree(c->d_i420);
-            c->d_i420 = nullptr; c->i420_cap = 0;
-            if (hipMalloc((void **)&c->d_i420, fbytes * (size_t)count + 256) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(c, -1, "no device memory for %d packed frames (%zu MB)", count, fbytes * (size_t)count >> 20);
-            }
-            c->i420_cap = fbytes * (size_t)count;
-        }
-        long units = (long)count * (tiled ? c->dg.mb_rows : c->height + 2 * ((c->height + 1) / 2));
-        if (units > 16L * c->num_cu) units = 16L * c->num_cu;
-        if (tiled)
-            hipLaunchKernelGGL(vp8_pack_i420_tiles_kernel, dim3((unsigned)units), dim3(256), 0, c->stream_d2h, (const uint8_t *)c->fb_tiles[(size_t)first_fb],
-                               c->tile_frame, c->d_i420, fbytes, count, c->dg, c->width, c->height);
-        else
-            hipLaunchKernelGGL(vp8_pack_i420_raster_kernel, dim3((unsigned)units), dim3(256), 0, c->stream_d2h, (const uint8_t *)c->fb_block, c->fb_stride,
-                               first_fb, c->d_i420, fbytes, count, c->dg, c->width, c->height);
-        HIPCHK(c, hipGetLastError());
-        const int pieces = count >= 64 ? c->knobs.d2h_streams : 1;
-        const int per = (count + pieces - 1) / pieces;
+        if (packed_staging(c, count, true) || pack_frames(c, first_fb, count, tiled, c->stream_d2h)) return -1;
         // (the packed copy is there: the copies' other streams, and the hash, wait for this)
-        if (!c->ev_pack) HIPCHK(c, hipEventCreateWithFlags(&c->ev_pack, hipEventDisableTiming));
+        HIPCHK(c, c->ev_pack.ensure());
         HIPCHK(c, hipEventRecord(c->ev_pack, c->stream_d2h));
-        for (int k = 1; k < pieces; k++) {
-            if (!c->stream_d2h_more[k - 1]) {
-                HIPCHK(c, hipStreamCreateWithFlags(&c->stream_d2h_more[k - 1], hipStreamNonBlocking));
-                HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2h_more[k - 1], hipEventDisableTiming));
-            }
-            const int at = k * per, n = count - at < per ? count - at : per;
-            if (n < 1) break;
-            HIPCHK(c, hipStreamWaitEvent(c->stream_d2h_more[k - 1], c->ev_pack, 0));
-            HIPCHK(c, hipMemcpyAsync(dst + fbytes * (size_t)at, c->d_i420 + fbytes * (size_t)at, fbytes * (size_t)n, hipMemcpyDeviceToHost, c->stream_d2h_more[k - 1]));
-            HIPCHK(c, hipEventRecord(c->ev_d2h_more[k - 1], c->stream_d2h_more[k - 1]));
-        }
-        HIPCHK(c, hipMemcpyAsync(dst, c->d_i420, fbytes * (size_t)(per < count ? per : count), hipMemcpyDeviceToHost, c->stream_d2h));
-        for (int k = 1; k < pieces && k * per < count; k++) HIPCHK(c, hipStreamWaitEvent(c->stream_d2h, c->ev_d2h_more[k - 1], 0));
-    } else if (dst) {
-        if (tiled) {
-            // (the pass is bound by PCIe, not by the device: a workgroup per CU keeps the link full and leaves the SIMDs to the
-            // launches that run beside it)
-            long units = (long)c->dg.mb_rows * count;
-            const long cap = c->knobs.download_blocks > 0 ? c->knobs.download_blocks : c->num_cu;
-            if (units > cap) units = cap;
-            hipLaunchKernelGGL(vp8_detile_run_kernel, dim3((unsigned)units), dim3(256), 0, c->stream_d2h, (const uint8_t *)c->fb_tiles[(size_t)first_fb],
-                               c->tile_frame, dst, c->fb_stride, count, c->dg);
-            HIPCHK(c, hipGetLastError());
-        } else {
-            // (a copy is one copy engine's work: 25-33 GB/s; in pieces on streams of their own the link's other engines take part)
-            const int pieces = count >= 64 ? c->knobs.d2h_streams : 1;
-            const int per = (count + pieces - 1) / pieces;
-            for (int k = 1; k < pieces; k++) {
-                if (!c->stream_d2h_more[k - 1]) {
-                    HIPCHK(c, hipStreamCreateWithFlags(&c->stream_d2h_more[k - 1], hipStreamNonBlocking));
-                    HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2h_more[k - 1], hipEventDisableTiming));
-                }
-                const int at = k * per, n = count - at < per ? count - at : per;
-                if (n < 1) break;
-                HIPCHK(c, hipStreamWaitEvent(c->stream_d2h_more[k - 1], c->ev_d2h_from, 0));
-                HIPCHK(c, hipMemcpyAsync(dst + c->fb_stride * (size_t)at, c->fb[first_fb + at], c->fb_stride * (size_t)n, hipMemcpyDeviceToHost, c->stream_d2h_more[k - 1]));
-                HIPCHK(c, hipEventRecord(c->ev_d2h_more[k - 1], c->stream_d2h_more[k - 1]));
-            }
-            HIPCHK(c, hipMemcpyAsync(dst, c->fb[first_fb], c->fb_stride * (size_t)(per < count ? per : count), hipMemcpyDeviceToHost, c->stream_d2h));
-            for (int k = 1; k < pieces && k * per < count; k++) HIPCHK(c, hipStreamWaitEvent(c->stream_d2h, c->ev_d2h_more[k - 1], 0));
-        }
-    }
+        if (d2h_copy(c, dst, c->d_i420, fbytes, count, c->ev_pack)) return -1;
+    } else if (dst && tiled) {
+        // (the pass is bound by PCIe, not by the device: a workgroup per CU keeps the link full and leaves the SIMDs to the
+        // launches that run beside it)
+        long units = (long)c->dg.mb_rows * count;
+        const long cap = c->knobs.download_blocks > 0 ? c->knobs.download_blocks : c->num_cu;
+        if (units > cap) units = cap;
+        hipLaunchKernelGGL(vp8_detile_run_kernel, dim3((unsigned)units), dim3(256), 0, c->stream_d2h, (const uint8_t *)c->fb_tiles[(size_t)first_fb],
+                           c->tile_frame, dst, c->fb_stride, count, c->dg);
+        HIPCHK(c, hipGetLastError());
+    } else if (dst && d2h_copy(c, dst, c->fb[first_fb], c->fb_stride, count, c->ev_d2h_from))
+        return -1;
     if (digests) {
-        if (c->md5_cap < count) {
-            HIPCHK(c, hipStreamSynchronize(c->stream_d2h));
-            if (c->d_md5) (void)hipFree(c->d_md5);
-            c->d_md5 = nullptr; c->md5_cap = 0;
-            HIPCHK(c, hipMalloc((void **)&c->d_md5, 16 * (size_t)(count < 64 ? 64 : count)));
-            c->md5_cap = count < 64 ? 64 : count;
-        }
+        if (digest_room(c, count, false)) return -1;
         // a frame per lane: the frames' hashes run side by side -- and, when the frames themselves are asked for as well, BESIDE their
         // copy, on a stream of their own: a hash is 70-90 ms whatever the batch, a fifth of what 4096 1080p frames take over the link
         hipStream_t ms = c->stream_d2h;
         if (dst) {
-            if (!c->stream_d2h_more[2]) {
-                HIPCHK(c, hipStreamCreateWithFlags(&c->stream_d2h_more[2], hipStreamNonBlocking));
-                HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2h_more[2], hipEventDisableTiming));
-            }
+            if (d2h_side_stream(c, 2)) return -1;
             ms = c->stream_d2h_more[2];
             HIPCHK(c, hipStreamWaitEvent(ms, c->ev_d2h_from, 0));
         }
@@ -780,40 +744,15 @@ static int fetch_impl(vp8hip_ctx *c, int first_fb, int count, uint8_t *dst, uint
         // frames were packed for the download anyway the copy is there; else it is made if the device has the room (3.1 MB a frame).
         bool from_packed = tiled && whole_blocks && dst && packed;
         if (tiled && whole_blocks && !dst && count >= c->knobs.md5_pack_from) {
-            const size_t fbytes = vp8hip_i420_bytes(c);
-            if (fbytes * (size_t)count > c->i420_cap) {
-                HIPCHK(c, hipStreamSynchronize(c->stream_d2h));
-                if (c->d_i420) (void)hipFree(c->d_i420);
-                c->d_i420 = nullptr; c->i420_cap = 0;
-                if (hipMalloc((void **)&c->d_i420, fbytes * (size_t)count + 256) == hipSuccess) c->i420_cap = fbytes * (size_t)count;
-                else { (void)hipGetLastError(); c->d_i420 = nullptr; }
-            }
-            if (c->d_i420 && fbytes * (size_t)count <= c->i420_cap) {
-                long units = (long)count * c->dg.mb_rows;
-                if (units > 16L * c->num_cu) units = 16L * c->num_cu;
-                hipLaunchKernelGGL(vp8_pack_i420_tiles_kernel, dim3((unsigned)units), dim3(256), 0, ms, (const uint8_t *)c->fb_tiles[(size_t)first_fb],
-                                   c->tile_frame, c->d_i420, fbytes, count, c->dg, c->width, c->height);
-                HIPCHK(c, hipGetLastError());
+            if (packed_staging(c, count, false)) return -1;
+            if (fbytes * (size_t)count <= c->d_i420.cap) {
+                if (pack_frames(c, first_fb, count, true, ms)) return -1;
                 from_packed = true;
             }
         }
-        if (from_packed) {
-            // (the hash kernel of a packed batch download runs on a stream of its own: behind the pack pass)
-            if (dst) HIPCHK(c, hipStreamWaitEvent(ms, c->ev_pack, 0));
-            DevGeom pg = c->dg;
-            const int cw = c->width / 2, ch = (c->height + 1) / 2;
-            pg.y_off = 0; pg.y_stride = c->width; pg.uv_stride = cw;
-            pg.u_off = c->width * c->height; pg.v_off = pg.u_off + cw * ch;
-            hipLaunchKernelGGL(vp8_md5_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ms, (const uint8_t *)c->d_i420, vp8hip_i420_bytes(c),
-                               (const int *)nullptr, 0, count, pg, c->width, c->height, c->d_md5);
-        } else if (tiled)
-            hipLaunchKernelGGL(vp8_md5_tiles_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ms,
-                               (const uint8_t *)c->tile_block, c->tile_frame, (const int *)nullptr, first_fb, count, c->dg, c->width, c->height, c->d_md5);
-        else
-            hipLaunchKernelGGL(whole_blocks ? vp8_md5_kernel : vp8_md5_any_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ms,
-                               (const uint8_t *)c->fb_block, c->fb_stride, (const int *)nullptr, first_fb, count, c->dg, c->width, c->height, c->d_md5);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(digests, c->d_md5, 16 * (size_t)count, hipMemcpyDeviceToHost, ms));
+        // (the hash kernel of a packed batch download runs on a stream of its own: behind the pack pass)
+        if (from_packed && dst) HIPCHK(c, hipStreamWaitEvent(ms, c->ev_pack, 0));
+        if (hash_frames(c, from_packed ? HASH_PACKED : tiled ? HASH_TILES : HASH_RASTER, nullptr, first_fb, count, digests, ms)) return -1;
         if (dst) {
             HIPCHK(c, hipEventRecord(c->ev_d2h_more[2], ms));
             HIPCHK(c, hipStreamWaitEvent(c->stream_d2h, c->ev_d2h_more[2], 0));
@@ -852,48 +791,17 @@ extern "C" int vp8hip_frames_md5_list_async(vp8hip_ctx *c, const int *fbs, int n
     for (int i = 0; i < n; i++)
         if (fbs[i] < 0 || fbs[i] >= (int)c->fb.size()) return fail(c, -2, "vp8hip_frames_md5_list_async: frame buffer %d out of range", fbs[i]);
     HIPCHK(c, hipSetDevice(c->device));
-    const bool whole_blocks = (c->width & 127) == 0;
-    bool tiled = c->tile_block != nullptr && whole_blocks;
+    bool tiled = c->tile_block != nullptr && md5_whole_blocks(c);
     for (int i = 0; i < n && tiled; i++) tiled = (c->fb_state[(size_t)fbs[i]] & FB_TILES) != 0;
     if (!tiled && (vp8hip_raster_pool(c) || vp8hip_need_raster_list(c, fbs, n))) return -1;
-    if (!c->stream_d2h) {
-        int prio_least = 0, prio_greatest = 0;
-        HIPCHK(c, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-        HIPCHK(c, hipStreamCreateWithPriority(&c->stream_d2h, hipStreamNonBlocking, c->knobs.d2h_prio ? prio_least : 0));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2h_from, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_d2h_done, hipEventDisableTiming));
-    }
+    if (d2h_stream(c)) return -1;
     if (c->d2h_count) HIPCHK(c, hipEventSynchronize(c->ev_d2h_done));  // one fetch in flight at a time
-    if (c->md5_cap < n || c->md5_idx_cap < n) {
-        HIPCHK(c, hipStreamSynchronize(c->stream_d2h));
-        const int cap = n < 64 ? 64 : n;
-        if (c->md5_cap < n) {
-            if (c->d_md5) (void)hipFree(c->d_md5);
-            c->d_md5 = nullptr; c->md5_cap = 0;
-            HIPCHK(c, hipMalloc((void **)&c->d_md5, 16 * (size_t)cap));
-            c->md5_cap = cap;
-        }
-        if (c->md5_idx_cap < n) {
-            if (c->d_md5_idx) (void)hipFree(c->d_md5_idx);
-            if (c->h_md5_idx) (void)hipHostFree(c->h_md5_idx);
-            c->d_md5_idx = nullptr; c->h_md5_idx = nullptr; c->md5_idx_cap = 0;
-            HIPCHK(c, hipMalloc((void **)&c->d_md5_idx, sizeof(int) * (size_t)cap));
-            HIPCHK(c, hipHostMalloc((void **)&c->h_md5_idx, sizeof(int) * (size_t)cap, hipHostMallocDefault));
-            c->md5_idx_cap = cap;
-        }
-    }
+    if (digest_room(c, n, true)) return -1;
     memcpy(c->h_md5_idx, fbs, sizeof(int) * (size_t)n);      // (the previous fetch, which read this staging, has been waited for)
     HIPCHK(c, hipEventRecord(c->ev_d2h_from, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->stream_d2h, c->ev_d2h_from, 0));
     HIPCHK(c, hipMemcpyAsync(c->d_md5_idx, c->h_md5_idx, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream_d2h));
-    if (tiled)
-        hipLaunchKernelGGL(vp8_md5_tiles_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream_d2h, (const uint8_t *)c->tile_block,
-                           c->tile_frame, (const int *)c->d_md5_idx, 0, n, c->dg, c->width, c->height, c->d_md5);
-    else
-        hipLaunchKernelGGL(whole_blocks ? vp8_md5_kernel : vp8_md5_any_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream_d2h,
-                           (const uint8_t *)c->fb_block, c->fb_stride, (const int *)c->d_md5_idx, 0, n, c->dg, c->width, c->height, c->d_md5);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(digests, c->d_md5, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream_d2h));
+    if (hash_frames(c, tiled ? HASH_TILES : HASH_RASTER, c->d_md5_idx, 0, n, digests, c->stream_d2h)) return -1;
     HIPCHK(c, hipEventRecord(c->ev_d2h_done, c->stream_d2h));
     // (a launch that writes one of the listed frame buffers waits for this fetch)
     c->d2h_first = 0; c->d2h_count = (int)c->fb.size();

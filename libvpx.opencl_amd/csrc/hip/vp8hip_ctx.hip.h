@@ -10,6 +10,7 @@
 //                       the pool's readers vp8hip_trace_flow_async (vp8_trace.hip), vp8hip_trace_residual_async
 //                       (vp8_trace_residual.hip) and vp8hip_trace_gather_async (vp8_trace_gather.hip)
 //   vp8hip_handover.hip the checks those calls share
+// and vp8hip_res.hip.h: the owning types of the context's buffers, events and streams.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -20,6 +21,7 @@
 
 #include "vp8hip.h"
 #include "vp8_common.hip.h"
+#include "vp8hip_res.hip.h"
 
 #define VP8HIP_STATS_RING 32
 #define VP8HIP_NBUF 4          // device job tables in rotation (a launch's table may still be read while the next one is staged)
@@ -34,12 +36,12 @@
 // host staging of the same layout that a feeder fills and one copy sends.  The dense view (vp8hip_ir_map: what the oracle and
 // the tests speak) is host memory only; vp8hip_ir_upload converts it on the host.
 struct Slot {
-    vp8ir_mbx *d_mbx; int16_t *d_blocks; vp8ir_mv *d_mvs;
-    char *h_block;                                     // pinned staging, allocated on first map: same offsets as the device block
-    vp8ir_frame_hdr *h_hdr; vp8ir_mbx *h_mbx; int16_t *h_blocks; vp8ir_mv *h_mvs;
-    char *h_dense; vp8ir_mb *h_mbs; int16_t *h_coef;   // the dense view (pageable), allocated on first vp8hip_ir_map
-    vp8ir_frame_hdr hdr_copy;                          // header as of the last upload / copy / entropy launch (host side, for job setup)
-    size_t nblocks;                                    // blocks in the device stream, as far as the host knows (NBLOCKS_UNKNOWN: written on the device)
+    vp8ir_mbx *d_mbx = nullptr; int16_t *d_blocks = nullptr; vp8ir_mv *d_mvs = nullptr;
+    PinnedBuf<char> h_block;                           // pinned staging, allocated on first map: same offsets as the device block
+    vp8ir_frame_hdr *h_hdr = nullptr; vp8ir_mbx *h_mbx = nullptr; int16_t *h_blocks = nullptr; vp8ir_mv *h_mvs = nullptr;
+    HeapBuf<char> h_dense; vp8ir_mb *h_mbs = nullptr; int16_t *h_coef = nullptr;   // the dense view (pageable), allocated on first vp8hip_ir_map
+    vp8ir_frame_hdr hdr_copy = {};                     // header as of the last upload / copy / entropy launch (host side, for job setup)
+    size_t nblocks = 0;                                // blocks in the device stream, as far as the host knows (NBLOCKS_UNKNOWN: written on the device)
 };
 #define NBLOCKS_UNKNOWN ((size_t)-1)
 
@@ -56,31 +58,45 @@ struct Slot {
 //                              ms; 128: 1.56 -> 1.45) and costs throughput in launches that fill the chip anyway (512: 3.82 -> 4.03)
 #define VP8HIP_TILE_FRONT 4096
 struct Knobs {
-    int recon_force;       // 0 automatic, 1 lane-per-row, 2 wave-per-row
-    int md5_pack_from;     // VP8HIP_MD5_PACK_FROM: batches of this many tiled frames and more are hashed from a packed copy (vp8hip.hip: fetch_impl)
-    int pred_tiles;        // VP8HIP_PRED_TILES: 1 (default) a large launch whose references are all there as tiles, and not all as raster frames,
+    int recon_force = 0;   // 0 automatic, 1 lane-per-row, 2 wave-per-row
+    int md5_pack_from = 0; // VP8HIP_MD5_PACK_FROM: batches of this many tiled frames and more are hashed from a packed copy (vp8hip.hip: fetch_impl)
+    int pred_tiles = 0;    // VP8HIP_PRED_TILES: 1 (default) a large launch whose references are all there as tiles, and not all as raster frames,
                            // predicts from the tiles; 2: whenever all are there as tiles; 0: never (the raster form is made first)
-    int inter_split, eager_raster, direct_download, download_blocks, d2h_prio, d2h_streams;
-    int lgG, simt_waves, wg_per_cu, xcu, xcu_S, xcu_NW, recon_nw, lf_nw;
+    int inter_split = 0, eager_raster = 0, direct_download = 0, download_blocks = 0, d2h_prio = 0, d2h_streams = 0;
+    int lgG = 0, simt_waves = 0, wg_per_cu = 0, xcu = 0, xcu_S = 0, xcu_NW = 0, recon_nw = 0, lf_nw = 0;
 };
 
+// WHO OWNS WHAT.  Every buffer, event and stream of a context is a member of an owning type (vp8hip_res.hip.h): deleting the
+// context -- vp8hip_destroy, a failure in vp8hip_create -- gives all of it back, and nothing is freed by hand anywhere.  Members
+// are destroyed last to first, so the streams come first here: buffers and events go while the streams still exist, the main
+// stream goes last.  A buffer that grows does so through Buf::grow, behind the wait its call site makes.
+// WHAT SURVIVES A RECONFIGURATION.  vp8hip_configure gives back what is shaped by the geometry or the counts (free_pools in
+// vp8hip.hip): the raster, tile and block pools, the slots with their stagings, the granule buffers and the intra flags.
+// Everything else stays and is reused: job and conversion tables, digest buffers, the packed staging and the RGB scratch (caches:
+// vp8hip_drop_staging), the entropy decoder's input sets, the MFQE and visualizer stagings, all streams and events -- and the
+// post-processing tables with pp_rv_loaded: the caller's noise state outlives a reconfiguration too (vp8/common/postproc.c keeps
+// postproc_state.noise across vp8_alloc_frame_buffers) and only sends the noise table again when q changes.
 struct vp8hip_ctx {
-    int device;
+    int device = 0;
     Knobs knobs;
-    hipStream_t stream;
+    Stream stream;
+    // batch download of whole frame buffers on a stream of its own (vp8hip_frames_download_async): PCIe is full duplex, the next
+    // batch's uploads run beside it; in up to four pieces on streams of their own (a copy engine each)
+    Stream stream_d2h, stream_d2h_more[3];
+    Stream stream_h2d;             // vp8hip_entropy_decode: a launch's input
     // timing events of the last VP8HIP_STATS_RING launches: [0..3] on the main stream around recon / loop filter /
     // extend, [4..5] around the tiled -> raster pass on whichever stream it ran
-    hipEvent_t evr[VP8HIP_STATS_RING][6];
-    bool evr_tiled[VP8HIP_STATS_RING]; vp8hip_stats evr_stats[VP8HIP_STATS_RING];
-    long ncalls;
-    hipEvent_t ev_jobs2[VP8HIP_NBUF];   // the job table staged in h_jobs2[k] has been copied
-    int parity;                    // job table used by the next launch
-    char err[256];
+    Event evr[VP8HIP_STATS_RING][6];
+    bool evr_tiled[VP8HIP_STATS_RING] = {}; vp8hip_stats evr_stats[VP8HIP_STATS_RING] = {};
+    long ncalls = 0;
+    Event ev_jobs2[VP8HIP_NBUF];   // the job table staged in h_jobs2[k] has been copied
+    int parity = 0;                // job table used by the next launch
+    char err[256] = "";
     // geometry
-    int width, height;
-    vp8ir_geom geom;
-    DevGeom dg;
-    int nmb;
+    int width = 0, height = 0;
+    vp8ir_geom geom = {};
+    DevGeom dg = {};
+    int nmb = 0;
     // pools.  A frame buffer has TWO forms on the device (vp8hip_launch.hip): the raster form -- the reference's YV12 layout with
     // its borders, fb[i] -- and the tiled form the lane-per-row kernels write -- macroblock-window tiles, fb_tiles[i], allocated
     // with the first large launch --, and fb_state[i] says which of them hold the frame.  Whoever needs a form the frame is not
@@ -88,58 +104,55 @@ struct vp8hip_ctx {
     std::vector<uint8_t *> fb, fb_tiles;
     std::vector<uint8_t> fb_state;
     std::vector<Slot> slots;
-    uint8_t *fb_block; char *slot_block_dev;
-    uint8_t *tile_block; size_t tile_frame;          // the tiled forms of all frame buffers (tile_frame bytes each) + the dummy tile
-    uint8_t *tile_alloc;                             // ... as allocated: VP8HIP_TILE_FRONT bytes in front of tile_block (the tile-reading predictor's loads left of a tile row)
-    DevJob *d_conv_jobs, *h_conv_jobs; int conv_cap; hipEvent_t ev_conv;    // job table of a tiled -> raster pass
-    size_t slot_bytes, o_mbx, o_blocks, o_mvs, cap_blocks;            // slot layout; cap_blocks = nmb * 24 (pooled: 0)
+    DevBuf<uint8_t> fb_block; DevBuf<char> slot_block_dev;
+    uint8_t *tile_block = nullptr; size_t tile_frame = 0;   // the tiled forms of all frame buffers (tile_frame bytes each) + the dummy tile
+    DevBuf<uint8_t> tile_alloc;                      // ... as allocated: VP8HIP_TILE_FRONT bytes in front of tile_block (the tile-reading predictor's loads left of a tile row)
+    DevBuf<DevJob> d_conv_jobs; PinnedBuf<DevJob> h_conv_jobs; Event ev_conv;    // job table of a tiled -> raster pass
+    size_t slot_bytes = 0, o_mbx = 0, o_blocks = 0, o_mvs = 0, cap_blocks = 0;   // slot layout; cap_blocks = nmb * 24 (pooled: 0)
     // vp8hip_configure_pooled: the slots have no block streams of their own; the device's entropy decoder takes the blocks' room out
     // of this pool, chunk_blocks blocks at a time (pool_chunks chunks + one that takes what no longer fits); *d_pool_ctr = chunks taken
-    char *pool; unsigned int *d_pool_ctr; unsigned int pool_chunks, chunk_blocks;
+    DevBuf<char> pool; DevBuf<unsigned int> d_pool_ctr; unsigned int pool_chunks = 0, chunk_blocks = 0;
     // job staging
     // (device tables and page-locked stagings in rotation: a caller may queue VP8HIP_NBUF launches before it has to wait for the
     // device to have taken the first one's table -- behind an entropy launch of a quarter of a second, say)
-    DevJob *d_jobs2[VP8HIP_NBUF]; DevJob *h_jobs2[VP8HIP_NBUF]; DevJob *d_jobs; DevJob *h_jobs; int jobs_cap;   // d_jobs / h_jobs = those of the call
+    DevBuf<DevJob> d_jobs2[VP8HIP_NBUF]; PinnedBuf<DevJob> h_jobs2[VP8HIP_NBUF]; DevJob *d_jobs = nullptr, *h_jobs = nullptr;   // d_jobs / h_jobs = those of the call
     // launch configuration
-    int num_cu, max_lds;
-    int recon_nw, lf_nw;
-    size_t recon_lds, lf_lds;
-    vp8hip_stats stats;
+    int num_cu = 0, max_lds = 0;
+    int recon_nw = 0, lf_nw = 0;
+    size_t recon_lds = 0, lf_lds = 0;
+    vp8hip_stats stats = {};
     // Small launches spread every frame pair over several CUs (vp8_recon_xcu_kernel / vp8_loopfilter_xcu_kernel): granule
-    // buffers of the row-to-row hand-over, the launch counter that tags the granules, and the status word a kernel
-    // sets (host-mapped memory) when a hand-over does not arrive
-    unsigned long long *gran_recon, *gran_lf; size_t gran_recon_cap, gran_lf_cap;
-    unsigned int epoch;
-    int *h_status, *d_status;
-    // batch download of whole frame buffers on a stream of its own (vp8hip_frames_download_async): PCIe is full duplex, the next
-    // batch's uploads run beside it
-    hipStream_t stream_d2h;
-    uint8_t *d_i420; size_t i420_cap; hipEvent_t ev_pack;     // vp8hip_frames_fetch_i420_async: the batch as packed I420, before it leaves
-    uint8_t *d_rgb; size_t rgb_cap;                           // vp8hip_frames_rgb_async: a chunk of frames as packed I420 at the scaled size (a cache)
-    hipStream_t stream_d2h_more[3]; hipEvent_t ev_d2h_more[3];      // a batch download in up to four pieces on streams of their own (a copy engine each)
-    hipEvent_t ev_d2h_from, ev_d2h_done;
-    int d2h_first, d2h_count;      // frame buffers of the copy in flight (count 0: none)
-    std::vector<uint8_t> d2h_mask; bool d2h_listed;     // ... of a fetch by list (vp8hip_frames_md5_list_async): a flag per frame buffer
-    uint8_t *d_md5; int md5_cap;   // vp8hip_frames_fetch_async: the batch's digests on the device
-    int *d_md5_idx, *h_md5_idx; int md5_idx_cap;    // vp8hip_frames_md5_list_async: which frame buffers
-    size_t fb_stride;
-    unsigned int *d_intra_flags; int intra_flags_cap;       // per job of a launch: the frame has intra macroblocks (vp8_inter_mb_kernel)
+    // buffers of the row-to-row hand-over (capacities in bytes), the launch counter that tags the granules, and the status word a
+    // kernel sets (host-mapped memory) when a hand-over does not arrive
+    DevBuf<unsigned long long> gran_recon, gran_lf;
+    unsigned int epoch = 0;
+    MappedBuf<int> h_status; int *d_status = nullptr;
+    DevBuf<uint8_t> d_i420; Event ev_pack;           // vp8hip_frames_fetch_i420_async: the batch as packed I420, before it leaves (capacity in bytes, 256 more are there)
+    DevBuf<uint8_t> d_rgb;                           // vp8hip_frames_rgb_async: a chunk of frames as packed I420 at the scaled size (a cache)
+    Event ev_d2h_more[3];                            // the piece on stream_d2h_more[k] has left
+    Event ev_d2h_from, ev_d2h_done;
+    int d2h_first = 0, d2h_count = 0;  // frame buffers of the copy in flight (count 0: none)
+    std::vector<uint8_t> d2h_mask; bool d2h_listed = false;     // ... of a fetch by list (vp8hip_frames_md5_list_async): a flag per frame buffer
+    DevBuf<uint8_t> d_md5;         // vp8hip_frames_fetch_async: the batch's digests on the device (capacity in digests)
+    DevBuf<int> d_md5_idx; PinnedBuf<int> h_md5_idx;    // vp8hip_frames_md5_list_async: which frame buffers
+    size_t fb_stride = 0;
+    DevBuf<unsigned int> d_intra_flags;              // per job of a launch: the frame has intra macroblocks (vp8_inter_mb_kernel)
     // vp8hip_postproc: dither table (440 shorts), noise table (3072) and per-row noise phases (16384) on the device
-    char *d_pp, *h_pp; bool pp_rv_loaded; hipEvent_t ev_pp;
-    uint8_t *d_mfqe, *h_mfqe; int mfqe_cap; hipEvent_t ev_mfqe;     // vp8hip_mfqe: the macroblock classes of the frame
-    char *d_vis, *h_vis; hipEvent_t ev_vis;         // vp8hip_visualize: the frame-info and rate strings on their way to the device
+    DevBuf<char> d_pp; PinnedBuf<char> h_pp; bool pp_rv_loaded = false; Event ev_pp;
+    DevBuf<uint8_t> d_mfqe; PinnedBuf<uint8_t> h_mfqe; Event ev_mfqe;     // vp8hip_mfqe: the macroblock classes of the frame
+    DevBuf<char> d_vis; PinnedBuf<char> h_vis; Event ev_vis;         // vp8hip_visualize: the frame-info and rate strings on their way to the device
     // vp8hip_entropy_decode: the frames' descriptions, their bytes, per-frame scratch and status on the device; the stream the
-    // launch runs on (its own: beside the pixel path of other slots) and the events that order it against the main stream
-    // (descriptions and bytes in TWO sets: a launch's input is copied on a stream of its own, stream_h2d, while the launch before
+    // launch's input is copied on (stream_h2d: beside the pixel path of other slots) and the events that order it against the main
+    // stream (descriptions and bytes in TWO sets, capacities in bytes: a launch's input is copied while the launch before
     // and its frames' pixel path still run -- 3 to 5 GB per launch of 24,576 1080p frames; ev_ent_in[k]: set k's copies have landed,
     // ev_ent_out[k]: the kernel that read set k is done)
-    char *d_ent_frames2[2], *d_ent_data2[2]; size_t ent_frames_cap2[2], ent_data_cap2[2]; int ent_set;
-    hipStream_t stream_h2d; hipEvent_t ev_ent_in[2], ev_ent_out[2];
-    unsigned int *d_ent_scratch, *d_ent_status; size_t ent_status_cap, ent_scratch_cap; int ent_last_count;
-    struct { int count, set, np; const vp8hip_entropy_frame *frames; size_t data_bytes; } ent_staged;    // input sent, kernel not yet launched (count 0: none)
-    bool ent_tables_loaded, ent_parts_off; int ent_lpw;
-    int ent_resident[3];           // waves of vp8_entropy_kernel the device holds at once with 64 / 32 / 16 lanes carrying a frame (LDS)
-    unsigned int *d_sched;         // vp8_keyframe_kernel's role / work counters
+    DevBuf<char> d_ent_frames2[2]; DevBuf<uint8_t> d_ent_data2[2]; int ent_set = 0;
+    Event ev_ent_in[2], ev_ent_out[2];
+    DevBuf<unsigned int> d_ent_scratch, d_ent_status; int ent_last_count = 0;
+    struct { int count = 0, set = 0, np = 0; const vp8hip_entropy_frame *frames = nullptr; size_t data_bytes = 0; } ent_staged;    // input sent, kernel not yet launched (count 0: none)
+    bool ent_tables_loaded = false, ent_parts_off = false; int ent_lpw = 0;
+    int ent_resident[3] = {};      // waves of vp8_entropy_kernel the device holds at once with 64 / 32 / 16 lanes carrying a frame (LDS)
+    DevBuf<unsigned int> d_sched;  // vp8_keyframe_kernel's role / work counters
 };
 
 int vp8hip_fail(vp8hip_ctx *c, int code, const char *fmt, ...);

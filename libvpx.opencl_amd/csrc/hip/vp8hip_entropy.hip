@@ -39,19 +39,13 @@ extern "C" int vp8hip_entropy_decode(vp8hip_ctx *c, int first_slot, int count, c
     c->ent_staged.count = 0;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t swords = np > 1 ? (size_t)count * ((size_t)c->dg.mb_cols + 3 * (size_t)c->nmb) : (size_t)count * (8 * (size_t)c->dg.mb_cols + 64);
-    if ((size_t)count > c->ent_status_cap) {
+    if ((size_t)count > c->d_ent_status.cap) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_ent_status) (void)hipFree(c->d_ent_status);
-        c->d_ent_status = nullptr; c->ent_status_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_ent_status, (size_t)count * 4));
-        c->ent_status_cap = (size_t)count;
+        HIPCHK(c, c->d_ent_status.grow((size_t)count));
     }
-    if (swords > c->ent_scratch_cap) {
+    if (swords > c->d_ent_scratch.cap) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_ent_scratch) (void)hipFree(c->d_ent_scratch);
-        c->d_ent_scratch = nullptr; c->ent_scratch_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_ent_scratch, swords * 4));
-        c->ent_scratch_cap = swords;
+        HIPCHK(c, c->d_ent_scratch.grow(swords));
     }
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ent_in[set], 0));
     for (int i = 0; i < count; i++) {
@@ -96,29 +90,20 @@ static int entropy_stage(vp8hip_ctx *c, int count, const vp8hip_entropy_frame *f
     }
     if (c->dg.mb_cols < np || c->dg.mb_cols > 256 || c->dg.mb_cols * (64 / np) > 4096 || c->ent_parts_off || any_inter) np = 1;
     if (c->pool) np = 1;           // (the partition-per-lane kernel gives every partition a worst-case region of the slot's own stream)
-    if (!c->stream_h2d) {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->stream_h2d, hipStreamNonBlocking));
-        for (int k = 0; k < 2; k++) {
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_ent_in[k], hipEventDisableTiming));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_ent_out[k], hipEventDisableTiming));
-        }
+    HIPCHK(c, c->stream_h2d.ensure());
+    for (int k = 0; k < 2; k++) {
+        HIPCHK(c, c->ev_ent_in[k].ensure());
+        HIPCHK(c, c->ev_ent_out[k].ensure());
     }
     const int set = c->ent_set;
     c->ent_set ^= 1;
-    if (fbytes > c->ent_frames_cap2[set]) {
+    if (fbytes > c->d_ent_frames2[set].cap) {
         HIPCHK(c, hipEventSynchronize(c->ev_ent_out[set]));          // (the launch that read this set)
-        if (c->d_ent_frames2[set]) (void)hipFree(c->d_ent_frames2[set]);
-        c->d_ent_frames2[set] = nullptr; c->ent_frames_cap2[set] = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_ent_frames2[set], fbytes));
-        c->ent_frames_cap2[set] = fbytes;
+        HIPCHK(c, c->d_ent_frames2[set].grow(fbytes));
     }
-    if (data_bytes + 16 > c->ent_data_cap2[set]) {
+    if (data_bytes + 16 > c->d_ent_data2[set].cap) {
         HIPCHK(c, hipEventSynchronize(c->ev_ent_out[set]));
-        if (c->d_ent_data2[set]) (void)hipFree(c->d_ent_data2[set]);
-        c->d_ent_data2[set] = nullptr; c->ent_data_cap2[set] = 0;
-        const size_t cap = data_bytes + data_bytes / 4 + 4096;
-        HIPCHK(c, hipMalloc((void **)&c->d_ent_data2[set], cap));
-        c->ent_data_cap2[set] = cap;
+        HIPCHK(c, c->d_ent_data2[set].grow(data_bytes + data_bytes / 4 + 4096));
     }
     // the launch's input: on the copy stream, as soon as the kernel that last read this set is done -- beside whatever the context's
     // stream still has to do before this launch
@@ -156,11 +141,11 @@ static int entropy_launch(vp8hip_ctx *c, int first_slot, int count, int set, int
     }
     if (np > 1)
         hipLaunchKernelGGL(vp8_entropy_parts_kernel, dim3((unsigned)((count + 64 / np - 1) / (64 / np))), dim3(64), 0, c->stream,
-                           (const vp8hip_entropy_frame *)c->d_ent_frames2[set], count, np, (const uint8_t *)c->d_ent_data2[set], c->dg, data_bytes,
+                           (const vp8hip_entropy_frame *)c->d_ent_frames2[set].p, count, np, (const uint8_t *)c->d_ent_data2[set], c->dg, data_bytes,
                            c->slot_block_dev, c->slot_bytes, c->o_mbx, c->o_blocks, first_slot, c->d_ent_scratch, c->d_ent_status);
     else
         hipLaunchKernelGGL(vp8_entropy_kernel, dim3((unsigned)((count + lpw - 1) / lpw)), dim3(64), vp8_entropy_lds_bytes(lpw), c->stream,
-                           (const vp8hip_entropy_frame *)c->d_ent_frames2[set], count, lpw, (const uint8_t *)c->d_ent_data2[set], c->dg, data_bytes,
+                           (const vp8hip_entropy_frame *)c->d_ent_frames2[set].p, count, lpw, (const uint8_t *)c->d_ent_data2[set], c->dg, data_bytes,
                            c->slot_block_dev, c->slot_bytes, c->o_mbx, c->o_blocks, c->o_mvs, first_slot, c->d_ent_scratch, c->d_ent_status,
                            c->pool, c->d_pool_ctr, c->pool_chunks, c->chunk_blocks);
     HIPCHK(c, hipGetLastError());

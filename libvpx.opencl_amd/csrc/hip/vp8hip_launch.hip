@@ -54,15 +54,11 @@ static int convert_list(vp8hip_ctx *c, const int *fbs, int n, bool to_tiles)
     for (int i = 0; i < n; i++) m += c->fb_state[(size_t)fbs[i]] == lacks;
     if (!m) return 0;
     if (to_tiles ? tile_pool(c) : vp8hip_raster_pool(c)) return -1;
-    if (m > c->conv_cap) {
+    if ((size_t)m > vp8hip_cap(c->d_conv_jobs, c->h_conv_jobs)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_conv_jobs) (void)hipFree(c->d_conv_jobs);
-        if (c->h_conv_jobs) (void)hipHostFree(c->h_conv_jobs);
-        c->d_conv_jobs = c->h_conv_jobs = nullptr; c->conv_cap = 0;
-        const int cap = m < 64 ? 64 : m;
-        HIPCHK(c, hipMalloc((void **)&c->d_conv_jobs, sizeof(DevJob) * (size_t)cap));
-        HIPCHK(c, hipHostMalloc((void **)&c->h_conv_jobs, sizeof(DevJob) * (size_t)cap, hipHostMallocDefault));
-        c->conv_cap = cap;
+        const size_t cap = m < 64 ? 64 : (size_t)m;
+        HIPCHK(c, c->d_conv_jobs.grow(cap));
+        HIPCHK(c, c->h_conv_jobs.grow(cap));
     } else
         HIPCHK(c, hipEventSynchronize(c->ev_conv));           // the table of the pass before has been copied
     m = 0;
@@ -127,16 +123,11 @@ static int tile_pool(vp8hip_ctx *c)
 {
     if (c->tile_block) return 0;
     const int nfb = (int)c->fb.size();
-    hipError_t e = hipMalloc((void **)&c->tile_alloc, c->tile_frame * (size_t)nfb + 8192 + VP8HIP_TILE_FRONT);
-    if (e != hipSuccess && vp8hip_drop_staging(c) == 1) {       // (the packed staging is a cache: vp8hip.hip)
-        (void)hipGetLastError();
-        e = hipMalloc((void **)&c->tile_alloc, c->tile_frame * (size_t)nfb + 8192 + VP8HIP_TILE_FRONT);
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        c->tile_alloc = nullptr;
+    const size_t bytes = c->tile_frame * (size_t)nfb + 8192 + VP8HIP_TILE_FRONT;
+    hipError_t e = c->tile_alloc.grow(bytes);
+    if (e != hipSuccess && vp8hip_drop_staging(c) == 1) e = c->tile_alloc.grow(bytes);       // (the packed staging is a cache: vp8hip.hip)
+    if (e != hipSuccess)
         return fail(c, -1, "no device memory for the tiled form of %d frame buffers (%zu MB)", nfb, c->tile_frame * (size_t)nfb >> 20);
-    }
     c->tile_block = c->tile_alloc + VP8HIP_TILE_FRONT;
     c->fb_tiles.resize((size_t)nfb);
     for (int i = 0; i < nfb; i++) c->fb_tiles[(size_t)i] = c->tile_block + c->tile_frame * (size_t)i;
@@ -159,18 +150,19 @@ extern "C" int vp8hip_decode(vp8hip_ctx *c, const vp8hip_job *jobs, int njobs, i
     if (!c || !jobs || njobs <= 0) return fail(c, -2, "vp8hip_decode: bad arguments");
     if (!c->width) return fail(c, -2, "vp8hip_decode: context not configured");
     HIPCHK(c, hipSetDevice(c->device));
-    if (njobs > c->jobs_cap) {
-        // the staging arrays are reused by in-flight launches: drain before growing
+    size_t jobs_cap = vp8hip_cap(c->d_jobs2[0], c->h_jobs2[0]);       // what the smallest of the eight tables holds
+    for (int k = 1; k < VP8HIP_NBUF; k++) {
+        const size_t cap_k = vp8hip_cap(c->d_jobs2[k], c->h_jobs2[k]);
+        if (cap_k < jobs_cap) jobs_cap = cap_k;
+    }
+    if ((size_t)njobs > jobs_cap) {
+        // the staging arrays are reused by in-flight launches: drain before growing.  (After a failure part-way the table that
+        // failed holds nothing, so the next launch of any size takes this path again; the tables that did grow stay.)
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        const size_t cap = njobs < 64 ? 64 : (size_t)njobs;
         for (int k = 0; k < VP8HIP_NBUF; k++) {
-            if (c->d_jobs2[k]) (void)hipFree(c->d_jobs2[k]);
-            if (c->h_jobs2[k]) (void)hipHostFree(c->h_jobs2[k]);
-            c->d_jobs2[k] = nullptr; c->h_jobs2[k] = nullptr;
-        }
-        c->jobs_cap = njobs < 64 ? 64 : njobs;
-        for (int k = 0; k < VP8HIP_NBUF; k++) {
-            HIPCHK(c, hipMalloc((void **)&c->d_jobs2[k], sizeof(DevJob) * c->jobs_cap));
-            HIPCHK(c, hipHostMalloc((void **)&c->h_jobs2[k], sizeof(DevJob) * c->jobs_cap, hipHostMallocDefault));
+            HIPCHK(c, c->d_jobs2[k].grow(cap));
+            HIPCHK(c, c->h_jobs2[k].grow(cap));
         }
     } else {
         // this call's staging was read by the copy of the call VP8HIP_NBUF calls ago; wait for that copy only
@@ -293,34 +285,32 @@ extern "C" int vp8hip_decode(vp8hip_ctx *c, const vp8hip_job *jobs, int njobs, i
         if (S > 1) {
             xcu_S = S; xcu_grid = 8 * S * per_xcd;
             if (!c->h_status) {
-                HIPCHK(c, hipHostMalloc((void **)&c->h_status, sizeof(int), hipHostMallocMapped));
+                HIPCHK(c, c->h_status.grow(1));
                 *c->h_status = 0;
                 HIPCHK(c, hipHostGetDevicePointer((void **)&c->d_status, c->h_status, 0));
             }
             // granule buffers: recon one unfiltered pixel line per MB row (cols*8+2 granules), loop filter four
             // context rows per MB row (cols*32), per frame; zeroed once -- the tags of later launches never repeat
             const size_t need_r = (size_t)npairs * 2 * rows * (cols * 8 + 2) * 8, need_l = (size_t)npairs * 2 * rows * cols * 32 * 8;
-            if (c->gran_recon_cap < need_r || c->gran_lf_cap < need_l) {
+            if (c->gran_recon.cap < need_r || c->gran_lf.cap < need_l) {
+                // (both anew, zeroed: the tags start over)
                 HIPCHK(c, hipStreamSynchronize(c->stream));
-                if (c->gran_recon) (void)hipFree(c->gran_recon);
-                if (c->gran_lf) (void)hipFree(c->gran_lf);
-                c->gran_recon = c->gran_lf = nullptr; c->gran_recon_cap = c->gran_lf_cap = 0;
-                HIPCHK(c, hipMalloc((void **)&c->gran_recon, need_r));
-                HIPCHK(c, hipMalloc((void **)&c->gran_lf, need_l));
+                c->gran_recon.reset(); c->gran_lf.reset();
+                HIPCHK(c, c->gran_recon.grow(need_r, need_r));
+                HIPCHK(c, c->gran_lf.grow(need_l, need_l));
                 HIPCHK(c, hipMemsetAsync(c->gran_recon, 0, need_r, c->stream));
                 HIPCHK(c, hipMemsetAsync(c->gran_lf, 0, need_l, c->stream));
-                c->gran_recon_cap = need_r; c->gran_lf_cap = need_l;
                 c->epoch = 0;
             }
             if (++c->epoch == 0) {          // 2^32 launches later: start over with clean buffers
-                HIPCHK(c, hipMemsetAsync(c->gran_recon, 0, c->gran_recon_cap, c->stream));
-                HIPCHK(c, hipMemsetAsync(c->gran_lf, 0, c->gran_lf_cap, c->stream));
+                HIPCHK(c, hipMemsetAsync(c->gran_recon, 0, c->gran_recon.cap, c->stream));
+                HIPCHK(c, hipMemsetAsync(c->gran_lf, 0, c->gran_lf.cap, c->stream));
                 c->epoch = 1;
             }
             c->stats.workgroups = xcu_grid; c->stats.recon_waves = XCU_NW; c->stats.lf_waves = XCU_NW;
         }
     }
-    hipEvent_t *ev = c->evr[c->ncalls % VP8HIP_STATS_RING];
+    const Event *ev = c->evr[c->ncalls % VP8HIP_STATS_RING];
     HIPCHK(c, hipEventRecord(ev[0], c->stream));
     // "one MB row per lane" kernels: G lanes per strand of frames, row period P = max(cols, 2G + 2).  A strand's frames follow each
     // other row after row, G rows at a time, so a launch takes ceil(frames per strand x rows / G) rounds of P steps + 2 (G - 1) to
@@ -357,7 +347,7 @@ extern "C" int vp8hip_decode(vp8hip_ctx *c, const vp8hip_job *jobs, int njobs, i
         if (tiled) {
             // one kernel, two waves per SIMD: the first to arrive on a SIMD reconstructs luma, the second chroma (see the kernel)
             if (!c->d_sched) {
-                HIPCHK(c, hipMalloc((void **)&c->d_sched, sizeof(unsigned int) * VP8HIP_SCHED_WORDS));
+                HIPCHK(c, c->d_sched.grow(VP8HIP_SCHED_WORDS));
                 HIPCHK(c, hipMemsetAsync(c->d_sched, 0, sizeof(unsigned int) * VP8HIP_SCHED_WORDS, c->stream));
             }
             HIPCHK(c, hipMemsetAsync(c->d_sched, 0, 2 * sizeof(unsigned int), c->stream));
@@ -382,12 +372,7 @@ extern "C" int vp8hip_decode(vp8hip_ctx *c, const vp8hip_job *jobs, int njobs, i
             // row-ordered kernel for the intra macroblocks only
             const bool inter_first = !all_key && njobs <= K.inter_split;
             if (inter_first) {
-                if (c->intra_flags_cap < njobs) {
-                    if (c->d_intra_flags) (void)hipFree(c->d_intra_flags);
-                    c->d_intra_flags = nullptr; c->intra_flags_cap = 0;
-                    HIPCHK(c, hipMalloc((void **)&c->d_intra_flags, sizeof(unsigned int) * (size_t)njobs));
-                    c->intra_flags_cap = njobs;
-                }
+                HIPCHK(c, c->d_intra_flags.grow((size_t)njobs));     // (launches in flight read the flags: hipFree waits for them)
                 HIPCHK(c, hipMemsetAsync(c->d_intra_flags, 0, sizeof(unsigned int) * (size_t)njobs, c->stream));
                 const long units = (long)njobs * ((c->nmb + 1) / 2);
                 long igrid = (units + 3) / 4;

@@ -39,17 +39,17 @@ extern "C" int vp8hip_postproc(vp8hip_ctx *c, int src_fb, int dst_fb, int tmp_fb
     if (!c->d_pp || !c->h_pp || !c->ev_pp) {
         // (each piece on its own: a failure half way leaves what exists for the next call, never a null event to wait on)
         if (!c->d_pp) {
-            HIPCHK(c, hipMalloc((void **)&c->d_pp, 1024 + 3072 + 16384));
+            HIPCHK(c, c->d_pp.grow(1024 + 3072 + 16384));
             HIPCHK(c, hipMemsetAsync(c->d_pp, 0, 1024 + 3072 + 16384, c->stream));     // a noise table never sent is all zeros, as the reference's
         }
         // the caller's tables go through a pinned copy of our own, so that they may be reused the moment the call returns
-        if (!c->h_pp) HIPCHK(c, hipHostMalloc((void **)&c->h_pp, 1024 + 3072 + 16384, hipHostMallocDefault));
-        if (!c->ev_pp) HIPCHK(c, hipEventCreateWithFlags(&c->ev_pp, hipEventDisableTiming));
+        HIPCHK(c, c->h_pp.grow(1024 + 3072 + 16384));
+        HIPCHK(c, c->ev_pp.ensure());
     } else
         HIPCHK(c, hipEventSynchronize(c->ev_pp));       // the previous call's copies have left the pinned staging
-    const short *d_rv = (const short *)c->d_pp;
-    signed char *d_noise = (signed char *)c->d_pp + 1024;
-    uint8_t *d_rows = (uint8_t *)c->d_pp + 1024 + 3072;
+    const short *d_rv = (const short *)c->d_pp.p;
+    signed char *d_noise = (signed char *)c->d_pp.p + 1024;
+    uint8_t *d_rows = (uint8_t *)c->d_pp.p + 1024 + 3072;
     if (vp8hip_raster_pool(c)) return -1;
     uint8_t *src = c->fb[src_fb], *dst = c->fb[dst_fb];
     const struct { int off, stride, rows, cols; } pl[3] = { { g.y_off, g.y_stride, g.aligned_h, g.aligned_w },
@@ -99,17 +99,12 @@ extern "C" int vp8hip_mfqe(vp8hip_ctx *c, int show_fb, int prev_fb, int dst_fb, 
     }
     if (c->d2h_count) { HIPCHK(c, hipEventSynchronize(c->ev_d2h_done)); c->d2h_count = 0; }   // a batch download may be reading dst
     const int nmb = c->dg.mb_cols * c->dg.mb_rows;
-    if (nmb > c->mfqe_cap) {
-        if (c->ev_mfqe) HIPCHK(c, hipEventSynchronize(c->ev_mfqe));
-        if (c->d_mfqe) (void)hipFree(c->d_mfqe);
-        if (c->h_mfqe) (void)hipHostFree(c->h_mfqe);
-        c->d_mfqe = c->h_mfqe = nullptr; c->mfqe_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_mfqe, (size_t)nmb));
-        HIPCHK(c, hipHostMalloc((void **)&c->h_mfqe, (size_t)nmb, hipHostMallocDefault));
-        c->mfqe_cap = nmb;
+    if (c->ev_mfqe) HIPCHK(c, hipEventSynchronize(c->ev_mfqe));    // the previous call's copy has left the pinned staging
+    else HIPCHK(c, c->ev_mfqe.ensure());
+    if ((size_t)nmb > vp8hip_cap(c->d_mfqe, c->h_mfqe)) {
+        HIPCHK(c, c->d_mfqe.grow((size_t)nmb));
+        HIPCHK(c, c->h_mfqe.grow((size_t)nmb));
     }
-    if (!c->ev_mfqe) HIPCHK(c, hipEventCreateWithFlags(&c->ev_mfqe, hipEventDisableTiming));
-    else HIPCHK(c, hipEventSynchronize(c->ev_mfqe));    // the previous call's copy has left the pinned staging
     memcpy(c->h_mfqe, mb_class, (size_t)nmb);
     HIPCHK(c, hipMemcpyAsync(c->d_mfqe, c->h_mfqe, (size_t)nmb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_mfqe, c->stream));

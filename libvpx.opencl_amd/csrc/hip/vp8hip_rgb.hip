@@ -47,7 +47,7 @@ extern "C" size_t vp8hip_rgb_size(const vp8hip_rgb *p)
     return (size_t)p->dst_w * p->dst_h * (p->layout == VP8HIP_RGB_PACKED4 ? 4 : 3) * vp8hip_elem_size(p->dtype, 1);
 }
 
-extern "C" size_t vp8hip_rgb_scratch_bytes(const vp8hip_ctx *c) { return c ? c->rgb_cap : 0; }
+extern "C" size_t vp8hip_rgb_scratch_bytes(const vp8hip_ctx *c) { return c ? c->d_rgb.cap : 0; }
 
 // bytes between two images of the scratch: a multiple of 16, with room for the dword a row's last load may run into
 static size_t rgb_image_stride(int w, int h) { return align_up(vp8hip_i420_size(w, h) + 4, 16); }
@@ -117,17 +117,9 @@ extern "C" int vp8hip_frames_rgb_async(vp8hip_ctx *c, const int *fbs, int n, con
         const size_t fit = RGB_SCRATCH_MAX / istride;
         if ((size_t)chunk > fit) chunk = fit < 1 ? 1 : (int)fit;
         const size_t need = istride * (size_t)chunk;
-        if (need > c->rgb_cap) {
-            // (launches in flight read the scratch: hipFree waits for them)
-            if (c->d_rgb) (void)hipFree(c->d_rgb);
-            c->d_rgb = nullptr; c->rgb_cap = 0;
-            if (hipMalloc((void **)&c->d_rgb, need) != hipSuccess) {
-                (void)hipGetLastError();
-                c->d_rgb = nullptr;
-                return fail(c, -1, "vp8hip_frames_rgb_async: no device memory for %zu bytes of scratch", need);
-            }
-            c->rgb_cap = need;
-        }
+        // (launches in flight read the scratch: hipFree waits for them)
+        if (c->d_rgb.grow(need) != hipSuccess)
+            return fail(c, -1, "vp8hip_frames_rgb_async: no device memory for %zu bytes of scratch", need);
         scale_lds = vp8hip_scale_plan(c, p->dst_w, p->dst_h, p->filter, S);
     }
     RgbLaunch L;

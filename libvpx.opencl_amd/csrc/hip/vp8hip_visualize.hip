@@ -36,10 +36,10 @@ extern "C" int vp8hip_visualize(vp8hip_ctx *c, int fb, int ir_slot, const vp8hip
     const char *d_info = nullptr, *d_rate = nullptr;
     if (info || rate) {
         // the strings go through a pinned copy of our own, so that the caller's may go away when the call returns
-        if (!c->d_vis) HIPCHK(c, hipMalloc((void **)&c->d_vis, 2 * VIS_TEXT_MAX));
-        if (!c->h_vis) HIPCHK(c, hipHostMalloc((void **)&c->h_vis, 2 * VIS_TEXT_MAX, hipHostMallocDefault));
-        if (!c->ev_vis) HIPCHK(c, hipEventCreateWithFlags(&c->ev_vis, hipEventDisableTiming));
-        else HIPCHK(c, hipEventSynchronize(c->ev_vis));  // the previous call's copy has left the pinned staging
+        HIPCHK(c, c->d_vis.grow(2 * VIS_TEXT_MAX));
+        HIPCHK(c, c->h_vis.grow(2 * VIS_TEXT_MAX));
+        if (c->ev_vis) HIPCHK(c, hipEventSynchronize(c->ev_vis));  // the previous call's copy has left the pinned staging
+        else HIPCHK(c, c->ev_vis.ensure());
         if (info) memcpy(c->h_vis, v->frame_info, info_len);
         if (rate) memcpy(c->h_vis + VIS_TEXT_MAX, v->rate_info, rate_len);
         HIPCHK(c, hipMemcpyAsync(c->d_vis, c->h_vis, 2 * VIS_TEXT_MAX, hipMemcpyHostToDevice, c->stream));

@@ -13,7 +13,7 @@ import torch  # noqa: F401  (first: the library then shares torch's HIP runtime)
 import numpy as np
 import pytest
 
-from vp8_testlib import GOLDEN, ROOT, golden_md5, oracle_decode_ivf, synth_ir
+from vp8_testlib import GOLDEN, ROOT, golden_md5, md5_list, oracle_decode_ivf, synth_ir
 from vp8_writer import write_key_frame
 from handover_testlib import assert_destinations_refused, assert_guards_intact, decode_stream, guarded, large_launch
 import scale_reference as S
@@ -36,17 +36,6 @@ def listings():
 def md5s(t):
     a = t.cpu().numpy()
     return [hashlib.md5(a[i].tobytes()).hexdigest() for i in range(a.shape[0])]
-
-
-def md5_list(ctx, fbs):
-    L = ctx.L
-    L.vp8hip_frames_md5_list_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    L.vp8hip_download_wait.argtypes = [ctypes.c_void_p]
-    arr = (ctypes.c_int * len(fbs))(*fbs)
-    out = np.zeros(16 * len(fbs), np.uint8)
-    ctx._chk(L.vp8hip_frames_md5_list_async(ctx.h, arr, len(fbs), out.ctypes.data), "md5 list")
-    ctx._chk(L.vp8hip_download_wait(ctx.h), "wait")
-    return [out[16 * i:16 * i + 16].tobytes().hex() for i in range(len(fbs))]
 
 
 @pytest.mark.parametrize("form", ["tiles", "raster"])

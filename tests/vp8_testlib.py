@@ -33,6 +33,18 @@ def golden_md5(name):
     return [l.split()[0] for l in open(os.path.join(GOLDEN, name + ".md5"))]
 
 
+def md5_list(ctx, fbs):
+    """the digests of any list of frame buffers (vp8hip_frames_md5_list_async, which the package does not wrap), waited for"""
+    L = ctx.L
+    L.vp8hip_frames_md5_list_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    L.vp8hip_download_wait.argtypes = [ctypes.c_void_p]
+    arr = (ctypes.c_int * len(fbs))(*fbs)
+    out = np.zeros(16 * len(fbs), np.uint8)
+    ctx._chk(L.vp8hip_frames_md5_list_async(ctx.h, arr, len(fbs), out.ctypes.data), "md5 list")
+    ctx._chk(L.vp8hip_download_wait(ctx.h), "wait")
+    return [out[16 * i:16 * i + 16].tobytes().hex() for i in range(len(fbs))]
+
+
 def ivf_path(name):
     return os.path.join(GOLDEN, name + ".ivf")
 
