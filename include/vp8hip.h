@@ -616,6 +616,69 @@ size_t vp8hip_trace_gather_size(const vp8hip_ctx *ctx, const vp8hip_trace_gather
 int  vp8hip_trace_gather_async(vp8hip_ctx *ctx, const vp8hip_gather_job *jobs, int n, const vp8hip_trace_gather *p,
                                const void *pool, size_t pool_stride, int pool_frames,
                                const void *src, size_t src_stride, int src_frames, void *dst, size_t dst_stride);
+/* TRACE WEAR: where what vp8hip_trace_gather_async carried is still true.  The trace always gives an answer, also where the answer is
+ * a fiction -- an intra macroblock of an inter frame is "held in place", a vector that leaves the picture is clamped, a block with a
+ * coded residual was corrected after the copy, every hop rounds its vector to whole pixels -- and the methods that propagate a key
+ * frame's result decide per region when to stop trusting it.  The WEAR of a frame counts those events along the very chain its trace
+ * follows: d_h * d_w dwords, row-major, over the display-size luma grid -- a trace's shape and size (vp8hip_trace_size) -- pixel (y, x)
+ * holding four saturating byte counters, byte b in bits 8b .. 8b + 7, of the hops on the way to the anchor in which
+ *     byte 0  HOPS    anything happened: every hop
+ *     byte 1  INTRA   the pixel's macroblock was intra (held in place: no correspondence)
+ *     byte 2  EDGE    the clamp moved the position (predicted from border replication)
+ *     byte 3  CODED   the pixel's luma block may have had a non-zero residual
+ * Wear entries live in a POOL in the caller's device memory with a trace pool's rules (pool_frames entries, pool_stride BYTES apart,
+ * dword-aligned), numbered like the caller's trace pool and frame buffers.  A job is the vp8hip_job, read exactly as
+ * vp8hip_frames_trace_async reads it.  For a job with h = its slot's header as of the call and pixel (y, x), with mb, m, k, r, v as in
+ * the trace's definition (an intra macroblock: r = 1, v = (0, 0)):
+ *     h.frame_type == 0:  W(y, x) = 0; the records are not read.
+ *     ref_fb[r] < 0 (or an m.ref_frame above 3):  W(y, x) = 0: the trace is the identity there, the frame counts as an anchor.
+ *     otherwise, with arithmetic >>,
+ *         ux = x + ((v.col + 4) >> 3)          uy = y + ((v.row + 4) >> 3)
+ *         sx = clamp(ux, 0, d_w - 1)           sy = clamp(uy, 0, d_h - 1)
+ *         P  = pool[ref_fb[r]](sy, sx), the whole dword
+ *         inc = (1,  m.ref_frame == 0,  sx != ux || sy != uy,
+ *                !(m.flags & VP8IR_MB_SKIP) && (vp8ir_block_kind(&m, k) != 0 || vp8ir_block_kind(&m, 24) != 0))
+ *         W(y, x).byte[b] = min(P.byte[b] + inc[b], 255)
+ * CODED is conservative on purpose: in a macroblock with a Y2 block a luma block with nothing of its own still gets a DC through the
+ * WHT, and vp8ir_block_kind(m, 24) is 0 for B_PRED / SPLITMV, so an increment of 0 means the pixel's luma residual is exactly zero.
+ * Not counted: the sub-pixel part of a vector (the interpolation filters), the chroma residual, the loop filter.
+ * Wear values are data and never addresses: an entry nobody wrote yields garbage counters and nothing else; the positions that become
+ * addresses come from the slot's vectors, after the clamp.
+ * vp8hip_frames_wear_async has vp8hip_frames_trace_async's promises and refusals: enqueued on the context's stream; it reads the slots'
+ * records and vectors, not the blocks (also on a vp8hip_configure_pooled context), and a later writer of those slots runs behind it;
+ * only bytes inside [pool + dst * pool_stride, + size) are written; no device memory is added and no frame buffer is touched.  Returns
+ * -2 with nothing enqueued for n < 1; a slot out of range or never filled; pool_frames < 1; pool_stride below the size; pool or
+ * pool_stride not a multiple of 4; a pool that is not device memory of the context's device or whose pool_frames entries do not fit its
+ * allocation; a dst_fb outside 0 .. pool_frames - 1; a ref_fb[1..3] neither -1 nor in range; a dst_fb that is a ref of any job of the
+ * call or another job's dst_fb.  Whole 16-byte stores need d_w % 4 == 0 and pool, pool_stride aligned to 16; otherwise dword by dword,
+ * each once.
+ *
+ * vp8hip_trace_wear_async: any n pool entries (idx: any order, repeats allowed) as tensors [popcount(planes)][gh][gw] of dtype, the
+ * planes in bit order, frame i at dst + i * dst_stride BYTES.  dst_w = dst_h = 0: gw x gh = the display size; otherwise 1..16383 each,
+ * and output (y, x) takes wear pixel (sy, sx) by vp8hip_trace_flow_async's centre map, so that at a given size the tensor lines up
+ * element for element with vp8hip_trace_flow_async's, vp8hip_trace_residual_async's, vp8hip_trace_gather_async's and
+ * vp8hip_frames_rgb_async's.  With v the byte of counter c: VP8HIP_WEAR_U8: v; VP8HIP_WEAR_F32: (float)((double)v * (double)scale[c]);
+ * VP8HIP_WEAR_F16: that float rounded to nearest-even.  Same stream, same promises; no pool entry written.  Returns -2 with nothing
+ * enqueued for what vp8hip_trace_flow_async refuses (n < 1; a pool; an idx outside it; the sizes; a bad dtype; the destination), and
+ * for planes == 0 or bits other than VP8HIP_WEAR_*.  Whole-piece stores need gw % 4 == 0 and dst, dst_stride aligned to 4 bytes
+ * (bytes), 8 (halves) or 16 (floats); anything else is written element by element, each once.
+ * vp8hip_trace_wear_size: popcount(planes) * gh * gw * element size; 0 for what the call would refuse on p alone; ctx is read for the
+ * display size only and may be NULL for a sized grid. */
+enum { VP8HIP_WEAR_U8 = 0, VP8HIP_WEAR_F16 = 1, VP8HIP_WEAR_F32 = 2 };
+#define VP8HIP_WEAR_HOPS  1      /* bit order = plane order */
+#define VP8HIP_WEAR_INTRA 2
+#define VP8HIP_WEAR_EDGE  4
+#define VP8HIP_WEAR_CODED 8
+typedef struct vp8hip_trace_wear {
+    int dst_w, dst_h;          /* both 0: the display size; otherwise 1..16383 each */
+    int dtype;                 /* VP8HIP_WEAR_U8 / F16 / F32 */
+    unsigned planes;           /* VP8HIP_WEAR_* bits, at least one */
+    float scale[4];            /* by counter (HOPS, INTRA, EDGE, CODED), not by position; read for F16 / F32 only */
+} vp8hip_trace_wear;
+int  vp8hip_frames_wear_async(vp8hip_ctx *ctx, const vp8hip_job *jobs, int n, void *pool, size_t pool_stride, int pool_frames);
+size_t vp8hip_trace_wear_size(const vp8hip_ctx *ctx, const vp8hip_trace_wear *p);
+int  vp8hip_trace_wear_async(vp8hip_ctx *ctx, const int *idx, int n, const vp8hip_trace_wear *p, const void *pool, size_t pool_stride,
+                             int pool_frames, void *dst, size_t dst_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

@@ -432,6 +432,33 @@ def trace_residual_size(gw, gh, dtype=0):
     return int(load_hip().vp8hip_trace_residual_size(None, ctypes.byref(p)))
 
 
+WEAR_PLANES = {"hops": 1, "intra": 2, "edge": 4, "coded": 8}   # VP8HIP_WEAR_*: bit order = plane order = the counter's byte
+WEAR_U8, WEAR_F16, WEAR_F32 = 0, 1, 2
+
+
+def _wear_planes(planes):
+    """names (any order; the tensor's planes come in bit order) or the mask itself -> the mask, None for an unknown plane or none"""
+    if isinstance(planes, int):
+        return planes if 0 < planes < 16 else None
+    mask = 0
+    for name in planes:
+        if name not in WEAR_PLANES:
+            return None
+        mask |= WEAR_PLANES[name]
+    return mask or None
+
+
+def trace_wear_size(gw, gh, planes=("hops", "intra", "edge", "coded"), dtype=0):
+    """bytes of one frame's tensor of Vp8Hip.trace_wear on a grid of gw x gh (vp8hip_trace_wear_size): planes * gh * gw elements; 0 for
+    a size outside 1..16383, an unknown type, no plane or an unknown one.  dtype: WEAR_U8 / WEAR_F16 / WEAR_F32 or the torch / numpy
+    type's name.  For the display size pass the display size."""
+    dt, mask = _elem_dtype(dtype, _RGB_DTYPES), _wear_planes(planes)
+    if dt is None or mask is None or gw == 0 or gh == 0:         # (0 x 0 would ask for the display size, which needs a context)
+        return 0
+    p = TraceWearParams(int(gw), int(gh), dt, mask)
+    return int(load_hip().vp8hip_trace_wear_size(None, ctypes.byref(p)))
+
+
 GATHER_FILTERS = {"nearest": 0, "bilinear": 1}               # VP8HIP_GATHER_NEAREST, BILINEAR
 GATHER_LAYOUTS = {"planar": 0, "channels_last": 1}            # VP8HIP_GATHER_PLANAR, CHANNELS_LAST
 
@@ -516,6 +543,10 @@ class TraceGatherParams(ctypes.Structure):  # vp8hip_trace_gather, include/vp8hi
                 ("layout", c_int), ("filter", c_int)]
 
 
+class TraceWearParams(ctypes.Structure):    # vp8hip_trace_wear, include/vp8hip.h
+    _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("dtype", c_int), ("planes", ctypes.c_uint), ("scale", ctypes.c_float * 4)]
+
+
 class VisParams(ctypes.Structure):          # vp8hip_vis, include/vp8hip.h
     _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
                 ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
@@ -592,6 +623,11 @@ def load_hip():
         L.vp8hip_trace_gather_size.restype = c_size_t
         L.vp8hip_trace_gather_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(TraceGatherParams), c_void_p, c_size_t, c_int,
                                                 c_void_p, c_size_t, c_int, c_void_p, c_size_t]
+        L.vp8hip_frames_wear_async.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int]
+        L.vp8hip_trace_wear_size.argtypes = [c_void_p, ctypes.POINTER(TraceWearParams)]
+        L.vp8hip_trace_wear_size.restype = c_size_t
+        L.vp8hip_trace_wear_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(TraceWearParams), c_void_p, c_size_t, c_int, c_void_p,
+                                              c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1018,13 +1054,15 @@ class Vp8Hip:
         torch, dev = self._torch_device("trace_pool")
         return torch.empty((int(n), self.height, self.width, 2), dtype=torch.int16, device=dev)
 
-    def _trace_pool_args(self, who, pool):
-        """-> (dev, pointer, stride in bytes, entries) of a pool as trace_pool makes them (a view is fine: each entry dense)"""
+    def _trace_pool_args(self, who, pool, kind=("int16", 2)):
+        """-> (dev, pointer, stride in bytes, entries) of a pool as trace_pool makes them (a view is fine: each entry dense); kind:
+        the type's name and how many make a pixel's dword -- ("uint8", 4): a pool as wear_pool makes them"""
         torch, dev = self._torch_device(who)
+        name, per = kind
         if not (torch.is_tensor(pool) and pool.dim() == 4 and pool.shape[0] >= 1
-                and self._dense(pool, torch.int16, (pool.shape[0], self.height, self.width, 2), dev)):
-            raise ValueError(f"{who}: pool must be an int16 tensor [n, {self.height}, {self.width}, 2], each entry dense, on {dev}")
-        return dev, c_void_p(pool.data_ptr()), pool.stride(0) * 2, int(pool.shape[0])
+                and self._dense(pool, getattr(torch, name), (pool.shape[0], self.height, self.width, per), dev)):
+            raise ValueError(f"{who}: pool must be {'an' if name[0] == 'i' else 'a'} {name} tensor [n, {self.height}, {self.width}, {per}], each entry dense, on {dev}")
+        return dev, c_void_p(pool.data_ptr()), pool.stride(0) * (4 // per), int(pool.shape[0])
 
     def frames_trace(self, jobs, pool):
         """The traces of `jobs` -- a list of (ir_slot, dst, (last, golden, alt)) as decode takes it, dst and the three references read
@@ -1072,6 +1110,61 @@ class Vp8Hip:
                               lambda arr_out, stride: self.L.vp8hip_trace_flow_async(
                                   self.h, (c_int * max(n, 1))(*idx), n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
                               "vp8hip_trace_flow_async")[0]
+
+    def wear_pool(self, n):
+        """a pool of n wear entries for frames_wear on the context's device: a torch.uint8 tensor [n, d_h, d_w, 4], the counters (hops,
+        intra, edge, coded) per pixel of the display-size grid (include/vp8hip.h).  Not initialised."""
+        torch, dev = self._torch_device("wear_pool")
+        return torch.empty((int(n), self.height, self.width, 4), dtype=torch.uint8, device=dev)
+
+    def frames_wear(self, jobs, pool):
+        """The wear of `jobs` -- the jobs of frames_trace, dst and the three references read as entries of `pool` (wear_pool; -1 or
+        refs None: no entry) -- written into pool[dst] (vp8hip_frames_wear_async): what happened to each pixel on the way its trace
+        takes to the anchor picture, four saturating byte counters -- every hop; the hops in which its macroblock was intra (held
+        in place); those in which the clamp moved the position; those in which its luma block may have had a residual.  A key
+        frame's is zero; an inter frame's is the wear of the reference at the position the trace's hop goes to, plus the hop's
+        increments.  A pool numbered like the trace pool takes the very jobs of frames_trace.  Stream ordering: as frames_trace.
+        Returns pool."""
+        arr, n = (jobs, len(jobs)) if isinstance(jobs, ctypes.Array) else (self.job_array(list(jobs)), len(jobs))
+        dev, ptr, stride, entries = self._trace_pool_args("frames_wear", pool, ("uint8", 4))
+        self._between_stream_waits(dev, lambda: self.L.vp8hip_frames_wear_async(self.h, arr, n, ptr, stride, entries),
+                                   "vp8hip_frames_wear_async")
+        return pool
+
+    def trace_wear(self, pool, idx, width=None, height=None, planes=("hops", "intra", "edge", "coded"), dtype=None, scale=None, out=None):
+        """Entries `idx` of the wear pool `pool` (any order, repeats allowed) as tensors [n, C, gh, gw] on the context's device
+        (vp8hip_trace_wear_async): the counters of `planes` ("hops", "intra", "edge", "coded", or the mask) in bit order, at the
+        display size or under each output's centre at width x height (then the tensor lines up with trace_flow's, trace_gather's
+        and frames_rgb's at that size).  torch.uint8 (the default: the counter), torch.float16 or torch.float32; float types:
+        float32(float64(v) * scale[c]) with scale = one number or four, by counter (hops, intra, edge, coded) whatever planes are
+        asked for, float32 (default 1).  `out`: a tensor of that shape and type, each frame dense, stride(0) free.  Stream
+        ordering: as frames_scaled."""
+        import torch
+        idx = [int(i) for i in idx]
+        n = len(idx)
+        dst_w, dst_h, gw, gh = self._trace_grid("trace_wear", width, height)
+        dtype = torch.uint8 if dtype is None else dtype
+        dt, mask = _elem_dtype(dtype, _RGB_DTYPES), _wear_planes(planes)
+        if dt is None or mask is None:
+            raise ValueError(f"trace_wear: dtype {dtype}, planes {planes!r}")
+        if scale is None:
+            sc = (1.0,) * 4
+        elif np.ndim(scale) == 0 and not isinstance(scale, str):
+            sc = (float(scale),) * 4
+        else:
+            sc = tuple(float(v) for v in scale) if not isinstance(scale, str) else ()
+            if len(sc) != 4:
+                raise ValueError(f"trace_wear: scale {scale!r}")
+        p = TraceWearParams(dst_w, dst_h, dt, mask)
+        for c in range(4):
+            p.scale[c] = np.float32(sc[c])
+        if not self.L.vp8hip_trace_wear_size(self.h, ctypes.byref(p)):
+            raise ValueError(f"trace_wear: grid {gw}x{gh}: refused (sizes 1..16383)")
+        _, pptr, pstride, entries = self._trace_pool_args("trace_wear", pool, ("uint8", 4))
+        return self._to_torch("trace_wear", [("out", out, _RGB_DTYPES[dt], (n, bin(mask).count("1"), gh, gw))],
+                              lambda arr_out, stride: self.L.vp8hip_trace_wear_async(
+                                  self.h, (c_int * max(n, 1))(*idx), n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
+                              "vp8hip_trace_wear_async")[0]
 
     def trace_residual(self, pool, jobs, width=None, height=None, dtype=None, matrix="bt601", order="rgb", scale=None, out=None):
         """The accumulated residual of `jobs` -- a list of (fb, entry, anchor_fb): the frame buffer that holds a frame, the entry of

@@ -85,6 +85,7 @@ struct RgbLaunch {
 #define TENSOR_I16 0
 #define TENSOR_F16 1
 #define TENSOR_F32 2
+#define TENSOR_U8 3               // a byte, the value itself: vp8hip_trace_wear::dtype 0 (VP8HIP_WEAR_F16 / _F32 are TENSOR_F16 / _F32)
 
 // One launch of vp8hip_frames_side_async (vp8_side.hip), as the host's plan (vp8hip_side.hip: side_plan) left it
 #define SIDE_MAX_FRAMES 256       // slots per launch (kernel arguments)
@@ -158,6 +159,14 @@ struct TraceGrid {
 struct FlowLaunch {
     TraceGrid g;
     float scale[2];               // x, y; float types
+    int idx[FLOW_MAX_FRAMES];     // pool entry of frame k of the launch
+};
+
+// One launch of vp8hip_trace_wear_async (vp8_trace_wear.hip); vp8hip_frames_wear_async launches with the trace's TraceLaunch
+struct WearLaunch {
+    TraceGrid g;
+    unsigned planes;              // VP8HIP_WEAR_* bits: counter c is a plane of the tensor where bit c is set, in bit order
+    float scale[4];               // by counter: HOPS, INTRA, EDGE, CODED; float types
     int idx[FLOW_MAX_FRAMES];     // pool entry of frame k of the launch
 };
 

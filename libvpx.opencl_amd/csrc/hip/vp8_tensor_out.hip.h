@@ -1,5 +1,5 @@
 // The output side shared by the kernels that hand something to a device consumer as tensors (vp8_side.hip, vp8_residual.hip, the
-// three vp8_trace*.hip through vp8_trace_read.hip.h and, for the walk and the planar store, vp8_rgb.hip): the element of a dtype,
+// vp8_trace*.hip through vp8_trace_read.hip.h and, for the walk and the planar store, vp8_rgb.hip): the element of a dtype,
 // value x scale as the element's bits, the map between an output grid and the samples it is laid over in both directions, the share
 // of a row range among workgroups, the store of four neighbouring elements and a lane's walk over a row range in groups of four.
 #pragma once
@@ -14,13 +14,14 @@ template <int ES> struct TensorUint;
 template <> struct TensorUint<1> { typedef unsigned char T; };
 template <> struct TensorUint<2> { typedef unsigned short T; };
 template <> struct TensorUint<4> { typedef unsigned int T; };
-template <int DTYPE> struct TensorElem : TensorUint<DTYPE == TENSOR_F32 ? 4 : 2> {};
+template <int DTYPE> struct TensorElem : TensorUint<DTYPE == TENSOR_F32 ? 4 : DTYPE == TENSOR_U8 ? 1 : 2> {};
 
-// v (an int16) as the bits of an element: itself, or v x scale as a float / a half
+// v (an int16; TENSOR_U8: a byte) as the bits of an element: itself, or v x scale as a float / a half
 template <int DTYPE>
 __device__ __forceinline__ unsigned tensor_value(int v, float scale)
 {
     if constexpr (DTYPE == TENSOR_I16) return (unsigned)v & 0xffffu;
+    else if constexpr (DTYPE == TENSOR_U8) return (unsigned)v & 0xffu;
     else {
         // (float)((double)v * (double)scale): the product of an int16 and a float is exact in double, so this is that product
         // rounded once -- which is what the single-precision multiply gives (denormal results kept: the kernels' float mode)

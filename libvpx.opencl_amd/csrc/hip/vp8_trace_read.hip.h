@@ -1,7 +1,8 @@
 // Reading a trace (include/vp8hip.h: one dword per pixel of the display-size grid, x' in the low int16 and y' in the high one), once
 // for the kernels that do: vp8_trace_kernel for a reference's trace, and the readers of a pool entry laid under an output grid
 // (TraceGrid, vp8_common.hip.h) -- vp8_flow_*_kernel (vp8_trace.hip), vp8_anchor_*_kernel (vp8_trace_residual.hip) and
-// vp8_gather_*_kernel (vp8_trace_gather.hip).
+// vp8_gather_*_kernel (vp8_trace_gather.hip); and vp8_trace_wear.hip, whose pool has a trace pool's geometry and whose dwords are
+// counters: vp8_wear_kernel gathers a reference's as vp8_trace_kernel does, vp8_wear_*_kernel reads an entry through trace_read4.
 //
 // THE CLAMP.  In vp8_trace.hip a trace value is data; in the other two files it becomes an address.  There every value goes through
 // trace_clamp before anything is formed from it, so a pool entry nobody wrote yields garbage values and never a read outside the

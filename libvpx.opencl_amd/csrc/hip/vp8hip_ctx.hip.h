@@ -8,7 +8,9 @@
 //                       _residual_async: frames, and what the slots hold beside them, as tensors in the caller's device memory
 //   vp8hip_trace.hip    vp8hip_frames_trace_async: accumulated motion in a pool in the caller's device memory (vp8_trace.hip), and
 //                       the pool's readers vp8hip_trace_flow_async (vp8_trace.hip), vp8hip_trace_residual_async
-//                       (vp8_trace_residual.hip) and vp8hip_trace_gather_async (vp8_trace_gather.hip)
+//                       (vp8_trace_residual.hip) and vp8hip_trace_gather_async (vp8_trace_gather.hip); vp8hip_frames_wear_async and
+//                       vp8hip_trace_wear_async: what happened along the trace, in a pool of its own, and its entries as tensors
+//                       (vp8_trace_wear.hip)
 //   vp8hip_handover.hip the checks those calls share
 // and vp8hip_res.hip.h: the owning types of the context's buffers, events and streams.
 #pragma once

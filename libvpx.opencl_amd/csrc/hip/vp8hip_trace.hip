@@ -1,18 +1,25 @@
-// vp8hip_frames_trace_async, vp8hip_trace_flow_async, vp8hip_trace_residual_async and vp8hip_trace_gather_async (include/vp8hip.h):
+// vp8hip_frames_trace_async, vp8hip_trace_flow_async, vp8hip_trace_residual_async, vp8hip_trace_gather_async and the trace's wear,
+// vp8hip_frames_wear_async and vp8hip_trace_wear_async (include/vp8hip.h):
 // accumulated motion -- every pixel traced back through the frames it was predicted from to the key frame that started the group -- in
 // a pool in the caller's device memory, a pool entry as a flow tensor, a frame minus its anchor picture gathered at its trace as a
 // residual tensor, and a tensor of the caller's gathered at a trace.  The plans and the checks are made here, once per call; the
-// kernels are in vp8_trace.hip, vp8_trace_residual.hip and vp8_trace_gather.hip.  The trace
+// kernels are in vp8_trace.hip, vp8_trace_residual.hip, vp8_trace_gather.hip and vp8_trace_wear.hip (what happened to a pixel along its
+// trace: four counters a pixel in a pool of its own, chained as the trace is, and a pool entry as a tensor).  The trace
 // reads the slots' records and vectors (also on a vp8hip_configure_pooled context) and the pool entries its jobs name; the slots'
 // header bits come with the launch, as of this call: nothing is allocated on the device, copied or synchronised.
 #include "vp8hip_ctx.hip.h"
 
 #define TRACE_ARGS const char *slot_base, size_t slot_bytes, size_t o_mbx, size_t o_mvs, uint8_t *pool, size_t pool_stride, TraceLaunch L
 extern "C" __global__ void vp8_trace_kernel(TRACE_ARGS);
+extern "C" __global__ void vp8_wear_kernel(TRACE_ARGS);
 #define FLOW_ARGS const uint8_t *pool, size_t pool_stride, uint8_t *dst, size_t dst_stride, FlowLaunch L
 extern "C" __global__ void vp8_flow_i16_kernel(FLOW_ARGS);
 extern "C" __global__ void vp8_flow_f16_kernel(FLOW_ARGS);
 extern "C" __global__ void vp8_flow_f32_kernel(FLOW_ARGS);
+#define WEAR_ARGS const uint8_t *pool, size_t pool_stride, uint8_t *dst, size_t dst_stride, WearLaunch L
+extern "C" __global__ void vp8_wear_u8_kernel(WEAR_ARGS);
+extern "C" __global__ void vp8_wear_f16_kernel(WEAR_ARGS);
+extern "C" __global__ void vp8_wear_f32_kernel(WEAR_ARGS);
 
 #define ANCHOR_ARGS const uint8_t *raster, size_t fb_stride, const uint8_t *tiles, size_t tile_frame, const uint8_t *pool, size_t pool_stride, \
                     uint8_t *dst, size_t dst_stride, AnchorLaunch L
@@ -50,14 +57,17 @@ static int trace_check_pool(vp8hip_ctx *c, const char *who, const void *pool, si
     return vp8hip_check_dst(c, who, pool, pool_stride, vp8hip_trace_size(c), 4, pool_frames);
 }
 
-extern "C" int vp8hip_frames_trace_async(vp8hip_ctx *c, const vp8hip_job *jobs, int n, void *pool, size_t pool_stride, int pool_frames)
+// What vp8hip_frames_trace_async and vp8hip_frames_wear_async are: the checks of a call whose jobs chain entries of a pool through
+// the slots' records and vectors, and the launches of `kernel` (vp8_trace_kernel's shape: groups of macroblock rows x jobs).
+// who_pool: the name the pool's check speaks under
+static int trace_frames(vp8hip_ctx *c, const char *who, const char *who_pool, void (*kernel)(TRACE_ARGS), const vp8hip_job *jobs, int n, void *pool,
+                        size_t pool_stride, int pool_frames)
 {
-    const char *who = "vp8hip_frames_trace_async";
     if (!c || !jobs || n < 1 || !pool || c->slots.empty() || !c->width) return fail(c, -2, "%s: bad arguments", who);
     std::vector<int> slots((size_t)n);
     for (int i = 0; i < n; i++) slots[(size_t)i] = jobs[i].ir_slot;
     if (int rc = vp8hip_check_slots(c, who, slots.data(), n)) return rc;
-    if (int rc = trace_check_pool(c, "vp8hip_frames_trace_async (pool)", pool, pool_stride, pool_frames)) return rc;
+    if (int rc = trace_check_pool(c, who_pool, pool, pool_stride, pool_frames)) return rc;
     // one marker byte per pool entry: 1 a reference of some job, 2 some job's destination
     std::vector<uint8_t> mark((size_t)pool_frames, 0);
     for (int i = 0; i < n; i++) {
@@ -86,7 +96,7 @@ extern "C" int vp8hip_frames_trace_async(vp8hip_ctx *c, const vp8hip_job *jobs, 
     L.R = R;
     const size_t lds = align_up((size_t)R * row_bytes, 16);
     if (lds > 65536)             // (frames wider than 15408: one macroblock row is all a workgroup stages)
-        HIPCHK(c, hipFuncSetAttribute((const void *)vp8_trace_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     L.vec = L.dw % 4 == 0 && (uintptr_t)pool % 16 == 0 && pool_stride % 16 == 0;
     const unsigned groups = (unsigned)((L.mb_rows + R - 1) / R);
     for (int i0 = 0; i0 < n; i0 += TRACE_MAX_FRAMES) {
@@ -98,11 +108,22 @@ extern "C" int vp8hip_frames_trace_async(vp8hip_ctx *c, const vp8hip_job *jobs, 
             J.ref[0] = job.ref_fb[1]; J.ref[1] = job.ref_fb[2]; J.ref[2] = job.ref_fb[3];
             J.key = c->slots[(size_t)job.ir_slot].hdr_copy.frame_type == 0;
         }
-        hipLaunchKernelGGL(vp8_trace_kernel, dim3(groups, (unsigned)m), dim3(256), (unsigned)lds, c->stream, (const char *)c->slot_block_dev,
+        hipLaunchKernelGGL(kernel, dim3(groups, (unsigned)m), dim3(256), (unsigned)lds, c->stream, (const char *)c->slot_block_dev,
                            c->slot_bytes, c->o_mbx, c->o_mvs, (uint8_t *)pool, pool_stride, L);
         HIPCHK(c, hipGetLastError());
     }
     return 0;
+}
+
+extern "C" int vp8hip_frames_trace_async(vp8hip_ctx *c, const vp8hip_job *jobs, int n, void *pool, size_t pool_stride, int pool_frames)
+{
+    return trace_frames(c, "vp8hip_frames_trace_async", "vp8hip_frames_trace_async (pool)", vp8_trace_kernel, jobs, n, pool, pool_stride, pool_frames);
+}
+
+// a wear entry has a trace's shape and size, and a macroblock takes the trace's 68 bytes of LDS (one dword of its record, sixteen vectors)
+extern "C" int vp8hip_frames_wear_async(vp8hip_ctx *c, const vp8hip_job *jobs, int n, void *pool, size_t pool_stride, int pool_frames)
+{
+    return trace_frames(c, "vp8hip_frames_wear_async", "vp8hip_frames_wear_async (pool)", vp8_wear_kernel, jobs, n, pool, pool_stride, pool_frames);
 }
 
 // the grid of dst_w x dst_h on context c (null: sized grids only); false for what the calls refuse
@@ -164,6 +185,52 @@ extern "C" int vp8hip_trace_flow_async(vp8hip_ctx *c, const int *idx, int n, con
     L.g = trace_grid(c, gw, gh, es, FLOW_PART_QUADS, dst, dst_stride);
     L.scale[0] = p->scale[0]; L.scale[1] = p->scale[1];
     void (*const kernels[3])(FLOW_ARGS) = {vp8_flow_i16_kernel, vp8_flow_f16_kernel, vp8_flow_f32_kernel};
+    for (int i0 = 0; i0 < n; i0 += FLOW_MAX_FRAMES) {
+        const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
+        memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
+        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.g.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
+                           (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+// the grid of p on context c; false for what the call refuses on p alone
+static bool wear_grid(const vp8hip_ctx *c, const vp8hip_trace_wear *p, int &gw, int &gh)
+{
+    const unsigned all = VP8HIP_WEAR_HOPS | VP8HIP_WEAR_INTRA | VP8HIP_WEAR_EDGE | VP8HIP_WEAR_CODED;
+    return p && p->dtype >= 0 && p->dtype <= 2 && p->planes && !(p->planes & ~all) && trace_out_grid(c, p->dst_w, p->dst_h, gw, gh);
+}
+
+extern "C" size_t vp8hip_trace_wear_size(const vp8hip_ctx *c, const vp8hip_trace_wear *p)
+{
+    int gw, gh;
+    return wear_grid(c, p, gw, gh) ? (size_t)__builtin_popcount(p->planes) * gh * gw * vp8hip_elem_size(p->dtype, 1) : 0;
+}
+
+extern "C" int vp8hip_trace_wear_async(vp8hip_ctx *c, const int *idx, int n, const vp8hip_trace_wear *p, const void *pool, size_t pool_stride,
+                                       int pool_frames, void *dst, size_t dst_stride)
+{
+    const char *who = "vp8hip_trace_wear_async";
+    if (!c || !idx || n < 1 || !p || !pool || !dst || !c->width) return fail(c, -2, "%s: bad arguments", who);
+    int gw, gh;
+    if (!wear_grid(c, p, gw, gh))
+        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), type %d, planes 0x%x", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE, p->dtype,
+                    p->planes);
+    if (int rc = trace_check_pool(c, "vp8hip_trace_wear_async (pool)", pool, pool_stride, pool_frames)) return rc;
+    for (int i = 0; i < n; i++)
+        if (idx[i] < 0 || idx[i] >= pool_frames) return fail(c, -2, "%s: entry %d outside the pool", who, idx[i]);
+    const size_t es = (size_t)vp8hip_elem_size(p->dtype, 1);
+    const size_t size = (size_t)__builtin_popcount(p->planes) * gh * gw * es;
+    if (int rc = vp8hip_check_dst(c, "vp8hip_trace_wear_async (dst)", dst, dst_stride, size, es, n)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+
+    WearLaunch L;
+    memset(&L, 0, offsetof(WearLaunch, idx));
+    L.g = trace_grid(c, gw, gh, es, FLOW_PART_QUADS, dst, dst_stride);
+    L.planes = p->planes;
+    for (int k = 0; k < 4; k++) L.scale[k] = p->scale[k];
+    void (*const kernels[3])(WEAR_ARGS) = {vp8_wear_u8_kernel, vp8_wear_f16_kernel, vp8_wear_f32_kernel};
     for (int i0 = 0; i0 < n; i0 += FLOW_MAX_FRAMES) {
         const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
         memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
