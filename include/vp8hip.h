@@ -679,6 +679,69 @@ int  vp8hip_frames_wear_async(vp8hip_ctx *ctx, const vp8hip_job *jobs, int n, vo
 size_t vp8hip_trace_wear_size(const vp8hip_ctx *ctx, const vp8hip_trace_wear *p);
 int  vp8hip_trace_wear_async(vp8hip_ctx *ctx, const int *idx, int n, const vp8hip_trace_wear *p, const void *pool, size_t pool_stride,
                              int pool_frames, void *dst, size_t dst_stride);
+/* A TRACE INVERTED: first descendant and descendant count per anchor pixel.  The trace and everything made from it face one way: for a
+ * pixel of a later frame, what is true about it in the anchor picture.  The inverse answers the opposite question -- for a pixel of the
+ * anchor picture, did it survive into the frame, where is it now, and how many pixels of the frame claim it -- which is what pushing
+ * boxes, keypoints and track seeds forward, telling a stretched region from a covered one, and warping a later frame's tensors onto the
+ * anchor's grid need.  With d_w x d_h the context's display size and T a trace pool entry:
+ *   - For a frame pixel p = (y, x), a(p) = trace_clamp(T(y, x)) = (ay, ax):
+ *         ax = clamp((int16)(t & 0xffff), 0, d_w - 1)      ay = clamp((int16)(t >> 16), 0, d_h - 1)
+ *     the one clamp the readers of a trace share.
+ *   - D(a) is the set of frame pixels p with a(p) = a.
+ * Two outputs are defined per job.  Each has a trace entry's shape and size: vp8hip_trace_size, d_h * d_w dwords, row-major over the
+ * anchor's grid.
+ *   - FIRST(ay, ax):
+ *       - It is the member of D(a) that comes first in raster order, packed as a trace packs a position (x in the low int16, y in the
+ *         high one).
+ *       - It is 0xffffffff where D(a) is empty.
+ *       - Positions are non-negative and below 16384.  So unsigned order of the packed dword IS raster order, and 0xffffffff is above
+ *         every position.  FIRST is the unsigned minimum over D(a) of y << 16 | x.
+ *       - A FIRST entry is therefore a trace in the other direction.  vp8hip_trace_flow_async and vp8hip_trace_gather_async read a
+ *         FIRST pool unchanged.  The gather then forward-warps a frame-t tensor onto the anchor grid.
+ *       - Where D(a) is empty they read (-1, -1).  Their existing definitions handle that value: it is data, clamped to (0, 0) before
+ *         it is an address.  COUNT is the mask for it.
+ *   - COUNT(ay, ax) = |D(a)|, an exact uint32.  It is at most d_w * d_h, which is below 2^28.
+ *   - The sum of COUNT over the entry is d_w * d_h.
+ * Both are pure functions of the trace entry.  They are unsigned min and integer add, so the result does not depend on the order in
+ * which lanes arrive.  Two runs give the same bits.
+ * vp8hip_trace_invert_async: `first` and `count` are pools in the caller's device memory with a trace pool's rules (out_frames entries
+ * each, first_stride / count_stride BYTES apart, dword-aligned, strides at least the entry size, inside one allocation of the context's
+ * device).  Either may be NULL, not both.  Job i reads pool[trace] and writes entry dst of each pool given; repeats of `trace` are
+ * allowed.  Enqueued on the context's stream: traces written by an earlier vp8hip_frames_trace_async are seen.  The call adds no device
+ * memory and reads no slot and no frame buffer; only bytes inside the dst entries are written.  THE CLAMP guards writes here: every
+ * trace value is clamped before an address is formed from it, so a trace entry nobody wrote scatters garbage inside the job's
+ * destination entries and nowhere else.  Returns -2 with nothing enqueued for n < 1; what vp8hip_trace_flow_async refuses of a pool,
+ * for each of the three pools; a trace outside 0 .. pool_frames - 1 or a dst outside 0 .. out_frames - 1; two jobs with one dst; both
+ * outputs NULL; any two of the three byte ranges [pool, + pool_frames * pool_stride), [first, + out_frames * first_stride),
+ * [count, + out_frames * count_stride) overlapping (vp8hip_trace_gather_async's rule for src / dst).
+ *
+ * vp8hip_trace_cover_async: any n entries of a COUNT pool (idx: any order, repeats allowed) as tensors [popcount(planes)][gh][gw] of
+ * dtype (VP8HIP_WEAR_U8 / F16 / F32), the planes in bit order, frame i at dst + i * dst_stride BYTES, under vp8hip_trace_flow_async's
+ * centre map: vp8hip_trace_wear_async's shape over a COUNT pool.  With c the count under the output's centre: VP8HIP_COVER_COUNT has
+ * v = min(c, 255), VP8HIP_COVER_SEEN has v = (c != 0).  U8 gives v; F32 (float)((double)v * (double)scale[plane]), by plane (COUNT,
+ * SEEN), not by position; F16 that float rounded to nearest-even.  v saturates at 255 for every dtype, as wear's counters do: these
+ * are compared with small thresholds, and the exact dwords are in the caller's pool already.  Refusals, alignment rules and
+ * whole-piece stores are those of vp8hip_trace_wear_async, with VP8HIP_COVER_* for its planes.
+ * vp8hip_trace_cover_size: popcount(planes) * gh * gw * element size; 0 for what the call would refuse on p alone; ctx is read for the
+ * display size only and may be NULL for a sized grid. */
+typedef struct vp8hip_invert_job {     /* one inverted trace */
+    int32_t trace;             /* pool entry that holds the frame's trace (vp8hip_frames_trace_async) */
+    int32_t dst;               /* entry of the FIRST pool and of the COUNT pool written */
+} vp8hip_invert_job;
+int  vp8hip_trace_invert_async(vp8hip_ctx *ctx, const vp8hip_invert_job *jobs, int n,
+                               const void *pool, size_t pool_stride, int pool_frames,      /* traces, read */
+                               void *first, size_t first_stride, void *count, size_t count_stride, int out_frames);
+#define VP8HIP_COVER_COUNT 1     /* bit order = plane order */
+#define VP8HIP_COVER_SEEN  2
+typedef struct vp8hip_trace_cover {
+    int dst_w, dst_h;          /* both 0: the display size; otherwise 1..16383 each */
+    int dtype;                 /* VP8HIP_WEAR_U8 / F16 / F32 */
+    unsigned planes;           /* VP8HIP_COVER_* bits, at least one */
+    float scale[2];            /* by plane (COUNT, SEEN), not by position; read for F16 / F32 only */
+} vp8hip_trace_cover;
+size_t vp8hip_trace_cover_size(const vp8hip_ctx *ctx, const vp8hip_trace_cover *p);
+int  vp8hip_trace_cover_async(vp8hip_ctx *ctx, const int *idx, int n, const vp8hip_trace_cover *p, const void *count, size_t count_stride,
+                              int count_frames, void *dst, size_t dst_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

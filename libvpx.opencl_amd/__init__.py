@@ -459,7 +459,33 @@ def trace_wear_size(gw, gh, planes=("hops", "intra", "edge", "coded"), dtype=0):
     return int(load_hip().vp8hip_trace_wear_size(None, ctypes.byref(p)))
 
 
-GATHER_FILTERS = {"nearest": 0, "bilinear": 1}               # VP8HIP_GATHER_NEAREST, BILINEAR
+COVER_PLANES = {"count": 1, "seen": 2}                        # VP8HIP_COVER_*: bit order = plane order
+
+
+def _cover_planes(planes):
+    """names (any order; the tensor's planes come in bit order) or the mask itself -> the mask, None for an unknown plane or none"""
+    if isinstance(planes, int):
+        return planes if 0 < planes < 4 else None
+    mask = 0
+    for name in planes:
+        if name not in COVER_PLANES:
+            return None
+        mask |= COVER_PLANES[name]
+    return mask or None
+
+
+def trace_cover_size(gw, gh, planes=("count", "seen"), dtype=0):
+    """bytes of one frame's tensor of Vp8Hip.trace_cover on a grid of gw x gh (vp8hip_trace_cover_size): planes * gh * gw elements; 0
+    for a size outside 1..16383, an unknown type, no plane or an unknown one.  dtype: WEAR_U8 / WEAR_F16 / WEAR_F32 or the torch /
+    numpy type's name.  For the display size pass the display size."""
+    dt, mask = _elem_dtype(dtype, _RGB_DTYPES), _cover_planes(planes)
+    if dt is None or mask is None or gw == 0 or gh == 0:         # (0 x 0 would ask for the display size, which needs a context)
+        return 0
+    p = TraceCoverParams(int(gw), int(gh), dt, mask)
+    return int(load_hip().vp8hip_trace_cover_size(None, ctypes.byref(p)))
+
+
+GATHER_FILTERS = {"nearest": 0, "bilinear": 1}              # VP8HIP_GATHER_NEAREST, BILINEAR
 GATHER_LAYOUTS = {"planar": 0, "channels_last": 1}            # VP8HIP_GATHER_PLANAR, CHANNELS_LAST
 
 
@@ -547,7 +573,15 @@ class TraceWearParams(ctypes.Structure):    # vp8hip_trace_wear, include/vp8hip.
     _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("dtype", c_int), ("planes", ctypes.c_uint), ("scale", ctypes.c_float * 4)]
 
 
-class VisParams(ctypes.Structure):          # vp8hip_vis, include/vp8hip.h
+class InvertJob(ctypes.Structure):          # vp8hip_invert_job, include/vp8hip.h
+    _fields_ = [("trace", ctypes.c_int32), ("dst", ctypes.c_int32)]
+
+
+class TraceCoverParams(ctypes.Structure):   # vp8hip_trace_cover, include/vp8hip.h
+    _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("dtype", c_int), ("planes", ctypes.c_uint), ("scale", ctypes.c_float * 2)]
+
+
+class VisParams(ctypes.Structure):         # vp8hip_vis, include/vp8hip.h
     _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
                 ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
 
@@ -628,6 +662,12 @@ def load_hip():
         L.vp8hip_trace_wear_size.restype = c_size_t
         L.vp8hip_trace_wear_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(TraceWearParams), c_void_p, c_size_t, c_int, c_void_p,
                                               c_size_t]
+        L.vp8hip_trace_invert_async.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
+                                                c_int]
+        L.vp8hip_trace_cover_size.argtypes = [c_void_p, ctypes.POINTER(TraceCoverParams)]
+        L.vp8hip_trace_cover_size.restype = c_size_t
+        L.vp8hip_trace_cover_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(TraceCoverParams), c_void_p, c_size_t, c_int, c_void_p,
+                                               c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1056,12 +1096,14 @@ class Vp8Hip:
 
     def _trace_pool_args(self, who, pool, kind=("int16", 2)):
         """-> (dev, pointer, stride in bytes, entries) of a pool as trace_pool makes them (a view is fine: each entry dense); kind:
-        the type's name and how many make a pixel's dword -- ("uint8", 4): a pool as wear_pool makes them"""
+        the type's name and how many make a pixel's dword -- ("uint8", 4): a pool as wear_pool makes them; ("int32", 1): the COUNT
+        pool of cover_pools, [n, d_h, d_w]"""
         torch, dev = self._torch_device(who)
         name, per = kind
-        if not (torch.is_tensor(pool) and pool.dim() == 4 and pool.shape[0] >= 1
-                and self._dense(pool, getattr(torch, name), (pool.shape[0], self.height, self.width, per), dev)):
-            raise ValueError(f"{who}: pool must be {'an' if name[0] == 'i' else 'a'} {name} tensor [n, {self.height}, {self.width}, {per}], each entry dense, on {dev}")
+        inner = (self.height, self.width) + ((per,) if per > 1 else ())
+        if not (torch.is_tensor(pool) and pool.dim() == 1 + len(inner) and pool.shape[0] >= 1
+                and self._dense(pool, getattr(torch, name), (pool.shape[0],) + inner, dev)):
+            raise ValueError(f"{who}: pool must be {'an' if name[0] == 'i' else 'a'} {name} tensor [n, {', '.join(str(v) for v in inner)}], each entry dense, on {dev}")
         return dev, c_void_p(pool.data_ptr()), pool.stride(0) * (4 // per), int(pool.shape[0])
 
     def frames_trace(self, jobs, pool):
@@ -1165,6 +1207,73 @@ class Vp8Hip:
                               lambda arr_out, stride: self.L.vp8hip_trace_wear_async(
                                   self.h, (c_int * max(n, 1))(*idx), n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
                               "vp8hip_trace_wear_async")[0]
+
+    def cover_pools(self, n):
+        """(FIRST, COUNT): pools of n entries each for trace_invert on the context's device.  FIRST is a torch.int16 tensor
+        [n, d_h, d_w, 2], exactly what trace_pool returns: (x, y) of the first frame pixel that descends from the anchor pixel,
+        (-1, -1) where none does.  COUNT is a torch.int32 tensor [n, d_h, d_w]: how many do.  Not initialised."""
+        torch, dev = self._torch_device("cover_pools")
+        return self.trace_pool(n), torch.empty((int(n), self.height, self.width), dtype=torch.int32, device=dev)
+
+    def trace_invert(self, pool, jobs, first=None, count=None):
+        """The traces of `pool` inverted (vp8hip_trace_invert_async).  `jobs`: a list of (entry, dst): the entry of `pool` that holds a
+        frame's trace (frames_trace) and the entry of `first` and of `count` (cover_pools; either may be None, not both) its
+        inverse is written into; repeats of an entry are allowed, every dst once.  For every pixel of the ANCHOR's grid, first[dst]
+        holds the first pixel of the frame in raster order whose trace, clamped to the picture, names it -- packed as a trace, so
+        trace_flow and trace_gather read `first` as a pool of traces in the other direction; (-1, -1) where there is none -- and
+        count[dst] how many there are.  The pools must not overlap.  Stream ordering: as frames_trace.  Returns (first, count)
+        as passed."""
+        arr, n = self._trace_jobs("trace_invert", jobs, InvertJob, "(entry, dst)")
+        if first is None and count is None:
+            raise ValueError("trace_invert: first, count or both")
+        dev, pptr, pstride, entries = self._trace_pool_args("trace_invert", pool)
+        fptr, fstride, fn = None, 0, None
+        cptr, cstride, cn = None, 0, None
+        if first is not None:
+            _, fptr, fstride, fn = self._trace_pool_args("trace_invert (first)", first)
+        if count is not None:
+            _, cptr, cstride, cn = self._trace_pool_args("trace_invert (count)", count, ("int32", 1))
+        if fn is not None and cn is not None and fn != cn:
+            raise ValueError(f"trace_invert: first has {fn} entries, count {cn}")
+        out_frames = fn if fn is not None else cn
+        self._between_stream_waits(dev, lambda: self.L.vp8hip_trace_invert_async(self.h, arr, n, pptr, pstride, entries, fptr, fstride, cptr,
+                                                                                 cstride, out_frames), "vp8hip_trace_invert_async")
+        return first, count
+
+    def trace_cover(self, count, idx, width=None, height=None, planes=("count", "seen"), dtype=None, scale=None, out=None):
+        """Entries `idx` of the COUNT pool `count` (trace_invert; any order, repeats allowed) as tensors [n, C, gh, gw] on the
+        context's device (vp8hip_trace_cover_async): the planes of `planes` ("count": min(count, 255); "seen": count != 0; or the
+        mask) in bit order, at the display size or under each output's centre at width x height (then the tensor lines up with
+        trace_flow's and trace_gather's of a FIRST pool at that size).  torch.uint8 (the default), torch.float16 or torch.float32;
+        float types: float32(float64(v) * scale[c]) with scale = one number or two, by plane (count, seen) whatever planes are
+        asked for, float32 (default 1).  `out`: a tensor of that shape and type, each frame dense, stride(0) free.  Stream
+        ordering: as frames_scaled."""
+        import torch
+        idx = [int(i) for i in idx]
+        n = len(idx)
+        dst_w, dst_h, gw, gh = self._trace_grid("trace_cover", width, height)
+        dtype = torch.uint8 if dtype is None else dtype
+        dt, mask = _elem_dtype(dtype, _RGB_DTYPES), _cover_planes(planes)
+        if dt is None or mask is None:
+            raise ValueError(f"trace_cover: dtype {dtype}, planes {planes!r}")
+        if scale is None:
+            sc = (1.0,) * 2
+        elif np.ndim(scale) == 0 and not isinstance(scale, str):
+            sc = (float(scale),) * 2
+        else:
+            sc = tuple(float(v) for v in scale) if not isinstance(scale, str) else ()
+            if len(sc) != 2:
+                raise ValueError(f"trace_cover: scale {scale!r}")
+        p = TraceCoverParams(dst_w, dst_h, dt, mask)
+        for c in range(2):
+            p.scale[c] = np.float32(sc[c])
+        if not self.L.vp8hip_trace_cover_size(self.h, ctypes.byref(p)):
+            raise ValueError(f"trace_cover: grid {gw}x{gh}: refused (sizes 1..16383)")
+        _, pptr, pstride, entries = self._trace_pool_args("trace_cover", count, ("int32", 1))
+        return self._to_torch("trace_cover", [("out", out, _RGB_DTYPES[dt], (n, bin(mask).count("1"), gh, gw))],
+                              lambda arr_out, stride: self.L.vp8hip_trace_cover_async(
+                                  self.h, (c_int * max(n, 1))(*idx), n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
+                              "vp8hip_trace_cover_async")[0]
 
     def trace_residual(self, pool, jobs, width=None, height=None, dtype=None, matrix="bt601", order="rgb", scale=None, out=None):
         """The accumulated residual of `jobs` -- a list of (fb, entry, anchor_fb): the frame buffer that holds a frame, the entry of

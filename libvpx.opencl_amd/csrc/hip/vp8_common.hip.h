@@ -207,6 +207,28 @@ struct GatherLaunch {
     GatherJob j[GATHER_MAX_JOBS];
 };
 
+// One launch of vp8hip_trace_invert_async (vp8_trace_invert.hip): the fill and the scatter take the same one
+#define INVERT_MAX_JOBS 256       // jobs per launch (kernel arguments: 8 bytes each)
+struct InvertJob {
+    int trace;                    // the pool entry read
+    int dst;                      // the entry of the FIRST and of the COUNT pool written
+};
+struct InvertLaunch {
+    int dw, dh;                   // the display size: the grid of the trace and of both outputs, and what trace values are clamped to
+    int S;                        // workgroups that share a job's rows (gridDim.x)
+    int vec;                      // the scatter's -DINVERT_LANE_QUADS variant: a lane's four trace dwords are one load (dw % 4 == 0 and pool, stride aligned to 16)
+    int first_vec, count_vec;     // fill: the entries of that pool take whole 16-byte stores (pool, stride aligned to 16)
+    InvertJob j[INVERT_MAX_JOBS];
+};
+
+// One launch of vp8hip_trace_cover_async (vp8_trace_invert.hip)
+struct CoverLaunch {
+    TraceGrid g;
+    unsigned planes;              // VP8HIP_COVER_* bits: plane c of the tensor where bit c is set, in bit order
+    float scale[2];               // by plane: COUNT, SEEN; float types
+    int idx[FLOW_MAX_FRAMES];     // COUNT pool entry of frame k of the launch
+};
+
 #define WAVE 64
 
 // Macroblock tiles of the one-MB-row-per-lane pipeline (vp8_keyframe_simt.hip has the layout): three 128-byte lines per macroblock.

@@ -2,12 +2,19 @@
 // for the kernels that do: vp8_trace_kernel for a reference's trace, and the readers of a pool entry laid under an output grid
 // (TraceGrid, vp8_common.hip.h) -- vp8_flow_*_kernel (vp8_trace.hip), vp8_anchor_*_kernel (vp8_trace_residual.hip) and
 // vp8_gather_*_kernel (vp8_trace_gather.hip); and vp8_trace_wear.hip, whose pool has a trace pool's geometry and whose dwords are
-// counters: vp8_wear_kernel gathers a reference's as vp8_trace_kernel does, vp8_wear_*_kernel reads an entry through trace_read4.
+// counters: vp8_wear_kernel gathers a reference's as vp8_trace_kernel does, vp8_wear_*_kernel reads an entry through trace_read4;
+// and vp8_trace_invert.hip: vp8_invert_*_kernel scatters a trace onto the anchor's grid, vp8_cover_*_kernel reads an entry of its
+// COUNT pool -- a trace pool's geometry again, the dwords counts -- through trace_read4.
 //
 // THE CLAMP.  In vp8_trace.hip a trace value is data; in the other two files it becomes an address.  There every value goes through
 // trace_clamp before anything is formed from it, so a pool entry nobody wrote yields garbage values and never a read outside the
 // picture; what lies behind the picture -- the anchor's frame buffer, the job's source tensor -- is the caller's to reach from a
 // position inside it.  trace_clamp is the one place that makes a position of a trace dword: a reader does not unpack one by itself.
+// vp8_trace_invert.hip is a fourth file where a trace value becomes an address (vp8_trace_wear.hip is none: its positions come from
+// the slot's vectors), and the first where that address is WRITTEN: vp8_invert_*_kernel does an atomic on dword ay * dw + ax of the
+// job's destination entries.  The rule is the same and now guards writes -- the position comes out of trace_clamp, 0 <= ax < dw and
+// 0 <= ay < dh, and nothing else of the dword takes part in the address --, so a trace entry nobody wrote scatters garbage inside
+// the destination entries, d_w * d_h dwords each, and never a byte outside them.
 #pragma once
 #include "vp8_tensor_out.hip.h"
 

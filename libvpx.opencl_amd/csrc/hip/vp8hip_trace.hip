@@ -1,10 +1,12 @@
-// vp8hip_frames_trace_async, vp8hip_trace_flow_async, vp8hip_trace_residual_async, vp8hip_trace_gather_async and the trace's wear,
-// vp8hip_frames_wear_async and vp8hip_trace_wear_async (include/vp8hip.h):
+// vp8hip_frames_trace_async, vp8hip_trace_flow_async, vp8hip_trace_residual_async, vp8hip_trace_gather_async, the trace's wear,
+// vp8hip_frames_wear_async and vp8hip_trace_wear_async, and its inverse, vp8hip_trace_invert_async and vp8hip_trace_cover_async
+// (include/vp8hip.h):
 // accumulated motion -- every pixel traced back through the frames it was predicted from to the key frame that started the group -- in
 // a pool in the caller's device memory, a pool entry as a flow tensor, a frame minus its anchor picture gathered at its trace as a
 // residual tensor, and a tensor of the caller's gathered at a trace.  The plans and the checks are made here, once per call; the
 // kernels are in vp8_trace.hip, vp8_trace_residual.hip, vp8_trace_gather.hip and vp8_trace_wear.hip (what happened to a pixel along its
-// trace: four counters a pixel in a pool of its own, chained as the trace is, and a pool entry as a tensor).  The trace
+// trace: four counters a pixel in a pool of its own, chained as the trace is, and a pool entry as a tensor) and vp8_trace_invert.hip
+// (a trace scattered onto the anchor's grid: first descendant and descendant count per anchor pixel, and a count entry as a tensor).  The trace
 // reads the slots' records and vectors (also on a vp8hip_configure_pooled context) and the pool entries its jobs name; the slots'
 // header bits come with the launch, as of this call: nothing is allocated on the device, copied or synchronised.
 #include "vp8hip_ctx.hip.h"
@@ -20,6 +22,16 @@ extern "C" __global__ void vp8_flow_f32_kernel(FLOW_ARGS);
 extern "C" __global__ void vp8_wear_u8_kernel(WEAR_ARGS);
 extern "C" __global__ void vp8_wear_f16_kernel(WEAR_ARGS);
 extern "C" __global__ void vp8_wear_f32_kernel(WEAR_ARGS);
+#define INVERT_FILL_ARGS uint8_t *first, size_t first_stride, uint8_t *count, size_t count_stride, InvertLaunch L
+extern "C" __global__ void vp8_invert_fill_kernel(INVERT_FILL_ARGS);
+#define INVERT_ARGS const uint8_t *pool, size_t pool_stride, uint8_t *first, size_t first_stride, uint8_t *count, size_t count_stride, InvertLaunch L
+extern "C" __global__ void vp8_invert_first_kernel(INVERT_ARGS);
+extern "C" __global__ void vp8_invert_count_kernel(INVERT_ARGS);
+extern "C" __global__ void vp8_invert_both_kernel(INVERT_ARGS);
+#define COVER_ARGS const uint8_t *pool, size_t pool_stride, uint8_t *dst, size_t dst_stride, CoverLaunch L
+extern "C" __global__ void vp8_cover_u8_kernel(COVER_ARGS);
+extern "C" __global__ void vp8_cover_f16_kernel(COVER_ARGS);
+extern "C" __global__ void vp8_cover_f32_kernel(COVER_ARGS);
 
 #define ANCHOR_ARGS const uint8_t *raster, size_t fb_stride, const uint8_t *tiles, size_t tile_frame, const uint8_t *pool, size_t pool_stride, \
                     uint8_t *dst, size_t dst_stride, AnchorLaunch L
@@ -46,6 +58,7 @@ extern "C" __global__ void vp8_gather_rows_bilinear_4_kernel(GATHER_ARGS);
 #define ANCHOR_PART_QUADS 4096                  // ... and of the residual kernel: its loads wait on the trace's, so more waves in flight
 #define GATHER_PART_QUADS 2048                  // ... and of the planar gather kernels, which make GATHER_GROUP_CH channels of each
 #define GATHER_GROUP_CH 8                       // channels a workgroup of the planar gather kernels makes
+#define INVERT_PART_QUADS 4096                  // groups of four trace pixels a workgroup of the fill and the scatter kernels walks
 
 extern "C" size_t vp8hip_trace_size(const vp8hip_ctx *c) { return c && c->width ? (size_t)4 * c->width * c->height : 0; }
 
@@ -235,6 +248,116 @@ extern "C" int vp8hip_trace_wear_async(vp8hip_ctx *c, const int *idx, int n, con
         const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
         memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
         hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.g.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
+                           (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+// [p, + stride * frames) and [q, + qstride * qframes) overlap -- vp8hip_trace_gather_async's rule for src / dst: the span checks have
+// bounded the products, so neither wraps, and the ends saturate
+static bool spans_overlap(const void *p, size_t stride, int frames, const void *q, size_t qstride, int qframes)
+{
+    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+    const size_t plen = stride * (size_t)frames, qlen = qstride * (size_t)qframes;
+    const uintptr_t p1 = p0 + plen < p0 ? UINTPTR_MAX : p0 + plen, q1 = q0 + qlen < q0 ? UINTPTR_MAX : q0 + qlen;
+    return p0 < q1 && q0 < p1;
+}
+
+extern "C" int vp8hip_trace_invert_async(vp8hip_ctx *c, const vp8hip_invert_job *jobs, int n, const void *pool, size_t pool_stride, int pool_frames,
+                                         void *first, size_t first_stride, void *count, size_t count_stride, int out_frames)
+{
+    const char *who = "vp8hip_trace_invert_async";
+    if (!c || !jobs || n < 1 || !pool || !c->width) return fail(c, -2, "%s: bad arguments", who);
+    if (!first && !count) return fail(c, -2, "%s: neither a FIRST nor a COUNT pool", who);
+    if (int rc = trace_check_pool(c, "vp8hip_trace_invert_async (pool)", pool, pool_stride, pool_frames)) return rc;
+    if (first)
+        if (int rc = trace_check_pool(c, "vp8hip_trace_invert_async (first)", first, first_stride, out_frames)) return rc;
+    if (count)
+        if (int rc = trace_check_pool(c, "vp8hip_trace_invert_async (count)", count, count_stride, out_frames)) return rc;
+    std::vector<uint8_t> mark((size_t)out_frames, 0);        // 1: some job's destination
+    for (int i = 0; i < n; i++) {
+        if (jobs[i].trace < 0 || jobs[i].trace >= pool_frames) return fail(c, -2, "%s: job %d: trace %d outside the pool", who, i, jobs[i].trace);
+        if (jobs[i].dst < 0 || jobs[i].dst >= out_frames) return fail(c, -2, "%s: job %d: destination %d outside the pools", who, i, jobs[i].dst);
+        uint8_t &m = mark[(size_t)jobs[i].dst];
+        if (m) return fail(c, -2, "%s: job %d: destination %d is another job's destination", who, i, jobs[i].dst);
+        m = 1;
+    }
+    if (first && spans_overlap(pool, pool_stride, pool_frames, first, first_stride, out_frames))
+        return fail(c, -2, "%s: the trace pool and the FIRST pool overlap", who);
+    if (count && spans_overlap(pool, pool_stride, pool_frames, count, count_stride, out_frames))
+        return fail(c, -2, "%s: the trace pool and the COUNT pool overlap", who);
+    if (first && count && spans_overlap(first, first_stride, out_frames, count, count_stride, out_frames))
+        return fail(c, -2, "%s: the FIRST pool and the COUNT pool overlap", who);
+    HIPCHK(c, hipSetDevice(c->device));
+
+    InvertLaunch L;
+    memset(&L, 0, offsetof(InvertLaunch, j));
+    L.dw = c->width; L.dh = c->height;
+    const long long quads = (long long)((L.dw + 3) >> 2) * L.dh;
+    L.S = (int)((quads + INVERT_PART_QUADS - 1) / INVERT_PART_QUADS);
+    if (L.S > L.dh) L.S = L.dh;
+    L.vec = L.dw % 4 == 0 && (uintptr_t)pool % 16 == 0 && pool_stride % 16 == 0;
+    L.first_vec = first && (uintptr_t)first % 16 == 0 && first_stride % 16 == 0;
+    L.count_vec = count && (uintptr_t)count % 16 == 0 && count_stride % 16 == 0;
+    void (*const kernel)(INVERT_ARGS) = !count ? vp8_invert_first_kernel : !first ? vp8_invert_count_kernel : vp8_invert_both_kernel;
+    for (int i0 = 0; i0 < n; i0 += INVERT_MAX_JOBS) {
+        const int m = n - i0 < INVERT_MAX_JOBS ? n - i0 : INVERT_MAX_JOBS;
+        for (int k = 0; k < m; k++) {
+            L.j[k].trace = jobs[i0 + k].trace;
+            L.j[k].dst = jobs[i0 + k].dst;
+        }
+        // the fill, and behind it on the stream the scatter into what it wrote
+        hipLaunchKernelGGL(vp8_invert_fill_kernel, dim3((unsigned)L.S, (unsigned)m), dim3(256), 0, c->stream, (uint8_t *)first, first_stride,
+                           (uint8_t *)count, count_stride, L);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(kernel, dim3((unsigned)L.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride, (uint8_t *)first,
+                           first_stride, (uint8_t *)count, count_stride, L);
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+// the grid of p on context c; false for what the call refuses on p alone
+static bool cover_grid(const vp8hip_ctx *c, const vp8hip_trace_cover *p, int &gw, int &gh)
+{
+    const unsigned all = VP8HIP_COVER_COUNT | VP8HIP_COVER_SEEN;
+    return p && p->dtype >= 0 && p->dtype <= 2 && p->planes && !(p->planes & ~all) && trace_out_grid(c, p->dst_w, p->dst_h, gw, gh);
+}
+
+extern "C" size_t vp8hip_trace_cover_size(const vp8hip_ctx *c, const vp8hip_trace_cover *p)
+{
+    int gw, gh;
+    return cover_grid(c, p, gw, gh) ? (size_t)__builtin_popcount(p->planes) * gh * gw * vp8hip_elem_size(p->dtype, 1) : 0;
+}
+
+extern "C" int vp8hip_trace_cover_async(vp8hip_ctx *c, const int *idx, int n, const vp8hip_trace_cover *p, const void *count, size_t count_stride,
+                                        int count_frames, void *dst, size_t dst_stride)
+{
+    const char *who = "vp8hip_trace_cover_async";
+    if (!c || !idx || n < 1 || !p || !count || !dst || !c->width) return fail(c, -2, "%s: bad arguments", who);
+    int gw, gh;
+    if (!cover_grid(c, p, gw, gh))
+        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), type %d, planes 0x%x", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE, p->dtype,
+                    p->planes);
+    if (int rc = trace_check_pool(c, "vp8hip_trace_cover_async (count)", count, count_stride, count_frames)) return rc;
+    for (int i = 0; i < n; i++)
+        if (idx[i] < 0 || idx[i] >= count_frames) return fail(c, -2, "%s: entry %d outside the pool", who, idx[i]);
+    const size_t es = (size_t)vp8hip_elem_size(p->dtype, 1);
+    const size_t size = (size_t)__builtin_popcount(p->planes) * gh * gw * es;
+    if (int rc = vp8hip_check_dst(c, "vp8hip_trace_cover_async (dst)", dst, dst_stride, size, es, n)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+
+    CoverLaunch L;
+    memset(&L, 0, offsetof(CoverLaunch, idx));
+    L.g = trace_grid(c, gw, gh, es, FLOW_PART_QUADS, dst, dst_stride);
+    L.planes = p->planes;
+    L.scale[0] = p->scale[0]; L.scale[1] = p->scale[1];
+    void (*const kernels[3])(COVER_ARGS) = {vp8_cover_u8_kernel, vp8_cover_f16_kernel, vp8_cover_f32_kernel};
+    for (int i0 = 0; i0 < n; i0 += FLOW_MAX_FRAMES) {
+        const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
+        memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
+        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.g.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)count, count_stride,
                            (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
         HIPCHK(c, hipGetLastError());
     }
