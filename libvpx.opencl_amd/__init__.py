@@ -393,23 +393,24 @@ SIDE_PLANES = {"ref": 1, "mode": 2, "skip": 4, "segment": 8, "qindex": 16, "code
 SIDE_I16, SIDE_F16, SIDE_F32 = 0, 1, 2
 
 
-def _side_planes(planes):
-    """names (any order; the tensor's planes come in bit order) or the mask itself -> the mask, None for an unknown plane"""
+def _plane_mask(planes, table, allow_empty):
+    """names of `table` (any order; the tensor's planes come in bit order) or the mask itself -> the mask, None for an unknown plane
+    and, unless allow_empty, for none"""
     if isinstance(planes, int):
-        return planes if 0 <= planes < 64 else None
+        return planes if (0 if allow_empty else 1) <= planes <= sum(table.values()) else None
     mask = 0
     for name in planes:
-        if name not in SIDE_PLANES:
+        if name not in table:
             return None
-        mask |= SIDE_PLANES[name]
-    return mask
+        mask |= table[name]
+    return mask if mask or allow_empty else None
 
 
 def side_sizes(gw, gh, mv_dtype=SIDE_I16, planes=("ref", "mode", "skip")):
     """(bytes of one frame's mv tensor, bytes of its info tensor) of Vp8Hip.frames_side on a grid of gw x gh (vp8hip_side_mv_size,
     vp8hip_side_info_size): 2 * gh * gw * element size and planes * gh * gw; (0, 0) for a size outside 1..16383, an unknown type or
     plane.  For the native grid gw, gh = 4 * mb_cols, 4 * mb_rows."""
-    dt, mask = _elem_dtype(mv_dtype, _INT16_DTYPES), _side_planes(planes)
+    dt, mask = _elem_dtype(mv_dtype, _INT16_DTYPES), _plane_mask(planes, SIDE_PLANES, True)
     if dt is None or mask is None or gw == 0 or gh == 0:         # (0 x 0 would ask for the native grid, which needs a context)
         return 0, 0
     L, p = load_hip(), SideParams(int(gw), int(gh), dt, mask)
@@ -436,53 +437,30 @@ WEAR_PLANES = {"hops": 1, "intra": 2, "edge": 4, "coded": 8}   # VP8HIP_WEAR_*: 
 WEAR_U8, WEAR_F16, WEAR_F32 = 0, 1, 2
 
 
-def _wear_planes(planes):
-    """names (any order; the tensor's planes come in bit order) or the mask itself -> the mask, None for an unknown plane or none"""
-    if isinstance(planes, int):
-        return planes if 0 < planes < 16 else None
-    mask = 0
-    for name in planes:
-        if name not in WEAR_PLANES:
-            return None
-        mask |= WEAR_PLANES[name]
-    return mask or None
+def _entry_tensor_size(gw, gh, planes, dtype, table, params, size):
+    """what trace_wear_size and trace_cover_size are: planes of `table`, the ctypes struct and the library's size call"""
+    dt, mask = _elem_dtype(dtype, _RGB_DTYPES), _plane_mask(planes, table, False)
+    if dt is None or mask is None or gw == 0 or gh == 0:         # (0 x 0 would ask for the display size, which needs a context)
+        return 0
+    p = params(int(gw), int(gh), dt, mask)
+    return int(getattr(load_hip(), size)(None, ctypes.byref(p)))
 
 
 def trace_wear_size(gw, gh, planes=("hops", "intra", "edge", "coded"), dtype=0):
     """bytes of one frame's tensor of Vp8Hip.trace_wear on a grid of gw x gh (vp8hip_trace_wear_size): planes * gh * gw elements; 0 for
     a size outside 1..16383, an unknown type, no plane or an unknown one.  dtype: WEAR_U8 / WEAR_F16 / WEAR_F32 or the torch / numpy
     type's name.  For the display size pass the display size."""
-    dt, mask = _elem_dtype(dtype, _RGB_DTYPES), _wear_planes(planes)
-    if dt is None or mask is None or gw == 0 or gh == 0:         # (0 x 0 would ask for the display size, which needs a context)
-        return 0
-    p = TraceWearParams(int(gw), int(gh), dt, mask)
-    return int(load_hip().vp8hip_trace_wear_size(None, ctypes.byref(p)))
+    return _entry_tensor_size(gw, gh, planes, dtype, WEAR_PLANES, TraceWearParams, "vp8hip_trace_wear_size")
 
 
 COVER_PLANES = {"count": 1, "seen": 2}                        # VP8HIP_COVER_*: bit order = plane order
-
-
-def _cover_planes(planes):
-    """names (any order; the tensor's planes come in bit order) or the mask itself -> the mask, None for an unknown plane or none"""
-    if isinstance(planes, int):
-        return planes if 0 < planes < 4 else None
-    mask = 0
-    for name in planes:
-        if name not in COVER_PLANES:
-            return None
-        mask |= COVER_PLANES[name]
-    return mask or None
 
 
 def trace_cover_size(gw, gh, planes=("count", "seen"), dtype=0):
     """bytes of one frame's tensor of Vp8Hip.trace_cover on a grid of gw x gh (vp8hip_trace_cover_size): planes * gh * gw elements; 0
     for a size outside 1..16383, an unknown type, no plane or an unknown one.  dtype: WEAR_U8 / WEAR_F16 / WEAR_F32 or the torch /
     numpy type's name.  For the display size pass the display size."""
-    dt, mask = _elem_dtype(dtype, _RGB_DTYPES), _cover_planes(planes)
-    if dt is None or mask is None or gw == 0 or gh == 0:         # (0 x 0 would ask for the display size, which needs a context)
-        return 0
-    p = TraceCoverParams(int(gw), int(gh), dt, mask)
-    return int(load_hip().vp8hip_trace_cover_size(None, ctypes.byref(p)))
+    return _entry_tensor_size(gw, gh, planes, dtype, COVER_PLANES, TraceCoverParams, "vp8hip_trace_cover_size")
 
 
 GATHER_FILTERS = {"nearest": 0, "bilinear": 1}              # VP8HIP_GATHER_NEAREST, BILINEAR
@@ -1018,7 +996,7 @@ class Vp8Hip:
         n = len(slots)
         native, gw, gh = self._grid("frames_side", width, height, 4)
         mv_dtype = torch.int16 if mv_dtype is None else mv_dtype
-        dt, mask = _elem_dtype(mv_dtype, _INT16_DTYPES), _side_planes(planes)
+        dt, mask = _elem_dtype(mv_dtype, _INT16_DTYPES), _plane_mask(planes, SIDE_PLANES, True)
         if dt is None or mask is None:
             raise ValueError(f"frames_side: mv_dtype {mv_dtype}, planes {planes!r}")
         want_mv = out_mv is not False
@@ -1106,6 +1084,55 @@ class Vp8Hip:
             raise ValueError(f"{who}: pool must be {'an' if name[0] == 'i' else 'a'} {name} tensor [n, {', '.join(str(v) for v in inner)}], each entry dense, on {dev}")
         return dev, c_void_p(pool.data_ptr()), pool.stride(0) * (4 // per), int(pool.shape[0])
 
+    def _chain_frames(self, who, jobs, pool, kind):
+        """what frames_trace and frames_wear are: vp8hip_<who>_async over `jobs`, chaining the entries of a pool of `kind`
+        (_trace_pool_args)"""
+        arr, n = (jobs, len(jobs)) if isinstance(jobs, ctypes.Array) else (self.job_array(list(jobs)), len(jobs))
+        dev, ptr, stride, entries = self._trace_pool_args(who, pool, kind)
+        call = f"vp8hip_{who}_async"
+        self._between_stream_waits(dev, lambda: getattr(self.L, call)(self.h, arr, n, ptr, stride, entries), call)
+        return pool
+
+    # what trace_flow, trace_wear and trace_cover differ in: the ctypes struct, the library's calls, the tensor types, the planes
+    # there are (None: no choice, two always; then scale may be "pixels"), the scales and the pool's kind (_trace_pool_args)
+    _ENTRY_CALLS = {"trace_flow": (TraceFlowParams, "vp8hip_trace_flow", _INT16_DTYPES, None, 2, ("int16", 2)),
+                    "trace_wear": (TraceWearParams, "vp8hip_trace_wear", _RGB_DTYPES, WEAR_PLANES, 4, ("uint8", 4)),
+                    "trace_cover": (TraceCoverParams, "vp8hip_trace_cover", _RGB_DTYPES, COVER_PLANES, 2, ("int32", 1))}
+
+    def _trace_entries(self, who, pool, idx, width, height, planes, dtype, scale, out):
+        """what trace_flow, trace_wear and trace_cover are: entries `idx` of `pool` as tensors [n, C, gh, gw] by the library's call"""
+        import torch
+        params, call, names, table, nscale, kind = self._ENTRY_CALLS[who]
+        idx = [int(i) for i in idx]
+        n = len(idx)
+        dst_w, dst_h, gw, gh = self._trace_grid(who, width, height)
+        dtype = getattr(torch, names[0]) if dtype is None else dtype
+        dt, mask = _elem_dtype(dtype, names), 3 if table is None else _plane_mask(planes, table, False)
+        if dt is None or mask is None:
+            raise ValueError(f"{who}: dtype {dtype}" + ("" if table is None else f", planes {planes!r}"))
+        if scale is None:
+            sc = (1.0,) * nscale
+        elif isinstance(scale, str):
+            if table is not None or scale != "pixels":
+                raise ValueError(f"{who}: scale {scale!r}")
+            sc = (gw / self.width, gh / self.height)
+        elif table is not None and np.ndim(scale) == 0:
+            sc = (float(scale),) * nscale
+        else:
+            sc = tuple(float(v) for v in scale)
+            if table is not None and len(sc) != nscale:
+                raise ValueError(f"{who}: scale {scale!r}")
+        p = params(dst_w, dst_h, dt) if table is None else params(dst_w, dst_h, dt, mask)
+        for c in range(nscale):
+            p.scale[c] = np.float32(sc[c])
+        if not getattr(self.L, call + "_size")(self.h, ctypes.byref(p)):
+            raise ValueError(f"{who}: grid {gw}x{gh}: refused (sizes 1..16383)")
+        _, pptr, pstride, entries = self._trace_pool_args(who, pool, kind)
+        return self._to_torch(who, [("out", out, names[dt], (n, bin(mask).count("1"), gh, gw))],
+                              lambda arr_out, stride: getattr(self.L, call + "_async")(
+                                  self.h, (c_int * max(n, 1))(*idx), n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
+                              call + "_async")[0]
+
     def frames_trace(self, jobs, pool):
         """The traces of `jobs` -- a list of (ir_slot, dst, (last, golden, alt)) as decode takes it, dst and the three references read
         as entries of `pool` (trace_pool; -1 or refs None: no trace) -- written into pool[dst] (vp8hip_frames_trace_async): a key
@@ -1113,11 +1140,7 @@ class Vp8Hip:
         into the trace of the reference its macroblock was predicted from.  A pool numbered like the frame buffers takes the very
         jobs of decode (a vp8hip_job array made by job_array is taken as it is).  Jobs of one call are independent.  Stream
         ordering, the `import torch` first rule and the remark on record_stream: as frames_scaled.  Returns pool."""
-        arr, n = (jobs, len(jobs)) if isinstance(jobs, ctypes.Array) else (self.job_array(list(jobs)), len(jobs))
-        dev, ptr, stride, entries = self._trace_pool_args("frames_trace", pool)
-        self._between_stream_waits(dev, lambda: self.L.vp8hip_frames_trace_async(self.h, arr, n, ptr, stride, entries),
-                                   "vp8hip_frames_trace_async")
-        return pool
+        return self._chain_frames("frames_trace", jobs, pool, ("int16", 2))
 
     def trace_flow(self, pool, idx, width=None, height=None, dtype=None, scale=None, out=None):
         """Entries `idx` of `pool` (any order, repeats allowed) as flow tensors [n, 2, gh, gw] on the context's device
@@ -1127,31 +1150,7 @@ class Vp8Hip:
         float32(float64(a) * scale[c]) with scale = (x, y) float32 numbers (default 1, 1); scale="pixels" is (gw / d_w, gh / d_h),
         computed in float64 and rounded once: the flow in pixels of the tensor.  `out`: a tensor of that shape and type, each
         frame dense, stride(0) free.  Stream ordering: as frames_scaled."""
-        import torch
-        idx = [int(i) for i in idx]
-        n = len(idx)
-        dst_w, dst_h, gw, gh = self._trace_grid("trace_flow", width, height)
-        dtype = torch.int16 if dtype is None else dtype
-        dt = _elem_dtype(dtype, _INT16_DTYPES)
-        if dt is None:
-            raise ValueError(f"trace_flow: dtype {dtype}")
-        if scale is None:
-            sc = (1.0, 1.0)
-        elif isinstance(scale, str):
-            if scale != "pixels":
-                raise ValueError(f"trace_flow: scale {scale!r}")
-            sc = (gw / self.width, gh / self.height)
-        else:
-            sc = tuple(float(v) for v in scale)
-        p = TraceFlowParams(dst_w, dst_h, dt)
-        p.scale[0], p.scale[1] = np.float32(sc[0]), np.float32(sc[1])
-        if not self.L.vp8hip_trace_flow_size(self.h, ctypes.byref(p)):
-            raise ValueError(f"trace_flow: grid {gw}x{gh}: refused (sizes 1..16383)")
-        _, pptr, pstride, entries = self._trace_pool_args("trace_flow", pool)
-        return self._to_torch("trace_flow", [("out", out, _INT16_DTYPES[dt], (n, 2, gh, gw))],
-                              lambda arr_out, stride: self.L.vp8hip_trace_flow_async(
-                                  self.h, (c_int * max(n, 1))(*idx), n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
-                              "vp8hip_trace_flow_async")[0]
+        return self._trace_entries("trace_flow", pool, idx, width, height, None, dtype, scale, out)
 
     def wear_pool(self, n):
         """a pool of n wear entries for frames_wear on the context's device: a torch.uint8 tensor [n, d_h, d_w, 4], the counters (hops,
@@ -1167,11 +1166,7 @@ class Vp8Hip:
         frame's is zero; an inter frame's is the wear of the reference at the position the trace's hop goes to, plus the hop's
         increments.  A pool numbered like the trace pool takes the very jobs of frames_trace.  Stream ordering: as frames_trace.
         Returns pool."""
-        arr, n = (jobs, len(jobs)) if isinstance(jobs, ctypes.Array) else (self.job_array(list(jobs)), len(jobs))
-        dev, ptr, stride, entries = self._trace_pool_args("frames_wear", pool, ("uint8", 4))
-        self._between_stream_waits(dev, lambda: self.L.vp8hip_frames_wear_async(self.h, arr, n, ptr, stride, entries),
-                                   "vp8hip_frames_wear_async")
-        return pool
+        return self._chain_frames("frames_wear", jobs, pool, ("uint8", 4))
 
     def trace_wear(self, pool, idx, width=None, height=None, planes=("hops", "intra", "edge", "coded"), dtype=None, scale=None, out=None):
         """Entries `idx` of the wear pool `pool` (any order, repeats allowed) as tensors [n, C, gh, gw] on the context's device
@@ -1181,32 +1176,7 @@ class Vp8Hip:
         float32(float64(v) * scale[c]) with scale = one number or four, by counter (hops, intra, edge, coded) whatever planes are
         asked for, float32 (default 1).  `out`: a tensor of that shape and type, each frame dense, stride(0) free.  Stream
         ordering: as frames_scaled."""
-        import torch
-        idx = [int(i) for i in idx]
-        n = len(idx)
-        dst_w, dst_h, gw, gh = self._trace_grid("trace_wear", width, height)
-        dtype = torch.uint8 if dtype is None else dtype
-        dt, mask = _elem_dtype(dtype, _RGB_DTYPES), _wear_planes(planes)
-        if dt is None or mask is None:
-            raise ValueError(f"trace_wear: dtype {dtype}, planes {planes!r}")
-        if scale is None:
-            sc = (1.0,) * 4
-        elif np.ndim(scale) == 0 and not isinstance(scale, str):
-            sc = (float(scale),) * 4
-        else:
-            sc = tuple(float(v) for v in scale) if not isinstance(scale, str) else ()
-            if len(sc) != 4:
-                raise ValueError(f"trace_wear: scale {scale!r}")
-        p = TraceWearParams(dst_w, dst_h, dt, mask)
-        for c in range(4):
-            p.scale[c] = np.float32(sc[c])
-        if not self.L.vp8hip_trace_wear_size(self.h, ctypes.byref(p)):
-            raise ValueError(f"trace_wear: grid {gw}x{gh}: refused (sizes 1..16383)")
-        _, pptr, pstride, entries = self._trace_pool_args("trace_wear", pool, ("uint8", 4))
-        return self._to_torch("trace_wear", [("out", out, _RGB_DTYPES[dt], (n, bin(mask).count("1"), gh, gw))],
-                              lambda arr_out, stride: self.L.vp8hip_trace_wear_async(
-                                  self.h, (c_int * max(n, 1))(*idx), n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
-                              "vp8hip_trace_wear_async")[0]
+        return self._trace_entries("trace_wear", pool, idx, width, height, planes, dtype, scale, out)
 
     def cover_pools(self, n):
         """(FIRST, COUNT): pools of n entries each for trace_invert on the context's device.  FIRST is a torch.int16 tensor
@@ -1248,32 +1218,7 @@ class Vp8Hip:
         float types: float32(float64(v) * scale[c]) with scale = one number or two, by plane (count, seen) whatever planes are
         asked for, float32 (default 1).  `out`: a tensor of that shape and type, each frame dense, stride(0) free.  Stream
         ordering: as frames_scaled."""
-        import torch
-        idx = [int(i) for i in idx]
-        n = len(idx)
-        dst_w, dst_h, gw, gh = self._trace_grid("trace_cover", width, height)
-        dtype = torch.uint8 if dtype is None else dtype
-        dt, mask = _elem_dtype(dtype, _RGB_DTYPES), _cover_planes(planes)
-        if dt is None or mask is None:
-            raise ValueError(f"trace_cover: dtype {dtype}, planes {planes!r}")
-        if scale is None:
-            sc = (1.0,) * 2
-        elif np.ndim(scale) == 0 and not isinstance(scale, str):
-            sc = (float(scale),) * 2
-        else:
-            sc = tuple(float(v) for v in scale) if not isinstance(scale, str) else ()
-            if len(sc) != 2:
-                raise ValueError(f"trace_cover: scale {scale!r}")
-        p = TraceCoverParams(dst_w, dst_h, dt, mask)
-        for c in range(2):
-            p.scale[c] = np.float32(sc[c])
-        if not self.L.vp8hip_trace_cover_size(self.h, ctypes.byref(p)):
-            raise ValueError(f"trace_cover: grid {gw}x{gh}: refused (sizes 1..16383)")
-        _, pptr, pstride, entries = self._trace_pool_args("trace_cover", count, ("int32", 1))
-        return self._to_torch("trace_cover", [("out", out, _RGB_DTYPES[dt], (n, bin(mask).count("1"), gh, gw))],
-                              lambda arr_out, stride: self.L.vp8hip_trace_cover_async(
-                                  self.h, (c_int * max(n, 1))(*idx), n, ctypes.byref(p), pptr, pstride, entries, arr_out, stride),
-                              "vp8hip_trace_cover_async")[0]
+        return self._trace_entries("trace_cover", count, idx, width, height, planes, dtype, scale, out)
 
     def trace_residual(self, pool, jobs, width=None, height=None, dtype=None, matrix="bt601", order="rgb", scale=None, out=None):
         """The accumulated residual of `jobs` -- a list of (fb, entry, anchor_fb): the frame buffer that holds a frame, the entry of

@@ -154,19 +154,13 @@ struct TraceGrid {
     int xmode;                    // SIDE_X_DISPLAY (gw is the display width: sx = x) or SIDE_X_ANY
 };
 
-// One launch of vp8hip_trace_flow_async (vp8_trace.hip)
+// One launch of a call that hands pool entries out as tensors (entry_tensor_body, vp8_trace_read.hip.h): vp8hip_trace_flow_async
+// (vp8_trace.hip), vp8hip_trace_wear_async (vp8_trace_wear.hip) and vp8hip_trace_cover_async (vp8_trace_invert.hip)
 #define FLOW_MAX_FRAMES 512       // pool entries per launch (kernel arguments)
-struct FlowLaunch {
+struct EntryLaunch {
     TraceGrid g;
-    float scale[2];               // x, y; float types
-    int idx[FLOW_MAX_FRAMES];     // pool entry of frame k of the launch
-};
-
-// One launch of vp8hip_trace_wear_async (vp8_trace_wear.hip); vp8hip_frames_wear_async launches with the trace's TraceLaunch
-struct WearLaunch {
-    TraceGrid g;
-    unsigned planes;              // VP8HIP_WEAR_* bits: counter c is a plane of the tensor where bit c is set, in bit order
-    float scale[4];               // by counter: HOPS, INTRA, EDGE, CODED; float types
+    unsigned planes;              // wear, cover: VP8HIP_WEAR_* / VP8HIP_COVER_* bits, plane c of the tensor where bit c is set, in bit order; flow: not read
+    float scale[4];               // by plane (flow: x, y; wear: HOPS, INTRA, EDGE, CODED; cover: COUNT, SEEN); float types
     int idx[FLOW_MAX_FRAMES];     // pool entry of frame k of the launch
 };
 
@@ -219,14 +213,6 @@ struct InvertLaunch {
     int vec;                      // the scatter's -DINVERT_LANE_QUADS variant: a lane's four trace dwords are one load (dw % 4 == 0 and pool, stride aligned to 16)
     int first_vec, count_vec;     // fill: the entries of that pool take whole 16-byte stores (pool, stride aligned to 16)
     InvertJob j[INVERT_MAX_JOBS];
-};
-
-// One launch of vp8hip_trace_cover_async (vp8_trace_invert.hip)
-struct CoverLaunch {
-    TraceGrid g;
-    unsigned planes;              // VP8HIP_COVER_* bits: plane c of the tensor where bit c is set, in bit order
-    float scale[2];               // by plane: COUNT, SEEN; float types
-    int idx[FLOW_MAX_FRAMES];     // COUNT pool entry of frame k of the launch
 };
 
 #define WAVE 64

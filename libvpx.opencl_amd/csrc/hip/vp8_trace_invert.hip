@@ -21,9 +21,8 @@
 // THE CLAMP (vp8_trace_read.hip.h) guards WRITES here: every trace value goes through trace_clamp before an address is formed from
 // it, so a trace entry nobody wrote scatters garbage inside the job's two destination entries and never a byte outside them.
 //
-// vp8_cover_*_kernel.  A COUNT entry as a tensor [planes][gh][gw]: output (y, x) takes count c at (sy, sx) by the centre map, read
-// through trace_read4 -- the pool has a trace pool's geometry --; plane COUNT holds min(c, 255), plane SEEN c != 0, converted as the
-// wear tensors are.  Counts are data there and never addresses.
+// vp8_cover_*_kernel is entry_tensor_body (vp8_trace_read.hip.h) with CoverPlanes: a COUNT entry as a tensor [planes][gh][gw], of
+// the count c an output takes plane COUNT holding min(c, 255) and plane SEEN c != 0.  Counts are data there and never addresses.
 #include "vp8_trace_read.hip.h"
 #include "vp8hip.h"
 
@@ -118,52 +117,11 @@ INVERT_KERNEL(vp8_invert_first_kernel, true, false)
 INVERT_KERNEL(vp8_invert_count_kernel, false, true)
 INVERT_KERNEL(vp8_invert_both_kernel, true, true)
 
-template <int DTYPE>
-__device__ __forceinline__ void cover_body(const uint8_t *__restrict__ pool, size_t pool_stride, uint8_t *__restrict__ dst, size_t dst_stride,
-                                           const CoverLaunch &L)
-{
-    typedef typename TensorElem<DTYPE>::T elem_t;
-    constexpr int ES = (int)sizeof(elem_t);
-    const int f = (int)blockIdx.y;
-    const int gw = L.g.gw, gh = L.g.gh;
-    int y0, y1;
-    tensor_share(0, gh, L.g.S, (int)blockIdx.x, y0, y1);
-    const uint8_t *src = pool + pool_stride * (size_t)L.idx[f];
-    uint8_t *D = dst + dst_stride * f;
-    const size_t plane = (size_t)gh * gw;
-    const int nrows = y1 - y0;
-#pragma unroll 1
-    for (TensorWalk t((gw + 3) >> 2); t.row < nrows; t.next()) {
-        const int y = y0 + t.row, x = t.col << 2;
-        const TraceQuad q = trace_read4(src, L.g, y, x);
-        uint8_t *o = D + ((size_t)y * gw + x) * ES;
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            if (!(L.planes >> c & 1u)) continue;         // (the same for every lane)
-            int v[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) v[i] = c == 0 ? (int)min(q.T[i], 255u) : (int)(q.T[i] != 0u);
-            unsigned e[4];
-            tensor_values4<DTYPE>(v, L.scale[c], e);
-            if (L.g.vec) tensor_store4<ES>(o, e);
-            else {
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-                    if (x + i < gw) ((GLOBAL_AS elem_t *)o)[i] = (elem_t)e[i];
-            }
-            o += plane * ES;
-        }
-    }
-}
-
-// grid: x = the workgroups that share a frame's output rows (L.g.S), y = the frames of the launch.  pool: entry 0 of the COUNT pool;
-// dst: the launch's first frame.
-#define COVER_KERNEL(NAME, DTYPE)                                                                                                         \
-    extern "C" __global__ void __launch_bounds__(256)                                                                                     \
-    NAME(const uint8_t *__restrict__ pool, size_t pool_stride, uint8_t *__restrict__ dst, size_t dst_stride, CoverLaunch L)               \
-    {                                                                                                                                     \
-        cover_body<DTYPE>(pool, pool_stride, dst, dst_stride, L);                                                                         \
-    }
-COVER_KERNEL(vp8_cover_u8_kernel, TENSOR_U8)
-COVER_KERNEL(vp8_cover_f16_kernel, TENSOR_F16)
-COVER_KERNEL(vp8_cover_f32_kernel, TENSOR_F32)
+struct CoverPlanes {
+    static constexpr int N = 2;
+    static constexpr bool MASKED = true;
+    static __device__ __forceinline__ int value(const TraceQuad &q, int i, int c) { return c == 0 ? (int)min(q.T[i], 255u) : (int)(q.T[i] != 0u); }
+};
+ENTRY_KERNEL(vp8_cover_u8_kernel, TENSOR_U8, CoverPlanes)
+ENTRY_KERNEL(vp8_cover_f16_kernel, TENSOR_F16, CoverPlanes)
+ENTRY_KERNEL(vp8_cover_f32_kernel, TENSOR_F32, CoverPlanes)

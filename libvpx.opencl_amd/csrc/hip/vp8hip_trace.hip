@@ -14,24 +14,22 @@
 #define TRACE_ARGS const char *slot_base, size_t slot_bytes, size_t o_mbx, size_t o_mvs, uint8_t *pool, size_t pool_stride, TraceLaunch L
 extern "C" __global__ void vp8_trace_kernel(TRACE_ARGS);
 extern "C" __global__ void vp8_wear_kernel(TRACE_ARGS);
-#define FLOW_ARGS const uint8_t *pool, size_t pool_stride, uint8_t *dst, size_t dst_stride, FlowLaunch L
-extern "C" __global__ void vp8_flow_i16_kernel(FLOW_ARGS);
-extern "C" __global__ void vp8_flow_f16_kernel(FLOW_ARGS);
-extern "C" __global__ void vp8_flow_f32_kernel(FLOW_ARGS);
-#define WEAR_ARGS const uint8_t *pool, size_t pool_stride, uint8_t *dst, size_t dst_stride, WearLaunch L
-extern "C" __global__ void vp8_wear_u8_kernel(WEAR_ARGS);
-extern "C" __global__ void vp8_wear_f16_kernel(WEAR_ARGS);
-extern "C" __global__ void vp8_wear_f32_kernel(WEAR_ARGS);
+#define ENTRY_ARGS const uint8_t *pool, size_t pool_stride, uint8_t *dst, size_t dst_stride, EntryLaunch L
+extern "C" __global__ void vp8_flow_i16_kernel(ENTRY_ARGS);
+extern "C" __global__ void vp8_flow_f16_kernel(ENTRY_ARGS);
+extern "C" __global__ void vp8_flow_f32_kernel(ENTRY_ARGS);
+extern "C" __global__ void vp8_wear_u8_kernel(ENTRY_ARGS);
+extern "C" __global__ void vp8_wear_f16_kernel(ENTRY_ARGS);
+extern "C" __global__ void vp8_wear_f32_kernel(ENTRY_ARGS);
+extern "C" __global__ void vp8_cover_u8_kernel(ENTRY_ARGS);
+extern "C" __global__ void vp8_cover_f16_kernel(ENTRY_ARGS);
+extern "C" __global__ void vp8_cover_f32_kernel(ENTRY_ARGS);
 #define INVERT_FILL_ARGS uint8_t *first, size_t first_stride, uint8_t *count, size_t count_stride, InvertLaunch L
 extern "C" __global__ void vp8_invert_fill_kernel(INVERT_FILL_ARGS);
 #define INVERT_ARGS const uint8_t *pool, size_t pool_stride, uint8_t *first, size_t first_stride, uint8_t *count, size_t count_stride, InvertLaunch L
 extern "C" __global__ void vp8_invert_first_kernel(INVERT_ARGS);
 extern "C" __global__ void vp8_invert_count_kernel(INVERT_ARGS);
 extern "C" __global__ void vp8_invert_both_kernel(INVERT_ARGS);
-#define COVER_ARGS const uint8_t *pool, size_t pool_stride, uint8_t *dst, size_t dst_stride, CoverLaunch L
-extern "C" __global__ void vp8_cover_u8_kernel(COVER_ARGS);
-extern "C" __global__ void vp8_cover_f16_kernel(COVER_ARGS);
-extern "C" __global__ void vp8_cover_f32_kernel(COVER_ARGS);
 
 #define ANCHOR_ARGS const uint8_t *raster, size_t fb_stride, const uint8_t *tiles, size_t tile_frame, const uint8_t *pool, size_t pool_stride, \
                     uint8_t *dst, size_t dst_stride, AnchorLaunch L
@@ -165,97 +163,114 @@ static TraceGrid trace_grid(const vp8hip_ctx *c, int gw, int gh, size_t es, int 
     return G;
 }
 
-// the grid of p on context c; false for what the call refuses on p alone
-static bool flow_grid(const vp8hip_ctx *c, const vp8hip_trace_flow *p, int &gw, int &gh)
+// What vp8hip_trace_flow_async, vp8hip_trace_wear_async and vp8hip_trace_cover_async are: pool entries handed out as tensors
+// (entry_tensor_body, vp8_trace_read.hip.h).  A call says what differs, and what its parameter struct holds (null: has_p false)
+struct EntryCall {
+    const char *who;              // the call's name
+    const char *pool_name;        // the pool's name in messages
+    int family;                   // the element of dtype 0, for vp8hip_elem_size: 2 (int16) or 1 (bytes)
+    unsigned valid;               // the plane bits there are; 0: no choice, two planes always
+    void (*kernels[3])(ENTRY_ARGS);
+    bool has_p;
+    int dst_w, dst_h, dtype;
+    unsigned planes;
+    float scale[4];
+};
+
+template <class P>
+static EntryCall entry_call(EntryCall d, const P *p, unsigned planes, int nscale)
 {
-    return p && p->dtype >= 0 && p->dtype <= 2 && trace_out_grid(c, p->dst_w, p->dst_h, gw, gh);
+    d.has_p = true;
+    d.dst_w = p->dst_w; d.dst_h = p->dst_h; d.dtype = p->dtype;
+    d.planes = planes;
+    for (int k = 0; k < nscale; k++) d.scale[k] = p->scale[k];
+    return d;
 }
 
-extern "C" size_t vp8hip_trace_flow_size(const vp8hip_ctx *c, const vp8hip_trace_flow *p)
+// the grid of d on context c; false for what the call refuses on its parameters alone
+static bool entry_grid(const vp8hip_ctx *c, const EntryCall &d, int &gw, int &gh)
+{
+    return d.has_p && d.dtype >= 0 && d.dtype <= 2 && (!d.valid || (d.planes && !(d.planes & ~d.valid))) && trace_out_grid(c, d.dst_w, d.dst_h, gw, gh);
+}
+
+// the bytes of one tensor on a grid of gw x gh
+static size_t entry_bytes(const EntryCall &d, int gw, int gh)
+{
+    return (size_t)(d.valid ? __builtin_popcount(d.planes) : 2) * gh * gw * vp8hip_elem_size(d.dtype, d.family);
+}
+
+static size_t entry_size(const vp8hip_ctx *c, const EntryCall &d)
 {
     int gw, gh;
-    return flow_grid(c, p, gw, gh) ? (size_t)2 * gh * gw * vp8hip_elem_size(p->dtype, 2) : 0;
+    return entry_grid(c, d, gw, gh) ? entry_bytes(d, gw, gh) : 0;
 }
+
+static int entry_tensors(vp8hip_ctx *c, const EntryCall &d, const int *idx, int n, const void *pool, size_t pool_stride, int pool_frames, void *dst,
+                         size_t dst_stride)
+{
+    const char *who = d.who;
+    if (!c || !idx || n < 1 || !d.has_p || !pool || !dst || !c->width) return fail(c, -2, "%s: bad arguments", who);
+    int gw, gh;
+    if (!entry_grid(c, d, gw, gh)) {
+        if (!d.valid) return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), type %d", who, d.dst_w, d.dst_h, VP8HIP_MAX_OUT_SIZE, d.dtype);
+        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), type %d, planes 0x%x", who, d.dst_w, d.dst_h, VP8HIP_MAX_OUT_SIZE, d.dtype, d.planes);
+    }
+    char who_pool[64], who_dst[64];
+    snprintf(who_pool, sizeof(who_pool), "%s (%s)", who, d.pool_name);
+    snprintf(who_dst, sizeof(who_dst), "%s (dst)", who);
+    if (int rc = trace_check_pool(c, who_pool, pool, pool_stride, pool_frames)) return rc;
+    for (int i = 0; i < n; i++)
+        if (idx[i] < 0 || idx[i] >= pool_frames) return fail(c, -2, "%s: entry %d outside the pool", who, idx[i]);
+    const size_t es = (size_t)vp8hip_elem_size(d.dtype, d.family);
+    if (int rc = vp8hip_check_dst(c, who_dst, dst, dst_stride, entry_bytes(d, gw, gh), es, n)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+
+    EntryLaunch L;
+    memset(&L, 0, offsetof(EntryLaunch, idx));
+    L.g = trace_grid(c, gw, gh, es, FLOW_PART_QUADS, dst, dst_stride);
+    L.planes = d.planes;
+    for (int k = 0; k < 4; k++) L.scale[k] = d.scale[k];
+    for (int i0 = 0; i0 < n; i0 += FLOW_MAX_FRAMES) {
+        const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
+        memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
+        hipLaunchKernelGGL(d.kernels[d.dtype], dim3((unsigned)L.g.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
+                           (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+static EntryCall flow_call(const vp8hip_trace_flow *p)
+{
+    const EntryCall d = {"vp8hip_trace_flow_async", "pool", 2, 0, {vp8_flow_i16_kernel, vp8_flow_f16_kernel, vp8_flow_f32_kernel}};
+    return p ? entry_call(d, p, 0, 2) : d;
+}
+
+extern "C" size_t vp8hip_trace_flow_size(const vp8hip_ctx *c, const vp8hip_trace_flow *p) { return entry_size(c, flow_call(p)); }
 
 extern "C" int vp8hip_trace_flow_async(vp8hip_ctx *c, const int *idx, int n, const vp8hip_trace_flow *p, const void *pool, size_t pool_stride,
                                        int pool_frames, void *dst, size_t dst_stride)
 {
-    const char *who = "vp8hip_trace_flow_async";
-    if (!c || !idx || n < 1 || !p || !pool || !dst || !c->width) return fail(c, -2, "%s: bad arguments", who);
-    int gw, gh;
-    if (!flow_grid(c, p, gw, gh))
-        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), type %d", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE, p->dtype);
-    if (int rc = trace_check_pool(c, "vp8hip_trace_flow_async (pool)", pool, pool_stride, pool_frames)) return rc;
-    for (int i = 0; i < n; i++)
-        if (idx[i] < 0 || idx[i] >= pool_frames) return fail(c, -2, "%s: entry %d outside the pool", who, idx[i]);
-    const size_t es = (size_t)vp8hip_elem_size(p->dtype, 2);
-    const size_t size = (size_t)2 * gh * gw * es;
-    if (int rc = vp8hip_check_dst(c, "vp8hip_trace_flow_async (dst)", dst, dst_stride, size, es, n)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-
-    FlowLaunch L;
-    memset(&L, 0, offsetof(FlowLaunch, idx));
-    L.g = trace_grid(c, gw, gh, es, FLOW_PART_QUADS, dst, dst_stride);
-    L.scale[0] = p->scale[0]; L.scale[1] = p->scale[1];
-    void (*const kernels[3])(FLOW_ARGS) = {vp8_flow_i16_kernel, vp8_flow_f16_kernel, vp8_flow_f32_kernel};
-    for (int i0 = 0; i0 < n; i0 += FLOW_MAX_FRAMES) {
-        const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
-        memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
-        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.g.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
-                           (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
-        HIPCHK(c, hipGetLastError());
-    }
-    return 0;
+    return entry_tensors(c, flow_call(p), idx, n, pool, pool_stride, pool_frames, dst, dst_stride);
 }
 
-// the grid of p on context c; false for what the call refuses on p alone
-static bool wear_grid(const vp8hip_ctx *c, const vp8hip_trace_wear *p, int &gw, int &gh)
+static EntryCall wear_call(const vp8hip_trace_wear *p)
 {
-    const unsigned all = VP8HIP_WEAR_HOPS | VP8HIP_WEAR_INTRA | VP8HIP_WEAR_EDGE | VP8HIP_WEAR_CODED;
-    return p && p->dtype >= 0 && p->dtype <= 2 && p->planes && !(p->planes & ~all) && trace_out_grid(c, p->dst_w, p->dst_h, gw, gh);
+    const EntryCall d = {"vp8hip_trace_wear_async", "pool", 1, VP8HIP_WEAR_HOPS | VP8HIP_WEAR_INTRA | VP8HIP_WEAR_EDGE | VP8HIP_WEAR_CODED,
+                         {vp8_wear_u8_kernel, vp8_wear_f16_kernel, vp8_wear_f32_kernel}};
+    return p ? entry_call(d, p, p->planes, 4) : d;
 }
 
-extern "C" size_t vp8hip_trace_wear_size(const vp8hip_ctx *c, const vp8hip_trace_wear *p)
-{
-    int gw, gh;
-    return wear_grid(c, p, gw, gh) ? (size_t)__builtin_popcount(p->planes) * gh * gw * vp8hip_elem_size(p->dtype, 1) : 0;
-}
+extern "C" size_t vp8hip_trace_wear_size(const vp8hip_ctx *c, const vp8hip_trace_wear *p) { return entry_size(c, wear_call(p)); }
 
 extern "C" int vp8hip_trace_wear_async(vp8hip_ctx *c, const int *idx, int n, const vp8hip_trace_wear *p, const void *pool, size_t pool_stride,
                                        int pool_frames, void *dst, size_t dst_stride)
 {
-    const char *who = "vp8hip_trace_wear_async";
-    if (!c || !idx || n < 1 || !p || !pool || !dst || !c->width) return fail(c, -2, "%s: bad arguments", who);
-    int gw, gh;
-    if (!wear_grid(c, p, gw, gh))
-        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), type %d, planes 0x%x", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE, p->dtype,
-                    p->planes);
-    if (int rc = trace_check_pool(c, "vp8hip_trace_wear_async (pool)", pool, pool_stride, pool_frames)) return rc;
-    for (int i = 0; i < n; i++)
-        if (idx[i] < 0 || idx[i] >= pool_frames) return fail(c, -2, "%s: entry %d outside the pool", who, idx[i]);
-    const size_t es = (size_t)vp8hip_elem_size(p->dtype, 1);
-    const size_t size = (size_t)__builtin_popcount(p->planes) * gh * gw * es;
-    if (int rc = vp8hip_check_dst(c, "vp8hip_trace_wear_async (dst)", dst, dst_stride, size, es, n)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-
-    WearLaunch L;
-    memset(&L, 0, offsetof(WearLaunch, idx));
-    L.g = trace_grid(c, gw, gh, es, FLOW_PART_QUADS, dst, dst_stride);
-    L.planes = p->planes;
-    for (int k = 0; k < 4; k++) L.scale[k] = p->scale[k];
-    void (*const kernels[3])(WEAR_ARGS) = {vp8_wear_u8_kernel, vp8_wear_f16_kernel, vp8_wear_f32_kernel};
-    for (int i0 = 0; i0 < n; i0 += FLOW_MAX_FRAMES) {
-        const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
-        memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
-        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.g.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)pool, pool_stride,
-                           (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
-        HIPCHK(c, hipGetLastError());
-    }
-    return 0;
+    return entry_tensors(c, wear_call(p), idx, n, pool, pool_stride, pool_frames, dst, dst_stride);
 }
 
-// [p, + stride * frames) and [q, + qstride * qframes) overlap -- vp8hip_trace_gather_async's rule for src / dst: the span checks have
-// bounded the products, so neither wraps, and the ends saturate
+// [p, + stride * frames) and [q, + qstride * qframes) overlap -- what vp8hip_trace_invert_async refuses of its pools and
+// vp8hip_trace_gather_async of src / dst: the span checks have bounded the products, so neither wraps, and the ends saturate
 static bool spans_overlap(const void *p, size_t stride, int frames, const void *q, size_t qstride, int qframes)
 {
     const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
@@ -318,50 +333,19 @@ extern "C" int vp8hip_trace_invert_async(vp8hip_ctx *c, const vp8hip_invert_job 
     return 0;
 }
 
-// the grid of p on context c; false for what the call refuses on p alone
-static bool cover_grid(const vp8hip_ctx *c, const vp8hip_trace_cover *p, int &gw, int &gh)
+static EntryCall cover_call(const vp8hip_trace_cover *p)
 {
-    const unsigned all = VP8HIP_COVER_COUNT | VP8HIP_COVER_SEEN;
-    return p && p->dtype >= 0 && p->dtype <= 2 && p->planes && !(p->planes & ~all) && trace_out_grid(c, p->dst_w, p->dst_h, gw, gh);
+    const EntryCall d = {"vp8hip_trace_cover_async", "count", 1, VP8HIP_COVER_COUNT | VP8HIP_COVER_SEEN,
+                         {vp8_cover_u8_kernel, vp8_cover_f16_kernel, vp8_cover_f32_kernel}};
+    return p ? entry_call(d, p, p->planes, 2) : d;
 }
 
-extern "C" size_t vp8hip_trace_cover_size(const vp8hip_ctx *c, const vp8hip_trace_cover *p)
-{
-    int gw, gh;
-    return cover_grid(c, p, gw, gh) ? (size_t)__builtin_popcount(p->planes) * gh * gw * vp8hip_elem_size(p->dtype, 1) : 0;
-}
+extern "C" size_t vp8hip_trace_cover_size(const vp8hip_ctx *c, const vp8hip_trace_cover *p) { return entry_size(c, cover_call(p)); }
 
 extern "C" int vp8hip_trace_cover_async(vp8hip_ctx *c, const int *idx, int n, const vp8hip_trace_cover *p, const void *count, size_t count_stride,
                                         int count_frames, void *dst, size_t dst_stride)
 {
-    const char *who = "vp8hip_trace_cover_async";
-    if (!c || !idx || n < 1 || !p || !count || !dst || !c->width) return fail(c, -2, "%s: bad arguments", who);
-    int gw, gh;
-    if (!cover_grid(c, p, gw, gh))
-        return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), type %d, planes 0x%x", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE, p->dtype,
-                    p->planes);
-    if (int rc = trace_check_pool(c, "vp8hip_trace_cover_async (count)", count, count_stride, count_frames)) return rc;
-    for (int i = 0; i < n; i++)
-        if (idx[i] < 0 || idx[i] >= count_frames) return fail(c, -2, "%s: entry %d outside the pool", who, idx[i]);
-    const size_t es = (size_t)vp8hip_elem_size(p->dtype, 1);
-    const size_t size = (size_t)__builtin_popcount(p->planes) * gh * gw * es;
-    if (int rc = vp8hip_check_dst(c, "vp8hip_trace_cover_async (dst)", dst, dst_stride, size, es, n)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-
-    CoverLaunch L;
-    memset(&L, 0, offsetof(CoverLaunch, idx));
-    L.g = trace_grid(c, gw, gh, es, FLOW_PART_QUADS, dst, dst_stride);
-    L.planes = p->planes;
-    L.scale[0] = p->scale[0]; L.scale[1] = p->scale[1];
-    void (*const kernels[3])(COVER_ARGS) = {vp8_cover_u8_kernel, vp8_cover_f16_kernel, vp8_cover_f32_kernel};
-    for (int i0 = 0; i0 < n; i0 += FLOW_MAX_FRAMES) {
-        const int m = n - i0 < FLOW_MAX_FRAMES ? n - i0 : FLOW_MAX_FRAMES;
-        memcpy(L.idx, idx + i0, sizeof(int) * (size_t)m);
-        hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.g.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)count, count_stride,
-                           (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
-        HIPCHK(c, hipGetLastError());
-    }
-    return 0;
+    return entry_tensors(c, cover_call(p), idx, n, count, count_stride, count_frames, dst, dst_stride);
 }
 
 // the grid of p on context c; false for what the call refuses on p alone
@@ -462,11 +446,7 @@ extern "C" int vp8hip_trace_gather_async(vp8hip_ctx *c, const vp8hip_gather_job 
     const size_t ssize = (size_t)p->channels * p->src_h * p->src_w * es, size = (size_t)p->channels * gh * gw * es;
     if (int rc = vp8hip_check_dst(c, "vp8hip_trace_gather_async (src)", src, src_stride, ssize, es, src_frames)) return rc;
     if (int rc = vp8hip_check_dst(c, "vp8hip_trace_gather_async (dst)", dst, dst_stride, size, es, n)) return rc;
-    // (the span checks have bounded both products: neither wraps, the ends saturate)
-    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
-    const size_t slen = src_stride * (size_t)src_frames, dlen = dst_stride * (size_t)n;
-    const uintptr_t s1 = s0 + slen < s0 ? UINTPTR_MAX : s0 + slen, d1 = d0 + dlen < d0 ? UINTPTR_MAX : d0 + dlen;
-    if (s0 < d1 && d0 < s1) return fail(c, -2, "%s: the source tensors and the destination overlap", who);
+    if (spans_overlap(src, src_stride, src_frames, dst, dst_stride, n)) return fail(c, -2, "%s: the source tensors and the destination overlap", who);
     HIPCHK(c, hipSetDevice(c->device));
 
     GatherLaunch L;
@@ -480,7 +460,7 @@ extern "C" int vp8hip_trace_gather_async(vp8hip_ctx *c, const vp8hip_gather_job 
         gz = (unsigned)((L.C + L.cgroup - 1) / L.cgroup);
     } else {
         L.g.S = (int)(((long long)gw * gh + GATHER_RUN - 1) / GATHER_RUN);
-        L.g.vec = ((size_t)L.C * es) % 16 == 0 && d0 % 16 == 0 && dst_stride % 16 == 0 && s0 % 16 == 0 && src_stride % 16 == 0;
+        L.g.vec = ((size_t)L.C * es) % 16 == 0 && (uintptr_t)dst % 16 == 0 && dst_stride % 16 == 0 && (uintptr_t)src % 16 == 0 && src_stride % 16 == 0;
     }
     // by filter, layout and element size (1, 2, 4)
     void (*const kernels[2][2][3])(GATHER_ARGS) = {

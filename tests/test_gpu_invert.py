@@ -3,6 +3,7 @@ Vp8Hip.trace_cover; csrc/hip/vp8_trace_invert.hip), dword for dword and bit for 
 (tests/invert_reference.py).  Most cases need no decode: a context of the size and traces placed in the pool.  torch is imported
 here, before the package loads libvpx's library: one HIP runtime per process."""
 import ctypes
+import functools
 import itertools
 
 import torch  # noqa: F401  (first: the library then shares torch's HIP runtime)
@@ -12,7 +13,7 @@ import pytest
 from handover_testlib import TORCH_DTYPE, assert_destinations_refused, assert_guards_intact, bits, equal_on_device, guarded
 import invert_reference as I
 import trace_reference as R
-from trace_testlib import dwords, random_trace, to_pool, traced_stream, whole_pixel_frame
+from trace_testlib import check_tensor as entry_check_tensor, dwords, random_trace, to_pool, traced_stream, whole_pixel_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -22,18 +23,10 @@ GRIDS = lambda w, h: ((0, 0), (224, 224), (w + 1, h - 1), (1, 1), (2 * w + 3, 2 
 FILL = 0xA5A5A5A5
 
 
-def count_dwords(t):
-    """int32 [..., h, w] on the device -> numpy uint32 [..., h, w]"""
-    return np.ascontiguousarray(t.cpu().numpy()).view(np.uint32)
-
-
-def to_count(a):
-    """numpy uint32 [h, w] -> int32 [h, w] on the device"""
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to("cuda:0")
-
-
-def scale2(scale):
-    return (1.0,) * 2 if scale is None else (scale,) * 2 if np.ndim(scale) == 0 else scale
+count_dwords = dwords                                         # int32 [..., h, w] on the device -> numpy uint32 [..., h, w]
+to_count = functools.partial(to_pool, dtype=np.int32)         # numpy uint32 [h, w] -> int32 [h, w] on the device
+# entries idx of the COUNT pool through trace_cover against the restatement on `want` (their counts, numpy)
+check_tensor = functools.partial(entry_check_tensor, "trace_cover", I.tensor, 2)
 
 
 def three_hops(P, rng, w, h):
@@ -52,16 +45,6 @@ def crafted(P, w, h):
     return [R.identity(w, h), np.full((h, w), R.pack(0, 0), np.uint32), random_trace(rng, w, h),
             rng.integers(0, 2 ** 32, (h, w), dtype=np.uint32),
             R.pack(rng.integers(-5, w + 5, (h, w)), rng.integers(-5, h + 5, (h, w)))] + three_hops(P, rng, w, h)[1:]
-
-
-def check_tensor(ctx, count, idx, want, dw, dh, dtype, planes, scale, what=None, **kw):
-    """entries idx of the COUNT pool through trace_cover against the restatement on `want` (their counts, numpy)"""
-    size = {} if dw == 0 else dict(width=dw, height=dh)
-    got = ctx.trace_cover(count, idx, planes=planes, dtype=TORCH_DTYPE[dtype], scale=scale, **size, **kw).cpu().numpy()
-    assert got.shape[0] == len(idx)
-    for k, c in enumerate(want):
-        ref = I.tensor(c, dw, dh, planes, dtype, scale2(scale))
-        assert got[k].shape == ref.shape and np.array_equal(bits(got[k], dtype), bits(ref, dtype)), (what, k, dw, dh, dtype, planes, scale)
 
 
 @pytest.mark.parametrize("size", [(16, 16), (17, 9), (130, 98), (20, 20), (67, 45), (176, 144)])

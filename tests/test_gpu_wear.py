@@ -4,6 +4,7 @@ Vp8Hip.trace_wear; csrc/hip/vp8_trace_wear.hip), dword for dword and bit for bit
 pool, for slots written by the host parser and by the device's entropy decoder.  torch is imported here, before the package loads
 libvpx's library: one HIP runtime per process."""
 import ctypes
+import functools
 import itertools
 
 import torch  # noqa: F401  (first: the library then shares torch's HIP runtime)
@@ -15,7 +16,7 @@ from handover_testlib import (TORCH_DTYPE, Producer, assert_destinations_refused
                               later_writers_producer, write_later_frames)
 import trace_reference as R
 import wear_reference as W
-from trace_testlib import dwords, slot_ir
+from trace_testlib import check_tensor as entry_check_tensor, dwords, slot_ir, to_pool
 
 pytestmark = pytest.mark.gpu
 
@@ -23,15 +24,10 @@ SCALES = [None, (1.0, 0.5, 0.25, 2.0), 1.0 / 255, (-1.0 / 3, 1e-3, 1.02852499485
 PLANE_SETS = [("hops", "intra", "edge", "coded"), ("coded",), ("edge", "hops"), 14, ("intra",), 9]
 
 
-def wear_dwords(t):
-    """uint8 [..., h, w, 4] on the device -> numpy uint32 [..., h, w]"""
-    a = np.ascontiguousarray(t.cpu().numpy())
-    return a.view(np.uint32).reshape(a.shape[:-1])
-
-
-def to_wear_pool(a):
-    """numpy uint32 [h, w] -> uint8 [h, w, 4] on the device"""
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(a.shape + (4,))).to("cuda:0")
+wear_dwords = dwords                                          # uint8 [..., h, w, 4] on the device -> numpy uint32 [..., h, w]
+to_wear_pool = functools.partial(to_pool, dtype=np.uint8)     # numpy uint32 [h, w] -> uint8 [h, w, 4] on the device
+# entries idx of the pool through trace_wear against the restatement on `want` (their wear, numpy)
+check_tensor = functools.partial(entry_check_tensor, "trace_wear", W.tensor, 4)
 
 
 def random_wear(rng, w, h):
@@ -53,20 +49,6 @@ def refs_as_the_parser_numbers_them(prod):
         swap(hdr)
     prod.parser.swap = noting
     return seen
-
-
-def scale4(scale):
-    return (1.0,) * 4 if scale is None else (scale,) * 4 if np.ndim(scale) == 0 else scale
-
-
-def check_tensor(ctx, pool, idx, want, dw, dh, dtype, planes, scale, what=None, **kw):
-    """entries idx of the pool through trace_wear against the restatement on `want` (their wear, numpy)"""
-    size = {} if dw == 0 else dict(width=dw, height=dh)
-    got = ctx.trace_wear(pool, idx, planes=planes, dtype=TORCH_DTYPE[dtype], scale=scale, **size, **kw).cpu().numpy()
-    assert got.shape[0] == len(idx)
-    for k, t in enumerate(want):
-        ref = W.tensor(t, dw, dh, planes, dtype, scale4(scale))
-        assert got[k].shape == ref.shape and np.array_equal(bits(got[k], dtype), bits(ref, dtype)), (what, k, dw, dh, dtype, planes, scale)
 
 
 @pytest.mark.parametrize("how", ["host", "entropy", "pooled"])

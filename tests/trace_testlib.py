@@ -81,15 +81,34 @@ def slot_ir(ctx, slot):
 
 
 def dwords(t):
-    """int16 [..., h, w, 2] on the device -> numpy uint32 [..., h, w]"""
+    """a pool or entries of one on the device -- int16 [..., h, w, 2], uint8 [..., h, w, 4] or int32 [..., h, w] -> numpy uint32
+    [..., h, w]"""
     a = np.ascontiguousarray(t.cpu().numpy())
-    return a.view(np.uint32).reshape(a.shape[:-1])
+    return a.view(np.uint32).reshape(a.shape if a.itemsize == 4 else a.shape[:-1])
 
 
-def to_pool(a):
-    """numpy uint32 [h, w] -> int16 [h, w, 2] on the device"""
+def to_pool(a, dtype=np.int16):
+    """numpy uint32 [h, w] -> a pool entry of elements `dtype` on the device: int16 [h, w, 2], uint8 [h, w, 4] or int32 [h, w]"""
     import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int16).reshape(a.shape + (2,))).to("cuda:0")
+    per = 4 // np.dtype(dtype).itemsize
+    return torch.from_numpy(np.ascontiguousarray(a).view(dtype).reshape(a.shape + ((per,) if per > 1 else ()))).to("cuda:0")
+
+
+def scales(n, scale):
+    """a call's scale argument -- None, one number or n -- as the n numbers the restatements take"""
+    return (1.0,) * n if scale is None else (scale,) * n if np.ndim(scale) == 0 else scale
+
+
+def check_tensor(call, tensor, nscale, ctx, pool, idx, want, dw, dh, dtype, planes, scale, what=None, **kw):
+    """entries idx of the pool through Vp8Hip's `call` (trace_wear, trace_cover) against the restatement `tensor` (wear_reference's,
+    invert_reference's) on `want` (what the entries hold, numpy)"""
+    from handover_testlib import TORCH_DTYPE, bits
+    size = {} if dw == 0 else dict(width=dw, height=dh)
+    got = getattr(ctx, call)(pool, idx, planes=planes, dtype=TORCH_DTYPE[dtype], scale=scale, **size, **kw).cpu().numpy()
+    assert got.shape[0] == len(idx)
+    for k, t in enumerate(want):
+        ref = tensor(t, dw, dh, planes, dtype, scales(nscale, scale))
+        assert got[k].shape == ref.shape and np.array_equal(bits(got[k], dtype), bits(ref, dtype)), (what, k, dw, dh, dtype, planes, scale)
 
 
 def random_trace(rng, w, h):
