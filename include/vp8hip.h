@@ -742,6 +742,58 @@ typedef struct vp8hip_trace_cover {
 size_t vp8hip_trace_cover_size(const vp8hip_ctx *ctx, const vp8hip_trace_cover *p);
 int  vp8hip_trace_cover_async(vp8hip_ctx *ctx, const int *idx, int n, const vp8hip_trace_cover *p, const void *count, size_t count_stride,
                               int count_frames, void *dst, size_t dst_stride);
+/* FRAME SUMMARIES: byte histograms of pictures, slots, wear and cover.  Everything above hands a device consumer a per-pixel tensor;
+ * the decisions a pipeline makes around those tensors are per frame -- is this a scene cut, is the picture black or frozen, how far is
+ * it from the anchor, has the trace worn out, what share of the frame is intra.  A 256-bin histogram is the exact reduction of byte
+ * data: from H[k] the caller derives count, sum, mean, variance, any percentile and any threshold share without loss, and from the
+ * histogram of |a - b| SAD, SSE, PSNR and "how many samples moved by more than t".  Each of the four calls is defined as the histogram
+ * of a U8 tensor an existing call gives; that tensor is never made.
+ * Every output has one shape: [popcount(planes)][256] of uint32, the planes in the order of their bits, output i at
+ * dst + i * dst_stride BYTES in the caller's device memory; vp8hip_hist_size(popcount) = popcount * 1024, 0 for a popcount outside
+ * 1..32.  Every plane's 256 counts sum to the number of elements counted; a count is at most 16383^2 < 2^28.  The result is integer
+ * counting: the same bits in every run, whatever order lanes and workgroups arrive in.
+ *
+ * vp8hip_frames_hist_async: let S(F) be the packed I420 image vp8hip_frames_scale_async writes for frame buffer F at the display size:
+ * luma d_w x d_h, chroma ((d_w + 1) / 2) x ((d_h + 1) / 2).  Job i with ref_fb < 0: H[p][k] = the number of samples of plane p of
+ * S(fb) equal to k.  With ref_fb >= 0: the number of sample positions where |S(fb) - S(ref_fb)| equals k.  planes: VP8HIP_HIST_Y, _U,
+ * _V.  Each frame buffer is read in a form it has -- raster where it exists, else tiles; the two of a pair independently; one never
+ * written reads as zeros --, nothing is converted or allocated, and no raster pool is made for frames left as tiles.  Jobs come in
+ * any order, with repeats; fb == ref_fb is legal and puts everything into bin 0.
+ *
+ * vp8hip_slots_hist_async: H[p][k] = the number of cells of the NATIVE grid (4 * mb_cols x 4 * mb_rows) whose value in plane p of
+ * vp8hip_frames_side_async's info tensor equals k: the planes VP8HIP_SIDE_REF, _MODE, _SKIP, _SEGMENT, _QINDEX and _CODED exactly as
+ * defined there, with the slot's header as of the call.  VP8HIP_HIST_MVMAG (this call only; vp8hip_frames_side_async keeps refusing
+ * bit 64) is a seventh plane, behind the six: with (vx, vy) the cell's vector as that call's I16 tensor holds it -- (0, 0) on key
+ * frames and intra macroblocks --, px = (vx + 4) >> 3 and py = (vy + 4) >> 3 (arithmetic shifts: the trace's rounding to whole
+ * pixels), the value is min(max(|px|, |py|), 255).  The call reads records and vectors, not blocks: also on a
+ * vp8hip_configure_pooled context.
+ *
+ * vp8hip_trace_wear_hist_async / vp8hip_trace_cover_hist_async: H[p][k] = the number of pixels of entry idx[i] (all d_w * d_h) whose
+ * value in plane p of vp8hip_trace_wear_async's / vp8hip_trace_cover_async's U8 tensor at the display size equals k.  planes:
+ * VP8HIP_WEAR_* / VP8HIP_COVER_*; COUNT saturates at 255 and SEEN fills bins 0 and 1 only.  Pool values are data and never addresses.
+ *
+ * All four are their neighbours: enqueued on the context's stream -- a later writer of a frame buffer, slot or pool entry runs behind
+ * the call, and an earlier vp8hip_decode, vp8hip_frames_wear_async or vp8hip_trace_invert_async is seen --; no device memory is added;
+ * no frame buffer, slot or pool entry is written; only bytes inside [dst + i * dst_stride, + size) are written.  They return -2 with
+ * nothing enqueued for n < 1; an fb, slot or idx out of range, or a slot never filled; a ref_fb neither -1 nor in range; planes == 0
+ * or bits the call does not know; what vp8hip_trace_flow_async refuses of a pool; dst_stride below the size; dst or dst_stride not a
+ * multiple of 4; a destination that is not device memory of the context's device or that cannot hold n outputs; and, for the two pool
+ * calls, [dst, + n * dst_stride) overlapping the pool. */
+#define VP8HIP_HIST_Y 1          /* bit order = plane order */
+#define VP8HIP_HIST_U 2
+#define VP8HIP_HIST_V 4
+#define VP8HIP_HIST_MVMAG 64     /* beside the VP8HIP_SIDE_* bits, for vp8hip_slots_hist_async only */
+typedef struct vp8hip_hist_job {       /* one output */
+    int32_t fb;                /* the frame buffer counted */
+    int32_t ref_fb;            /* -1: none; otherwise the frame buffer it is compared with */
+} vp8hip_hist_job;
+size_t vp8hip_hist_size(int planes_popcount);
+int  vp8hip_frames_hist_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int n, unsigned planes, void *dst, size_t dst_stride);
+int  vp8hip_slots_hist_async(vp8hip_ctx *ctx, const int *slots, int n, unsigned planes, void *dst, size_t dst_stride);
+int  vp8hip_trace_wear_hist_async(vp8hip_ctx *ctx, const int *idx, int n, unsigned planes, const void *pool, size_t pool_stride,
+                                  int pool_frames, void *dst, size_t dst_stride);
+int  vp8hip_trace_cover_hist_async(vp8hip_ctx *ctx, const int *idx, int n, unsigned planes, const void *count, size_t count_stride,
+                                   int count_frames, void *dst, size_t dst_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

@@ -463,6 +463,20 @@ def trace_cover_size(gw, gh, planes=("count", "seen"), dtype=0):
     return _entry_tensor_size(gw, gh, planes, dtype, COVER_PLANES, TraceCoverParams, "vp8hip_trace_cover_size")
 
 
+HIST_PLANES = {"y": 1, "u": 2, "v": 4}                       # VP8HIP_HIST_Y, _U, _V: bit order = plane order
+SLOT_HIST_PLANES = dict(SIDE_PLANES, mvmag=64)                # VP8HIP_SIDE_* and VP8HIP_HIST_MVMAG, for Vp8Hip.slots_hist only
+
+
+def hist_size(planes):
+    """bytes of one output of Vp8Hip.frames_hist, slots_hist, trace_wear_hist and trace_cover_hist (vp8hip_hist_size): 1024 a plane,
+    256 uint32 counts; 0 for no plane.  planes: how many there are, or their names"""
+    if isinstance(planes, (tuple, list, set, frozenset)):
+        planes = len(set(planes))
+    elif not isinstance(planes, int):
+        return 0
+    return int(load_hip().vp8hip_hist_size(int(planes)))
+
+
 GATHER_FILTERS = {"nearest": 0, "bilinear": 1}              # VP8HIP_GATHER_NEAREST, BILINEAR
 GATHER_LAYOUTS = {"planar": 0, "channels_last": 1}            # VP8HIP_GATHER_PLANAR, CHANNELS_LAST
 
@@ -559,6 +573,10 @@ class TraceCoverParams(ctypes.Structure):   # vp8hip_trace_cover, include/vp8hip
     _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("dtype", c_int), ("planes", ctypes.c_uint), ("scale", ctypes.c_float * 2)]
 
 
+class HistJob(ctypes.Structure):            # vp8hip_hist_job, include/vp8hip.h
+    _fields_ = [("fb", ctypes.c_int32), ("ref_fb", ctypes.c_int32)]
+
+
 class VisParams(ctypes.Structure):         # vp8hip_vis, include/vp8hip.h
     _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
                 ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
@@ -646,6 +664,12 @@ def load_hip():
         L.vp8hip_trace_cover_size.restype = c_size_t
         L.vp8hip_trace_cover_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(TraceCoverParams), c_void_p, c_size_t, c_int, c_void_p,
                                                c_size_t]
+        L.vp8hip_hist_size.argtypes = [c_int]
+        L.vp8hip_hist_size.restype = c_size_t
+        L.vp8hip_frames_hist_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_uint, c_void_p, c_size_t]
+        L.vp8hip_slots_hist_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_uint, c_void_p, c_size_t]
+        L.vp8hip_trace_wear_hist_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_uint, c_void_p, c_size_t, c_int, c_void_p, c_size_t]
+        L.vp8hip_trace_cover_hist_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_uint, c_void_p, c_size_t, c_int, c_void_p, c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1219,6 +1243,86 @@ class Vp8Hip:
         asked for, float32 (default 1).  `out`: a tensor of that shape and type, each frame dense, stride(0) free.  Stream
         ordering: as frames_scaled."""
         return self._trace_entries("trace_cover", count, idx, width, height, planes, dtype, scale, out)
+
+    @staticmethod
+    def _hist_args(who, items, planes, table):
+        """-> (how many jobs, the plane mask, how many planes) of a histogram call; ValueError for no job, no plane or an unknown one"""
+        mask = _plane_mask(planes, table, False)
+        if mask is None:
+            raise ValueError(f"{who}: planes {planes!r} (at least one of {', '.join(table)})")
+        if len(items) < 1:
+            raise ValueError(f"{who}: no jobs")
+        return len(items), mask, bin(mask).count("1")
+
+    def _hist(self, who, call, n, nplanes, out, fn):
+        """what the four histogram calls end in: the torch.int32 tensor [n, planes, 256] -- `out` when given, each job's counts
+        dense, stride(0) free -- filled by fn(pointer, stride in bytes) between the stream waits"""
+        return self._to_torch(who, [("out", out, "int32", (n, nplanes, 256))], fn, call)[0]
+
+    def frames_hist(self, jobs, planes=("y", "u", "v"), out=None):
+        """Byte histograms of pictures on the context's device (vp8hip_frames_hist_async): a torch.int32 tensor [n, P, 256].  `jobs`:
+        a list of frame buffers, or of (fb, ref_fb) with ref_fb None or -1 for none (any order, repeats allowed).  Without a
+        reference H[i, p, k] counts the samples of plane p of frame buffer fb -- as frames_scaled hands it out at the display size --
+        that equal k; with one, the sample positions where |fb - ref_fb| equals k, from which SAD, SSE and PSNR follow exactly.
+        planes: "y", "u", "v" (or the mask), in that order.  Each frame buffer is read in the form it has; nothing is converted or
+        allocated.  Counts are below 2^28.  Stream ordering, the `import torch` first rule and the remark on record_stream: as
+        frames_scaled."""
+        who = "frames_hist"
+        items = []
+        for j in jobs:
+            j = (j, None) if isinstance(j, (int, np.integer)) else tuple(j)
+            if len(j) != 2:
+                raise ValueError(f"{who}: jobs are frame buffers or (fb, ref_fb)")
+            items.append((int(j[0]), -1 if j[1] is None else int(j[1])))
+        n, mask, nplanes = self._hist_args(who, items, planes, HIST_PLANES)
+        if any(fb < 0 or ref < -1 for fb, ref in items):
+            raise ValueError(f"{who}: a negative frame buffer (ref_fb: None or -1 for none)")
+        arr = (HistJob * n)(*items)
+        return self._hist(who, "vp8hip_frames_hist_async", n, nplanes, out,
+                          lambda ptr, stride: self.L.vp8hip_frames_hist_async(self.h, arr, n, mask, ptr, stride))
+
+    def slots_hist(self, slots, planes, out=None):
+        """Byte histograms of IR slots' info planes on the context's device (vp8hip_slots_hist_async): a torch.int32 tensor [n, P, 256],
+        H[i, p, k] the number of cells of the native grid (a cell per 4x4 luma block of the coded area) whose value in plane p of
+        frames_side's info tensor equals k.  planes: frames_side's ("ref", "mode", "skip", "segment", "qindex", "coded") and "mvmag",
+        the larger component of the cell's vector in whole pixels, rounded as the trace rounds and capped at 255 (0 on key frames
+        and intra macroblocks); or the mask; always in bit order, "mvmag" last.  Stream ordering: as frames_scaled."""
+        who = "slots_hist"
+        slots = [int(s) for s in slots]
+        n, mask, nplanes = self._hist_args(who, slots, planes, SLOT_HIST_PLANES)
+        if any(s < 0 for s in slots):
+            raise ValueError(f"{who}: a negative slot")
+        arr = (c_int * n)(*slots)
+        return self._hist(who, "vp8hip_slots_hist_async", n, nplanes, out,
+                          lambda ptr, stride: self.L.vp8hip_slots_hist_async(self.h, arr, n, mask, ptr, stride))
+
+    def _entries_hist(self, who, pool, idx, planes, out):
+        """what trace_wear_hist and trace_cover_hist are: the histograms of entries `idx` of `pool` by the library's call"""
+        _, call, _, table, _, kind = self._ENTRY_CALLS[who[:-5]]
+        idx = [int(i) for i in idx]
+        n, mask, nplanes = self._hist_args(who, idx, planes, table)
+        if any(i < 0 for i in idx):
+            raise ValueError(f"{who}: a negative entry")
+        _, pptr, pstride, entries = self._trace_pool_args(who, pool, kind)
+        if any(i >= entries for i in idx):
+            raise ValueError(f"{who}: an entry outside the pool's {entries}")
+        arr = (c_int * n)(*idx)
+        return self._hist(who, call + "_hist_async", n, nplanes, out,
+                          lambda ptr, stride: getattr(self.L, call + "_hist_async")(self.h, arr, n, mask, pptr, pstride, entries, ptr, stride))
+
+    def trace_wear_hist(self, pool, idx, planes=("hops", "intra", "edge", "coded"), out=None):
+        """Byte histograms of wear entries on the context's device (vp8hip_trace_wear_hist_async): a torch.int32 tensor [n, P, 256],
+        H[i, p, k] the number of pixels of entry idx[i] of the wear pool `pool` whose counter p -- trace_wear's planes, in bit order
+        -- equals k.  What a scheduler reads to decide when to re-anchor, without trace_wear's tensor.  `out` must not overlap the
+        pool.  Stream ordering: as frames_scaled."""
+        return self._entries_hist("trace_wear_hist", pool, idx, planes, out)
+
+    def trace_cover_hist(self, count, idx, planes=("count", "seen"), out=None):
+        """Byte histograms of COUNT entries on the context's device (vp8hip_trace_cover_hist_async): a torch.int32 tensor [n, P, 256]
+        over trace_cover's planes at the display size: "count" is min(count, 255), "seen" fills bins 0 and 1 only -- H[i, p, 1] of
+        "seen" is how many anchor pixels survive into the frame.  `out` must not overlap the pool.  Stream ordering: as
+        frames_scaled."""
+        return self._entries_hist("trace_cover_hist", count, idx, planes, out)
 
     def trace_residual(self, pool, jobs, width=None, height=None, dtype=None, matrix="bt601", order="rgb", scale=None, out=None):
         """The accumulated residual of `jobs` -- a list of (fb, entry, anchor_fb): the frame buffer that holds a frame, the entry of

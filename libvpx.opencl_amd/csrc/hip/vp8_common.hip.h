@@ -215,6 +215,39 @@ struct InvertLaunch {
     InvertJob j[INVERT_MAX_JOBS];
 };
 
+// One launch of the byte histograms (vp8_hist.hip), as the host's plans (vp8hip_hist.hip) left it: vp8hip_frames_hist_async,
+// vp8hip_slots_hist_async, vp8hip_trace_wear_hist_async and vp8hip_trace_cover_hist_async.  gridDim.x workgroups share a job; where
+// that is more than one, vp8_hist_fill_kernel has run first and the workgroups add their counts with global atomics
+#define HIST_MAX_JOBS 256         // jobs per launch (kernel arguments: 8 bytes each at most)
+#define HIST_BINS 256
+#define HIST_ROW 257              // dwords from one LDS sub-histogram to the next: copy k's bin b lies in bank (b + k) % banks
+#define HIST_SLOT_MVMAG 6         // the plane of VP8HIP_HIST_MVMAG, behind the six of VP8HIP_SIDE_*
+struct HistFrameJob {
+    int fb;                       // the frame: frame buffer << 2 | form (SCALE_FROM_*), as of the call
+    int ref;                      // the frame it is compared with, the same way; -1: none
+};
+struct HistFrameLaunch {
+    int dw, dh;                   // the display size
+    int mb_cols, mb_rows;
+    int y_off, u_off, v_off, y_stride, uv_stride;    // the raster form: the planes' origins in a frame buffer and their strides
+    int S;                        // workgroups that share a job's rows (gridDim.x)
+    unsigned planes;              // VP8HIP_HIST_Y | _U | _V
+    HistFrameJob j[HIST_MAX_JOBS];
+};
+struct HistSlotLaunch {
+    int mb_cols, mb_rows;
+    int R;                        // macroblock rows a workgroup stages (a group: gridDim.x of them); LDS = histograms + R * mb_cols * 128 bytes
+    unsigned planes;              // VP8HIP_SIDE_* bits and VP8HIP_HIST_MVMAG
+    int slot[HIST_MAX_JOBS];      // IR slot of job k of the launch
+    unsigned q[HIST_MAX_JOBS];    // ... its header, as SideLaunch::q holds it
+};
+struct HistEntryLaunch {
+    int dw, dh;                   // the display size: an entry's grid
+    int S;                        // workgroups that share an entry's rows (gridDim.x)
+    unsigned planes;              // VP8HIP_WEAR_* / VP8HIP_COVER_* bits
+    int idx[HIST_MAX_JOBS];       // pool entry of job k of the launch
+};
+
 #define WAVE 64
 
 // Macroblock tiles of the one-MB-row-per-lane pipeline (vp8_keyframe_simt.hip has the layout): three 128-byte lines per macroblock.

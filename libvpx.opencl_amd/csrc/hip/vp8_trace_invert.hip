@@ -117,11 +117,7 @@ INVERT_KERNEL(vp8_invert_first_kernel, true, false)
 INVERT_KERNEL(vp8_invert_count_kernel, false, true)
 INVERT_KERNEL(vp8_invert_both_kernel, true, true)
 
-struct CoverPlanes {
-    static constexpr int N = 2;
-    static constexpr bool MASKED = true;
-    static __device__ __forceinline__ int value(const TraceQuad &q, int i, int c) { return c == 0 ? (int)min(q.T[i], 255u) : (int)(q.T[i] != 0u); }
-};
+// (CoverPlanes: vp8_trace_read.hip.h, beside entry_tensor_body)
 ENTRY_KERNEL(vp8_cover_u8_kernel, TENSOR_U8, CoverPlanes)
 ENTRY_KERNEL(vp8_cover_f16_kernel, TENSOR_F16, CoverPlanes)
 ENTRY_KERNEL(vp8_cover_f32_kernel, TENSOR_F32, CoverPlanes)

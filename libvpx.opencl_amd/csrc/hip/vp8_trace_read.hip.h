@@ -203,3 +203,17 @@ __device__ __forceinline__ void entry_tensor_body(const uint8_t *__restrict__ po
     {                                                                                                                                     \
         entry_tensor_body<DTYPE, PLANES>(pool, pool_stride, dst, dst_stride, L);                                                          \
     }
+
+// What the dwords of the two pools that are handed out plane by plane hold, for entry_tensor_body and for the histograms of the same
+// tensors (vp8_hist.hip).  A wear dword (vp8_trace_wear.hip): four byte counters, HOPS, INTRA, EDGE, CODED from the low byte up.
+struct WearPlanes {
+    static constexpr int N = 4;
+    static constexpr bool MASKED = true;
+    static __device__ __forceinline__ int value(const TraceQuad &q, int i, int c) { return (int)(q.T[i] >> 8 * c & 255u); }
+};
+// A COUNT dword (vp8_trace_invert.hip): plane COUNT holds min(c, 255), plane SEEN c != 0.
+struct CoverPlanes {
+    static constexpr int N = 2;
+    static constexpr bool MASKED = true;
+    static __device__ __forceinline__ int value(const TraceQuad &q, int i, int c) { return c == 0 ? (int)min(q.T[i], 255u) : (int)(q.T[i] != 0u); }
+};

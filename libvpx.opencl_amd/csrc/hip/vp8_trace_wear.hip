@@ -59,11 +59,7 @@ vp8_wear_kernel(const char *__restrict__ slot_base, size_t slot_bytes, size_t o_
     trace_hop_body<WearHop>(slot_base, slot_bytes, o_mbx, o_mvs, pool, pool_stride, L);
 }
 
-struct WearPlanes {
-    static constexpr int N = 4;
-    static constexpr bool MASKED = true;
-    static __device__ __forceinline__ int value(const TraceQuad &q, int i, int c) { return (int)(q.T[i] >> 8 * c & 255u); }
-};
+// (WearPlanes: vp8_trace_read.hip.h, beside entry_tensor_body)
 ENTRY_KERNEL(vp8_wear_u8_kernel, TENSOR_U8, WearPlanes)
 ENTRY_KERNEL(vp8_wear_f16_kernel, TENSOR_F16, WearPlanes)
 ENTRY_KERNEL(vp8_wear_f32_kernel, TENSOR_F32, WearPlanes)

@@ -11,6 +11,8 @@
 //                       (vp8_trace_residual.hip) and vp8hip_trace_gather_async (vp8_trace_gather.hip); vp8hip_frames_wear_async and
 //                       vp8hip_trace_wear_async: what happened along the trace, in a pool of its own, and its entries as tensors
 //                       (vp8_trace_wear.hip)
+//   vp8hip_hist.hip     vp8hip_frames_hist_async, vp8hip_slots_hist_async, vp8hip_trace_wear_hist_async, vp8hip_trace_cover_hist_async:
+//                       byte histograms of pictures, slots and pool entries (vp8_hist.hip)
 //   vp8hip_handover.hip the checks those calls share
 // and vp8hip_res.hip.h: the owning types of the context's buffers, events and streams.
 #pragma once
@@ -204,5 +206,13 @@ bool vp8hip_out_grid(const vp8hip_ctx *c, int dst_w, int dst_h, int cells, int &
 int vp8hip_check_device_span(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, int n);
 int vp8hip_check_dst(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, size_t elem_size, int n);
 unsigned vp8hip_segment_q_bits(const vp8ir_frame_hdr &h);
+// vp8hip_side.hip: what the kernels that read a slot's records take of its header (SideLaunch::q, HistSlotLaunch::q): vp8hip_segment_q_bits,
+// and bit 28 for a key frame
+unsigned vp8hip_side_header_bits(const vp8ir_frame_hdr &h);
+// vp8hip_trace.hip, for the calls that read a pool in the caller's device memory (those there and vp8hip_hist.hip): a pool of
+// pool_frames entries of the context's trace size, pool_stride apart, dword-aligned, inside one allocation of the device; and
+// whether [p, + stride * frames) and [q, + qstride * qframes) overlap
+int vp8hip_check_pool(vp8hip_ctx *c, const char *who, const void *pool, size_t pool_stride, int pool_frames);
+bool vp8hip_spans_overlap(const void *p, size_t stride, int frames, const void *q, size_t qstride, int qframes);
 // bytes of an element by dtype: F16 is 1 and F32 is 2 in VP8HIP_RGB_*, VP8HIP_SIDE_* and VP8HIP_RES_*; size0: type 0's (bytes: 1, int16: 2)
 static inline int vp8hip_elem_size(int dtype, int size0) { return dtype == 2 ? 4 : dtype == 1 ? 2 : size0; }

@@ -37,7 +37,7 @@ extern "C" size_t vp8hip_side_info_size(const vp8hip_ctx *c, const vp8hip_side *
 }
 
 // what the kernel needs of a slot's header: the quantiser index of each segment, and bit 28 for a key frame
-static unsigned side_header_bits(const vp8ir_frame_hdr &h) { return vp8hip_segment_q_bits(h) | (h.frame_type == 0 ? 1u << 28 : 0u); }
+unsigned vp8hip_side_header_bits(const vp8ir_frame_hdr &h) { return vp8hip_segment_q_bits(h) | (h.frame_type == 0 ? 1u << 28 : 0u); }
 
 // The launch for a grid of gw x gh: the size it is laid over, the group of macroblock rows a workgroup stages and how many
 // workgroups share a group's output rows.  Returns the LDS a workgroup takes.
@@ -98,7 +98,7 @@ extern "C" int vp8hip_frames_side_async(vp8hip_ctx *c, const int *slots, int n, 
         const int m = n - i0 < SIDE_MAX_FRAMES ? n - i0 : SIDE_MAX_FRAMES;
         for (int k = 0; k < m; k++) {
             L.slot[k] = slots[i0 + k];
-            L.q[k] = side_header_bits(c->slots[slots[i0 + k]].hdr_copy);
+            L.q[k] = vp8hip_side_header_bits(c->slots[slots[i0 + k]].hdr_copy);
         }
         hipLaunchKernelGGL(kernel, dim3(groups * (unsigned)L.S, (unsigned)m), dim3(256), (unsigned)lds, c->stream, (const char *)c->slot_block_dev,
                            c->slot_bytes, c->o_mbx, c->o_mvs, mv_dst ? (uint8_t *)mv_dst + mv_stride * (size_t)i0 : (uint8_t *)nullptr, mv_stride,

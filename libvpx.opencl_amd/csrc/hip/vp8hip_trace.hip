@@ -62,7 +62,7 @@ extern "C" size_t vp8hip_trace_size(const vp8hip_ctx *c) { return c && c->width 
 
 // the pool: pool_frames entries of the context's trace size, pool_stride apart, dword-aligned, inside one allocation of the device
 // (that the entries a call names lie inside it is the call's to check: they sit in different structs and the texts differ)
-static int trace_check_pool(vp8hip_ctx *c, const char *who, const void *pool, size_t pool_stride, int pool_frames)
+int vp8hip_check_pool(vp8hip_ctx *c, const char *who, const void *pool, size_t pool_stride, int pool_frames)
 {
     if (pool_frames < 1) return fail(c, -2, "%s: a pool of %d traces", who, pool_frames);
     return vp8hip_check_dst(c, who, pool, pool_stride, vp8hip_trace_size(c), 4, pool_frames);
@@ -78,7 +78,7 @@ static int trace_frames(vp8hip_ctx *c, const char *who, const char *who_pool, vo
     std::vector<int> slots((size_t)n);
     for (int i = 0; i < n; i++) slots[(size_t)i] = jobs[i].ir_slot;
     if (int rc = vp8hip_check_slots(c, who, slots.data(), n)) return rc;
-    if (int rc = trace_check_pool(c, who_pool, pool, pool_stride, pool_frames)) return rc;
+    if (int rc = vp8hip_check_pool(c, who_pool, pool, pool_stride, pool_frames)) return rc;
     // one marker byte per pool entry: 1 a reference of some job, 2 some job's destination
     std::vector<uint8_t> mark((size_t)pool_frames, 0);
     for (int i = 0; i < n; i++) {
@@ -218,7 +218,7 @@ static int entry_tensors(vp8hip_ctx *c, const EntryCall &d, const int *idx, int 
     char who_pool[64], who_dst[64];
     snprintf(who_pool, sizeof(who_pool), "%s (%s)", who, d.pool_name);
     snprintf(who_dst, sizeof(who_dst), "%s (dst)", who);
-    if (int rc = trace_check_pool(c, who_pool, pool, pool_stride, pool_frames)) return rc;
+    if (int rc = vp8hip_check_pool(c, who_pool, pool, pool_stride, pool_frames)) return rc;
     for (int i = 0; i < n; i++)
         if (idx[i] < 0 || idx[i] >= pool_frames) return fail(c, -2, "%s: entry %d outside the pool", who, idx[i]);
     const size_t es = (size_t)vp8hip_elem_size(d.dtype, d.family);
@@ -271,7 +271,7 @@ extern "C" int vp8hip_trace_wear_async(vp8hip_ctx *c, const int *idx, int n, con
 
 // [p, + stride * frames) and [q, + qstride * qframes) overlap -- what vp8hip_trace_invert_async refuses of its pools and
 // vp8hip_trace_gather_async of src / dst: the span checks have bounded the products, so neither wraps, and the ends saturate
-static bool spans_overlap(const void *p, size_t stride, int frames, const void *q, size_t qstride, int qframes)
+bool vp8hip_spans_overlap(const void *p, size_t stride, int frames, const void *q, size_t qstride, int qframes)
 {
     const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
     const size_t plen = stride * (size_t)frames, qlen = qstride * (size_t)qframes;
@@ -285,11 +285,11 @@ extern "C" int vp8hip_trace_invert_async(vp8hip_ctx *c, const vp8hip_invert_job 
     const char *who = "vp8hip_trace_invert_async";
     if (!c || !jobs || n < 1 || !pool || !c->width) return fail(c, -2, "%s: bad arguments", who);
     if (!first && !count) return fail(c, -2, "%s: neither a FIRST nor a COUNT pool", who);
-    if (int rc = trace_check_pool(c, "vp8hip_trace_invert_async (pool)", pool, pool_stride, pool_frames)) return rc;
+    if (int rc = vp8hip_check_pool(c, "vp8hip_trace_invert_async (pool)", pool, pool_stride, pool_frames)) return rc;
     if (first)
-        if (int rc = trace_check_pool(c, "vp8hip_trace_invert_async (first)", first, first_stride, out_frames)) return rc;
+        if (int rc = vp8hip_check_pool(c, "vp8hip_trace_invert_async (first)", first, first_stride, out_frames)) return rc;
     if (count)
-        if (int rc = trace_check_pool(c, "vp8hip_trace_invert_async (count)", count, count_stride, out_frames)) return rc;
+        if (int rc = vp8hip_check_pool(c, "vp8hip_trace_invert_async (count)", count, count_stride, out_frames)) return rc;
     std::vector<uint8_t> mark((size_t)out_frames, 0);        // 1: some job's destination
     for (int i = 0; i < n; i++) {
         if (jobs[i].trace < 0 || jobs[i].trace >= pool_frames) return fail(c, -2, "%s: job %d: trace %d outside the pool", who, i, jobs[i].trace);
@@ -298,11 +298,11 @@ extern "C" int vp8hip_trace_invert_async(vp8hip_ctx *c, const vp8hip_invert_job 
         if (m) return fail(c, -2, "%s: job %d: destination %d is another job's destination", who, i, jobs[i].dst);
         m = 1;
     }
-    if (first && spans_overlap(pool, pool_stride, pool_frames, first, first_stride, out_frames))
+    if (first && vp8hip_spans_overlap(pool, pool_stride, pool_frames, first, first_stride, out_frames))
         return fail(c, -2, "%s: the trace pool and the FIRST pool overlap", who);
-    if (count && spans_overlap(pool, pool_stride, pool_frames, count, count_stride, out_frames))
+    if (count && vp8hip_spans_overlap(pool, pool_stride, pool_frames, count, count_stride, out_frames))
         return fail(c, -2, "%s: the trace pool and the COUNT pool overlap", who);
-    if (first && count && spans_overlap(first, first_stride, out_frames, count, count_stride, out_frames))
+    if (first && count && vp8hip_spans_overlap(first, first_stride, out_frames, count, count_stride, out_frames))
         return fail(c, -2, "%s: the FIRST pool and the COUNT pool overlap", who);
     HIPCHK(c, hipSetDevice(c->device));
 
@@ -374,7 +374,7 @@ extern "C" int vp8hip_trace_residual_async(vp8hip_ctx *c, const vp8hip_anchor_jo
     if (!anchor_grid(c, p, gw, gh))
         return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), matrix %d, order %d, type %d", who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE,
                     p->matrix, p->order, p->dtype);
-    if (int rc = trace_check_pool(c, "vp8hip_trace_residual_async (pool)", pool, pool_stride, pool_frames)) return rc;
+    if (int rc = vp8hip_check_pool(c, "vp8hip_trace_residual_async (pool)", pool, pool_stride, pool_frames)) return rc;
     for (int i = 0; i < n; i++)
         if (jobs[i].trace < 0 || jobs[i].trace >= pool_frames) return fail(c, -2, "%s: job %d: trace %d outside the pool", who, i, jobs[i].trace);
     const size_t es = (size_t)vp8hip_elem_size(p->dtype, 2);
@@ -436,7 +436,7 @@ extern "C" int vp8hip_trace_gather_async(vp8hip_ctx *c, const vp8hip_gather_job 
         return fail(c, -2, "%s: grid %dx%d (both 0, or 1..%d each), source grid %dx%d (1..%d each), %d channels (1..%d), element %d, layout %d, filter %d",
                     who, p->dst_w, p->dst_h, VP8HIP_MAX_OUT_SIZE, p->src_w, p->src_h, VP8HIP_MAX_OUT_SIZE, p->channels, VP8HIP_GATHER_MAX_CHANNELS,
                     p->elem, p->layout, p->filter);
-    if (int rc = trace_check_pool(c, "vp8hip_trace_gather_async (pool)", pool, pool_stride, pool_frames)) return rc;
+    if (int rc = vp8hip_check_pool(c, "vp8hip_trace_gather_async (pool)", pool, pool_stride, pool_frames)) return rc;
     if (src_frames < 1) return fail(c, -2, "%s: %d source tensors", who, src_frames);
     for (int i = 0; i < n; i++) {
         if (jobs[i].trace < 0 || jobs[i].trace >= pool_frames) return fail(c, -2, "%s: job %d: trace %d outside the pool", who, i, jobs[i].trace);
@@ -446,7 +446,7 @@ extern "C" int vp8hip_trace_gather_async(vp8hip_ctx *c, const vp8hip_gather_job 
     const size_t ssize = (size_t)p->channels * p->src_h * p->src_w * es, size = (size_t)p->channels * gh * gw * es;
     if (int rc = vp8hip_check_dst(c, "vp8hip_trace_gather_async (src)", src, src_stride, ssize, es, src_frames)) return rc;
     if (int rc = vp8hip_check_dst(c, "vp8hip_trace_gather_async (dst)", dst, dst_stride, size, es, n)) return rc;
-    if (spans_overlap(src, src_stride, src_frames, dst, dst_stride, n)) return fail(c, -2, "%s: the source tensors and the destination overlap", who);
+    if (vp8hip_spans_overlap(src, src_stride, src_frames, dst, dst_stride, n)) return fail(c, -2, "%s: the source tensors and the destination overlap", who);
     HIPCHK(c, hipSetDevice(c->device));
 
     GatherLaunch L;
