@@ -454,6 +454,67 @@ typedef struct vp8hip_residual {
 } vp8hip_residual;
 size_t vp8hip_residual_size(const vp8hip_ctx *ctx, const vp8hip_residual *p);
 int  vp8hip_frames_residual_async(vp8hip_ctx *ctx, const int *slots, int n, const vp8hip_residual *p, void *dst, size_t dst_stride);
+/* The TRANSFORM COEFFICIENTS of IR slots as tensors, for consumers on the device that want them as they are: frequency-domain models
+ * (blocks as [frequency][block row][block column], often the first few of the scan only), forensics and quantiser estimation (the
+ * levels as coded, per frequency), requantisers (levels plus factors).  A forward DCT of vp8hip_frames_residual_async's samples does
+ * not give them: the reference's int16 truncations and >> 3 roundings do not invert.
+ * Any n IR slots on vp8hip_frames_residual_async's terms: any order, repeats, any producer; on a vp8hip_configure_pooled context the
+ * blocks are read from the pool; a starved slot is read in bounds and gives garbage; slot slots[i] goes to dst + i * dst_stride BYTES.
+ * There is only the native grid, the coded area: coefficients are not resampled, a consumer crops by whole blocks.
+ * Below R = mb_rows, C = mb_cols, m = the slot's record of the macroblock, h = the slot's header as of the call, the six factors those
+ * of vp8hip_frames_residual_async (mb_init_dequantizer for h and m.segment_id & 3).  Position (v, u) of block k is the reference's
+ * qcoeff[k * 16 + 4 * v + u] (the IR stores it at [u * 4 + v]).  "A Y2 macroblock": m.y_mode neither B_PRED nor SPLITMV.
+ * stage VP8HIP_COEF_LEVELS, what the stream codes:
+ *   - m.flags & VP8IR_MB_SKIP: 0 everywhere.  Not a Y2 macroblock: its Y2 plane is 0.
+ *   - a block k < 24 with m.eobs[k] > 1: the sixteen values the slot's block holds; with m.eobs[k] == 1 its first coefficient alone,
+ *     and only where vp8ir_block_kind(&m, k) is 1; every other block 0.
+ *   - position (0, 0) of a luma block of a Y2 macroblock: 0, whatever the stream's bytes hold there (its DC is not coded there).
+ *   - the Y2 block: with m.eobs[24] > 1 the sixteen values of m.y2, with m.eobs[24] == 1 its first alone, with 0 nothing.
+ * stage VP8HIP_COEF_DEQUANT, the `short`s that enter the inverse transforms:
+ *   - each LEVELS value times its factor (the first of a block: the dc factor, the others the ac factor; y1dc / y1ac, uvdc / uvac,
+ *     y2dc / y2ac) truncated to int16 (vp8_dequantize_b_c);
+ *   - but position (0, 0) of a luma block of a Y2 macroblock that is not skipped: that block's output of vp8_short_inv_walsh4x4_c --
+ *     of vp8_short_inv_walsh4x4_1_c with m.eobs[24] <= 1 -- as vp8hip_frames_residual_async defines it, with factor 1.
+ *   So vp8_short_idct4x4llm_c's arithmetic on a DEQUANT block gives vp8hip_frames_residual_async's block for EVERY block -- the full
+ *   transform of a lone DC is (dc + 4) >> 3 everywhere, vp8_dc_only_idct_add_c's value -- and the inverse WHT of the DEQUANT Y2 block
+ *   gives the luma DCs.
+ * The tensor: the planes asked for (planes: VP8HIP_COEF_Y | _U | _V | _Y2) back to back in bit order, each dense.  With G = 4 for Y,
+ * 2 for U and V, 1 for Y2 -- the blocks of a macroblock each way -- a plane is
+ *   VP8HIP_COEF_CHANNELS  [nfreq][G * R][G * C]: channel j at (block row, block column) is position j = 4 * v + u of that block
+ *                         (VP8HIP_COEF_RASTER), or position zigzag[j] (VP8HIP_COEF_ZIGZAG; the VP8 scan 0 1 4 8 5 2 3 6 9 12 13 10
+ *                         7 11 14 15), for j < nfreq: the first nfreq of the order;
+ *   VP8HIP_COEF_INPLACE   [4 * G * R][4 * G * C]: position (v, u) of block (by, bx) at (4 * by + v, 4 * bx + u) -- the residual's
+ *                         geometry; needs nfreq == 16 and VP8HIP_COEF_RASTER.
+ * dtype and scale: vp8hip_frames_residual_async's rule, scale[k] for plane k (Y, U, V, Y2): the int16 as defined, or
+ * (float)((double)v * (double)scale[k]), or that float rounded to nearest-even as a half.
+ * Whole-piece stores (8 bytes of int16 or halves, 16 of floats) go where a plane's row is a multiple of 4 elements and dst and
+ * dst_stride are aligned to the piece; everywhere else -- CHANNELS: U and V with odd C, Y2 with C % 4 != 0 -- element by element, each
+ * once.  Only bytes inside [dst + i * dst_stride, + size) are written.
+ * Enqueued on the context's stream like vp8hip_frames_residual_async and ordered the same against later writers of the slots.  No
+ * device memory is added and no frame buffer is touched.  Returns -2 with nothing enqueued for what vp8hip_frames_residual_async
+ * refuses of slots and destination; a bad stage, layout, order or dtype; nfreq outside 1..16; INPLACE with nfreq != 16 or ZIGZAG; no
+ * plane bit or an unknown one.
+ * vp8hip_coef_size: bytes of one frame's tensor on ctx; 0 for the parameters the call refuses, and for a NULL (or not yet
+ * configured) context: the grid is the context's.
+ * vp8hip_dequant_factors: out[s] = y1dc, y1ac, y2dc, y2ac, uvdc, uvac of segment s for header h, what a consumer of LEVELS needs beside
+ * them.  Host only: no context, no GPU.  Returns 0, or -2 for a null pointer. */
+enum { VP8HIP_COEF_DEQUANT = 0, VP8HIP_COEF_LEVELS = 1 };          /* stage  */
+enum { VP8HIP_COEF_CHANNELS = 0, VP8HIP_COEF_INPLACE = 1 };        /* layout */
+enum { VP8HIP_COEF_RASTER = 0, VP8HIP_COEF_ZIGZAG = 1 };           /* order  */
+#define VP8HIP_COEF_Y 1    /* bit order = plane order */
+#define VP8HIP_COEF_U 2
+#define VP8HIP_COEF_V 4
+#define VP8HIP_COEF_Y2 8
+typedef struct vp8hip_coef {
+    int stage, layout, order;
+    int nfreq;                 /* 1..16: channels kept, CHANNELS layout */
+    unsigned planes;           /* VP8HIP_COEF_* bits, at least one */
+    int dtype;                 /* VP8HIP_RES_I16 / F16 / F32 */
+    float scale[4];            /* Y, U, V, Y2; float types only */
+} vp8hip_coef;
+size_t vp8hip_coef_size(const vp8hip_ctx *ctx, const vp8hip_coef *p);
+int  vp8hip_frames_coef_async(vp8hip_ctx *ctx, const int *slots, int n, const vp8hip_coef *p, void *dst, size_t dst_stride);
+int  vp8hip_dequant_factors(const vp8ir_frame_hdr *h, int16_t out[4][6]);
 /* ACCUMULATED motion, for models that take a P frame's flow and residual relative to one anchor picture (CoViAR's accumulate=True):
  * every pixel traced back, hop by hop, through the frames it was predicted from to the key frame that started the group.
  * The TRACE of a frame is d_h * d_w dwords, row-major, over the display-size luma grid d_w x d_h of the context (no other size:

@@ -512,6 +512,63 @@ def split_residual(t, gw, gh):
     return split_i420(t, gw, gh)
 
 
+COEF_STAGES = {"dequant": 0, "levels": 1}                     # VP8HIP_COEF_DEQUANT, LEVELS
+COEF_LAYOUTS = {"channels": 0, "inplace": 1}                  # VP8HIP_COEF_CHANNELS, INPLACE
+COEF_ORDERS = {"raster": 0, "zigzag": 1}                      # VP8HIP_COEF_RASTER, ZIGZAG
+COEF_PLANES = {"y": 1, "u": 2, "v": 4, "y2": 8}               # VP8HIP_COEF_*: bit order = plane order
+COEF_CELLS = {"y": 4, "u": 2, "v": 2, "y2": 1}                # blocks of a macroblock each way
+COEF_ZIGZAG = (0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15)     # channel j of "zigzag" is position COEF_ZIGZAG[j] = 4 * v + u
+
+
+def _coef_params(stage, layout, planes, nfreq, order, dtype):
+    """-> (CoefParams, its dtype number, its plane mask), or None for names the tables do not have.  (Numbers go through as they
+    are: the library judges them.)"""
+    dt, mask = _elem_dtype(dtype, _INT16_DTYPES), _plane_mask(planes, COEF_PLANES, False)
+    if dt is None or mask is None or stage not in COEF_STAGES or layout not in COEF_LAYOUTS or order not in COEF_ORDERS:
+        return None
+    return CoefParams(COEF_STAGES[stage], COEF_LAYOUTS[layout], COEF_ORDERS[order], int(nfreq), mask, dt), dt, mask
+
+
+def coef_size(ctx, stage="dequant", layout="channels", planes=("y", "u", "v"), nfreq=16, order="raster", dtype=RES_I16):
+    """bytes of one frame's tensor of Vp8Hip.frames_coef on context `ctx`, a Vp8Hip (vp8hip_coef_size): the planes asked for, each
+    nfreq * (G * mb_rows) * (G * mb_cols) elements with G = 4, 2, 2, 1 for "y", "u", "v", "y2" ("inplace": nfreq is 16); 0 for what
+    the call refuses -- an unknown stage, layout, order, type or plane, no plane, nfreq outside 1..16, "inplace" with nfreq below 16
+    or "zigzag" -- and for ctx None: there is only the native grid, which is the context's."""
+    made = _coef_params(stage, layout, planes, nfreq, order, dtype)
+    if made is None:
+        return 0
+    return int(load_hip().vp8hip_coef_size(None if ctx is None else ctx.h, ctypes.byref(made[0])))
+
+
+def split_coef(t, mb_cols, mb_rows, layout="channels", planes=("y", "u", "v"), nfreq=16):
+    """{plane: view} of coefficient frames t [..., elements] (numpy or torch) as Vp8Hip.frames_coef writes them, the planes back to
+    back in bit order: "channels" [..., nfreq, G * mb_rows, G * mb_cols], "inplace" [..., 4 * G * mb_rows, 4 * G * mb_cols]"""
+    mask = _plane_mask(planes, COEF_PLANES, False)
+    if mask is None or layout not in COEF_LAYOUTS:
+        raise ValueError(f"split_coef: planes {planes!r}, layout {layout!r}")
+    views, at = {}, 0
+    for name, bit in COEF_PLANES.items():
+        if mask & bit:
+            g = COEF_CELLS[name]
+            shape = (int(nfreq), g * mb_rows, g * mb_cols) if layout == "channels" else (4 * g * mb_rows, 4 * g * mb_cols)
+            size = int(np.prod(shape))
+            views[name] = t[..., at:at + size].reshape(tuple(t.shape[:-1]) + shape)
+            at += size
+    if at != t.shape[-1]:
+        raise ValueError(f"split_coef: {t.shape[-1]} elements a frame, the planes take {at}")
+    return views
+
+
+def dequant_factors(hdr):
+    """int16 [4, 6]: y1dc, y1ac, y2dc, y2ac, uvdc, uvac of each segment for frame header `hdr` (vp8hip_dequant_factors; on the host, no
+    GPU): what turns the "levels" of Vp8Hip.frames_coef into its "dequant" values -- but for the luma DCs of macroblocks with a Y2
+    block, which come out of that block's inverse WHT."""
+    out = np.zeros((4, 6), np.int16)
+    if load_hip().vp8hip_dequant_factors(ctypes.byref(hdr), out.ctypes.data):
+        raise ValueError("dequant_factors: refused")
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # HIP pixel path (vp8hip.h)
 # ------------------------------------------------------------------------------------------
@@ -538,6 +595,11 @@ class SideParams(ctypes.Structure):         # vp8hip_side, include/vp8hip.h
 
 class ResidualParams(ctypes.Structure):     # vp8hip_residual, include/vp8hip.h
     _fields_ = [("dst_w", c_int), ("dst_h", c_int), ("layout", c_int), ("dtype", c_int), ("scale", ctypes.c_float * 3)]
+
+
+class CoefParams(ctypes.Structure):         # vp8hip_coef, include/vp8hip.h
+    _fields_ = [("stage", c_int), ("layout", c_int), ("order", c_int), ("nfreq", c_int), ("planes", ctypes.c_uint), ("dtype", c_int),
+                ("scale", ctypes.c_float * 4)]
 
 
 class TraceFlowParams(ctypes.Structure):    # vp8hip_trace_flow, include/vp8hip.h
@@ -638,6 +700,10 @@ def load_hip():
         L.vp8hip_residual_size.argtypes = [c_void_p, ctypes.POINTER(ResidualParams)]
         L.vp8hip_residual_size.restype = c_size_t
         L.vp8hip_frames_residual_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(ResidualParams), c_void_p, c_size_t]
+        L.vp8hip_coef_size.argtypes = [c_void_p, ctypes.POINTER(CoefParams)]
+        L.vp8hip_coef_size.restype = c_size_t
+        L.vp8hip_frames_coef_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(CoefParams), c_void_p, c_size_t]
+        L.vp8hip_dequant_factors.argtypes = [c_void_p, c_void_p]
         L.vp8hip_trace_size.argtypes = [c_void_p]
         L.vp8hip_trace_size.restype = c_size_t
         L.vp8hip_frames_trace_async.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int]
@@ -1089,6 +1155,45 @@ class Vp8Hip:
                               lambda arr_out, stride: self.L.vp8hip_frames_residual_async(
                                   self.h, (c_int * max(n, 1))(*slots), n, ctypes.byref(p), arr_out, stride),
                               "vp8hip_frames_residual_async")[0]
+
+    def frames_coef(self, slots, stage="dequant", layout="channels", planes=("y", "u", "v"), nfreq=16, order="raster", dtype=None, scale=None,
+                    out=None):
+        """IR slots `slots` (any order, repeats allowed) as transform-coefficient tensors on the context's device
+        (vp8hip_frames_coef_async; include/vp8hip.h has the definition): stage "levels", what the stream codes, or "dequant", the
+        values that enter the inverse transforms.  -> {plane: view} for the planes of `planes` ("y", "u", "v", "y2", or the mask), views
+        into ONE tensor [n, elements] that holds them back to back in bit order (split_coef): layout "channels" [n, nfreq, G * mb_rows,
+        G * mb_cols] with G = 4, 2, 2, 1 blocks of a macroblock each way, channel j position j = 4 * v + u of the block (order "raster")
+        or position COEF_ZIGZAG[j] ("zigzag"), the first nfreq of them; "inplace" [n, 4 * G * mb_rows, 4 * G * mb_cols], the residual's
+        geometry (nfreq 16, "raster").  The coded area only: coefficients are not resampled.  torch.int16 (the default), torch.float16
+        or torch.float32; float types: float32(float64(v) * scale[plane]) with scale = one number or one per plane of (Y, U, V, Y2),
+        float32 (default 1).  `out`: the [n, elements] tensor to fill, each frame dense, stride(0) free.  Stream ordering, the `import
+        torch` first rule and the remark on record_stream: as frames_scaled."""
+        import torch
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        dtype = torch.int16 if dtype is None else dtype
+        made = _coef_params(stage, layout, planes, nfreq, order, dtype)
+        if made is None:
+            raise ValueError(f"frames_coef: stage {stage!r}, layout {layout!r}, order {order!r}, planes {planes!r}, dtype {dtype}")
+        p, dt, mask = made
+        if scale is None:
+            sc = (1.0,) * 4
+        elif np.ndim(scale) == 0:
+            sc = (float(scale),) * 4
+        else:
+            sc = tuple(float(v) for v in scale)
+            if len(sc) != 4:
+                raise ValueError(f"frames_coef: scale {scale!r}: one number, or one each for Y, U, V, Y2")
+        for c in range(4):
+            p.scale[c] = np.float32(sc[c])
+        size = int(self.L.vp8hip_coef_size(self.h, ctypes.byref(p)))
+        if not size:
+            raise ValueError(f"frames_coef: nfreq {nfreq} with layout {layout!r}, order {order!r}: refused (1..16; \"inplace\": 16, \"raster\")")
+        flat = self._to_torch("frames_coef", [("out", out, _INT16_DTYPES[dt], (n, size // (2, 2, 4)[dt]))],
+                              lambda arr_out, stride: self.L.vp8hip_frames_coef_async(
+                                  self.h, (c_int * max(n, 1))(*slots), n, ctypes.byref(p), arr_out, stride),
+                              "vp8hip_frames_coef_async")[0]
+        return split_coef(flat, self.g.aligned_w // 16, self.g.aligned_h // 16, layout, mask, p.nfreq)
 
     def trace_pool(self, n):
         """a pool of n traces for frames_trace on the context's device: a torch.int16 tensor [n, d_h, d_w, 2], (x', y') per pixel of

@@ -129,6 +129,26 @@ struct ResLaunch {
     ResSlot s[RES_MAX_FRAMES];
 };
 
+// One launch of vp8hip_frames_coef_async (vp8_coef.hip), as the host's plan (vp8hip_coef.hip) left it
+#define COEF_DEQUANT 0            // vp8hip_coef::stage
+#define COEF_LEVELS 1
+#define COEF_CHANNELS 0           // vp8hip_coef::layout
+#define COEF_INPLACE 1
+#define COEF_RUN 32               // macroblocks of a workgroup: a run of one macroblock row (records 4 KB + image 27.3 KB of LDS)
+#define COEF_PLANES 4             // Y, U, V, Y2: bit order of vp8hip_coef::planes
+struct CoefLaunch {
+    int mb_cols, mb_rows;
+    int runs;                     // runs of a macroblock row: (mb_cols + COEF_RUN - 1) / COEF_RUN
+    int stage, layout;            // COEF_*
+    int zigzag;                   // CHANNELS: channel j is position zigzag[j], not j
+    int nfreq;                    // CHANNELS: channels kept; INPLACE: 16
+    unsigned planes;              // VP8HIP_COEF_* bits
+    unsigned vec;                 // bit p: every whole group of four of plane p is one aligned piece
+    float scale[COEF_PLANES];     // float types
+    unsigned long long off[COEF_PLANES];      // where plane p begins in a frame's tensor, in elements
+    ResSlot s[RES_MAX_FRAMES];
+};
+
 // One launch of vp8hip_frames_trace_async (vp8_trace.hip), as the host's plan (vp8hip_trace.hip) left it
 #define TRACE_MAX_FRAMES 128      // jobs per launch (kernel arguments: 24 bytes each)
 struct TraceJob {                 // a job and its slot's header as of the call
@@ -328,20 +348,21 @@ __device__ __forceinline__ int wave_sum(int v)
 }
 
 // quantiser lookups (vp8/common/quant_common.c:14-37); VP8 format constants
-__constant__ static const unsigned short k_dc_q[128] = {
-    4, 5, 6, 7, 8, 9, 10, 10, 11, 12, 13, 14, 15, 16, 17, 17, 18, 19, 20, 20, 21, 21, 22, 22, 23, 23, 24, 25, 25, 26,
-    27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 46, 47, 48, 49, 50, 51, 52,
-    53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63, 64, 65, 66, 67, 68, 69, 70, 71, 72, 73, 74, 75, 76, 76, 77, 78, 79,
-    80, 81, 82, 83, 84, 85, 86, 87, 88, 89, 91, 93, 95, 96, 98, 100, 101, 102, 104, 106, 108, 110, 112, 114, 116,
+// (the values as macros: vp8hip_dequant_factors, vp8hip_coef.hip, keeps the same two tables on the host)
+#define VP8_DC_Q_VALUES \
+    4, 5, 6, 7, 8, 9, 10, 10, 11, 12, 13, 14, 15, 16, 17, 17, 18, 19, 20, 20, 21, 21, 22, 22, 23, 23, 24, 25, 25, 26,  \
+    27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 46, 47, 48, 49, 50, 51, 52,    \
+    53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63, 64, 65, 66, 67, 68, 69, 70, 71, 72, 73, 74, 75, 76, 76, 77, 78, 79,    \
+    80, 81, 82, 83, 84, 85, 86, 87, 88, 89, 91, 93, 95, 96, 98, 100, 101, 102, 104, 106, 108, 110, 112, 114, 116,      \
     118, 122, 124, 126, 128, 130, 132, 134, 136, 138, 140, 143, 145, 148, 151, 154, 157
-};
-__constant__ static const unsigned short k_ac_q[128] = {
-    4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33,
-    34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 60, 62, 64,
-    66, 68, 70, 72, 74, 76, 78, 80, 82, 84, 86, 88, 90, 92, 94, 96, 98, 100, 102, 104, 106, 108, 110, 112, 114, 116,
-    119, 122, 125, 128, 131, 134, 137, 140, 143, 146, 149, 152, 155, 158, 161, 164, 167, 170, 173, 177, 181, 185,
+#define VP8_AC_Q_VALUES \
+    4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33,  \
+    34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 60, 62, 64,    \
+    66, 68, 70, 72, 74, 76, 78, 80, 82, 84, 86, 88, 90, 92, 94, 96, 98, 100, 102, 104, 106, 108, 110, 112, 114, 116,   \
+    119, 122, 125, 128, 131, 134, 137, 140, 143, 146, 149, 152, 155, 158, 161, 164, 167, 170, 173, 177, 181, 185,      \
     189, 193, 197, 201, 205, 209, 213, 217, 221, 225, 229, 234, 239, 245, 249, 254, 259, 264, 269, 274, 279, 284
-};
+__constant__ static const unsigned short k_dc_q[128] = { VP8_DC_Q_VALUES };
+__constant__ static const unsigned short k_ac_q[128] = { VP8_AC_Q_VALUES };
 
 // ---- in-kernel stamps (diagnostic builds only: -DVP8_STAMPS; never in the product build) ------------------
 // Where a lane-per-row kernel's step spends its cycles: STAMP(i) adds the shader cycles since the previous stamp

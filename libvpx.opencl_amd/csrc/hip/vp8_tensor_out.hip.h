@@ -1,4 +1,4 @@
-// The output side shared by the kernels that hand something to a device consumer as tensors (vp8_side.hip, vp8_residual.hip, the
+// The output side shared by the kernels that hand something to a device consumer as tensors (vp8_side.hip, vp8_residual.hip, vp8_coef.hip, the
 // vp8_trace*.hip through vp8_trace_read.hip.h and, for the walk and the planar store, vp8_rgb.hip): the element of a dtype,
 // value x scale as the element's bits, the map between an output grid and the samples it is laid over in both directions, the share
 // of a row range among workgroups, the store of four neighbouring elements and a lane's walk over a row range in groups of four.

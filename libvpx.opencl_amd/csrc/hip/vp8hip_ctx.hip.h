@@ -4,8 +4,9 @@
 //   vp8hip_entropy.hip  vp8hip_entropy_decode
 //   vp8hip_postproc.hip vp8hip_postproc, vp8hip_mfqe
 //   vp8hip_visualize.hip vp8hip_visualize
-//   vp8hip_scale.hip, vp8hip_rgb.hip, vp8hip_side.hip, vp8hip_residual.hip   vp8hip_frames_scale_async, _rgb_async, _side_async,
-//                       _residual_async: frames, and what the slots hold beside them, as tensors in the caller's device memory
+//   vp8hip_scale.hip, vp8hip_rgb.hip, vp8hip_side.hip, vp8hip_residual.hip, vp8hip_coef.hip   vp8hip_frames_scale_async, _rgb_async,
+//                       _side_async, _residual_async, _coef_async: frames, and what the slots hold beside them, as tensors in the
+//                       caller's device memory
 //   vp8hip_trace.hip    vp8hip_frames_trace_async: accumulated motion in a pool in the caller's device memory (vp8_trace.hip), and
 //                       the pool's readers vp8hip_trace_flow_async (vp8_trace.hip), vp8hip_trace_residual_async
 //                       (vp8_trace_residual.hip) and vp8hip_trace_gather_async (vp8_trace_gather.hip); vp8hip_frames_wear_async and
@@ -209,6 +210,9 @@ unsigned vp8hip_segment_q_bits(const vp8ir_frame_hdr &h);
 // vp8hip_side.hip: what the kernels that read a slot's records take of its header (SideLaunch::q, HistSlotLaunch::q): vp8hip_segment_q_bits,
 // and bit 28 for a key frame
 unsigned vp8hip_side_header_bits(const vp8ir_frame_hdr &h);
+// vp8hip_residual.hip: what the kernels that dequantise take of a slot's header (ResLaunch::s, CoefLaunch::s): the quantiser index
+// of each segment and the five *_delta_q
+ResSlot vp8hip_res_header_bits(int slot, const vp8ir_frame_hdr &h);
 // vp8hip_trace.hip, for the calls that read a pool in the caller's device memory (those there and vp8hip_hist.hip): a pool of
 // pool_frames entries of the context's trace size, pool_stride apart, dword-aligned, inside one allocation of the device; and
 // whether [p, + stride * frames) and [q, + qstride * qframes) overlap

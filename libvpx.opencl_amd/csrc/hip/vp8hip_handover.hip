@@ -1,5 +1,5 @@
 // What the calls that hand something to a device consumer share on the host (vp8hip_frames_scale_async, _rgb_async, _side_async,
-// _residual_async, and of vp8hip_trace.hip vp8hip_frames_trace_async, vp8hip_trace_flow_async, _residual_async, _gather_async, vp8hip_frames_wear_async, vp8hip_trace_wear_async): the checks of their lists, of the output grid and of a destination in the caller's device memory, and what a
+// _residual_async, _coef_async, and of vp8hip_trace.hip vp8hip_frames_trace_async, vp8hip_trace_flow_async, _residual_async, _gather_async, vp8hip_frames_wear_async, vp8hip_trace_wear_async): the checks of their lists, of the output grid and of a destination in the caller's device memory, and what a
 // kernel needs of a slot's quantiser header.  Every check returns 0, or -2 with the error set, its text begun with `who`, the
 // calling function's name; none enqueues anything.
 #include "vp8hip_ctx.hip.h"

@@ -36,7 +36,7 @@ extern "C" size_t vp8hip_residual_size(const vp8hip_ctx *c, const vp8hip_residua
 
 // what the kernel needs of a slot's header: the quantiser index of each segment, and the five *_delta_q as the header holds them
 // (bytes: a header built by hand may hold any int8)
-static ResSlot res_header_bits(int slot, const vp8ir_frame_hdr &h)
+ResSlot vp8hip_res_header_bits(int slot, const vp8ir_frame_hdr &h)
 {
     ResSlot s;
     s.slot = slot;
@@ -95,7 +95,7 @@ extern "C" int vp8hip_frames_residual_async(vp8hip_ctx *c, const int *slots, int
     const unsigned groups = (unsigned)(L.mb_rows * L.runs * L.S);
     for (int i0 = 0; i0 < n; i0 += RES_MAX_FRAMES) {
         const int m = n - i0 < RES_MAX_FRAMES ? n - i0 : RES_MAX_FRAMES;
-        for (int k = 0; k < m; k++) L.s[k] = res_header_bits(slots[i0 + k], c->slots[slots[i0 + k]].hdr_copy);
+        for (int k = 0; k < m; k++) L.s[k] = vp8hip_res_header_bits(slots[i0 + k], c->slots[slots[i0 + k]].hdr_copy);
         hipLaunchKernelGGL(kernel, dim3(groups, (unsigned)m), dim3(256), 0, c->stream, (const char *)c->slot_block_dev, c->slot_bytes, c->o_mbx,
                            c->o_blocks, (const char *)c->pool, (unsigned)cap, (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, L);
         HIPCHK(c, hipGetLastError());
