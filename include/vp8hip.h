@@ -855,6 +855,63 @@ int  vp8hip_trace_wear_hist_async(vp8hip_ctx *ctx, const int *idx, int n, unsign
                                   int pool_frames, void *dst, size_t dst_stride);
 int  vp8hip_trace_cover_hist_async(vp8hip_ctx *ctx, const int *idx, int n, unsigned planes, const void *count, size_t count_stride,
                                    int count_frames, void *dst, size_t dst_stride);
+/* STRUCTURAL SIMILARITY of picture pairs.  SSIM cannot be had from any histogram: it needs the joint second moments of two pictures
+ * over local windows.  vp8hip_frames_ssim_async computes what the reference reports beside PSNR for a picture pair (vp8_calc_ssim /
+ * vp8_calc_ssimg, vp8/encoder/ssim.c: vp8_ssim2 per plane, 8x8 windows on the 4-pixel grid "to penalize blocking artifacts") in
+ * the reference's integer definition, for any n jobs of vp8hip_hist_job (fb, ref_fb), in any order, with repeats.  ref_fb must be a
+ * frame buffer (-1 is refused); fb == ref_fb is legal.  The planes are those of vp8hip_frames_hist_async -- S(F), the display-size
+ * I420 image: luma d_w x d_h, chroma ((d_w + 1) / 2) x ((d_h + 1) / 2) --, chosen with VP8HIP_HIST_Y | _U | _V, in bit order.
+ *
+ * WINDOWS.  A plane of pw x ph has a window with its top left sample at row 4 * wy, column 4 * wx for every 4 * wy < ph - 8 and
+ * 4 * wx < pw - 8 -- vp8_ssim2's loop, strict < included: the last aligned window is left out as the reference leaves it out --,
+ * that is nwx = pw > 8 ? (pw - 5) / 4 : 0 columns and likewise nwy rows of windows (vp8hip_ssim_windows: host only, no context and
+ * no GPU; -2, and 0 x 0, for a size outside 1..16383).  Every window lies inside the display-size plane and nothing outside it is
+ * read.  A plane with pw <= 8 or ph <= 8 has no windows (the reference returns 0 / 0 there).
+ *
+ * VALUE.  With the five sums over a window's 64 samples (s from fb, r from ref_fb) in signed 64-bit integers, c1 = 26634 and
+ * c2 = 239708 (similarity() with count 64):
+ *     n = (2 * Ss * Sr + c1) * (2 * 64 * Ssr - 2 * Ss * Sr + c2)
+ *     d = (Ss * Ss + Sr * Sr + c1) * (64 * Sss - Ss * Ss + 64 * Srr - Sr * Sr + c2)
+ *     v = (double)n / (double)d
+ * the two conversions rounded to nearest and the division IEEE-correct.  Always d > 0 and |v| <= 1 (Cauchy-Schwarz on both factors).
+ *
+ * OUTPUTS, either of which may be NULL, not both:
+ *   scores  [popcount(planes)][2] of int64, job i at scores + i * scores_stride BYTES (both multiples of 8;
+ *           vp8hip_ssim_scores_size(popcount) = 16 * popcount, 0 for a popcount outside 1..3): [p][0] = the sum over the plane's
+ *           windows of llrint(v * 2^32) (round half to even; the product is exact), [p][1] = the number of windows, nwx * nwy.  The
+ *           sum is in integers: the same bits in every run, whatever order lanes and workgroups arrive in.  The mean is
+ *           [p][0] / 2^32 / [p][1]; it differs from vp8_ssim2's result by at most 2^-33 + N * 2^-52 (the rounding to Q32, and the
+ *           reference's own summation of N doubles).  |total| < 2^57.  fb == ref_fb gives exactly count << 32.
+ *   map     the planes asked for, back to back, plane p a dense [nwy_p][nwx_p] of map_dtype, job i at map + i * map_stride BYTES
+ *           (both aligned to the element): VP8HIP_SSIM_F32 is (float)v, VP8HIP_SSIM_F16 that float rounded to nearest-even.
+ *           vp8hip_ssim_map_size(ctx, p): the bytes of one job's map, 0 for what the call refuses on p alone (and for a NULL or
+ *           unconfigured ctx).  Every element is written once, element by element, the lanes of a wave on neighbouring windows of
+ *           a row.  map_dtype is 0 (no map: only where map is NULL), VP8HIP_SSIM_F16 or VP8HIP_SSIM_F32.
+ *
+ * The call is its neighbours: enqueued on the context's stream -- a later writer of a frame buffer runs behind it, an earlier
+ * vp8hip_decode is seen --; each frame buffer is read in a form it has (raster where it exists, else tiles; the two of a pair
+ * independently; one never written reads as zeros), nothing is converted, no raster pool is made and no device memory is added; no
+ * frame buffer is written; only bytes inside [scores + i * scores_stride, + size) and [map + i * map_stride, + size) are written.
+ * It returns -2 with nothing enqueued for n < 1; an fb or ref_fb out of range (ref_fb < 0 included); planes == 0 or bits other than
+ * VP8HIP_HIST_Y | _U | _V; both destinations NULL; a map asked for when no plane asked for has a window; a map_dtype other than
+ * the above, or 0 with a map; a stride below the size; a destination or stride not aligned (scores: 8, map: the element); a
+ * destination that is not device memory of the context's device or that cannot hold n outputs; scores and map that overlap.
+ *
+ * vp8hip_ssim_share(ctx, n, planes): how many workgroups share each job of a call of n jobs over `planes` on this context -- the
+ * call's own arithmetic.  1: a workgroup owns a job and stores its scores; more: the scores are first set to {0, count} and the
+ * workgroups add their sums to them.  0 for what the call refuses of n and planes.  The results do not depend on it. */
+#define VP8HIP_SSIM_F16 1
+#define VP8HIP_SSIM_F32 2
+typedef struct vp8hip_ssim {
+    unsigned planes;           /* VP8HIP_HIST_Y | _U | _V, at least one */
+    int map_dtype;             /* 0 (no map), VP8HIP_SSIM_F16, VP8HIP_SSIM_F32 */
+} vp8hip_ssim;
+int  vp8hip_ssim_windows(int w, int h, int *nwx, int *nwy);
+size_t vp8hip_ssim_scores_size(int planes_popcount);
+size_t vp8hip_ssim_map_size(const vp8hip_ctx *ctx, const vp8hip_ssim *p);
+int  vp8hip_ssim_share(const vp8hip_ctx *ctx, int n, unsigned planes);
+int  vp8hip_frames_ssim_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int n, const vp8hip_ssim *p, void *scores, size_t scores_stride,
+                              void *map, size_t map_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

@@ -477,6 +477,87 @@ def hist_size(planes):
     return int(load_hip().vp8hip_hist_size(int(planes)))
 
 
+SSIM_F16, SSIM_F32 = 1, 2                                    # VP8HIP_SSIM_F16, _F32
+_SSIM_DTYPES = (None, "float16", "float32")                   # by VP8HIP_SSIM_*: 0 is no map
+
+
+def _ssim_dtype(map_dtype):
+    """a map type's number -- SSIM_F16 / SSIM_F32 or the torch / numpy type's name -- or None for anything else"""
+    dt = _elem_dtype(map_dtype, _SSIM_DTYPES)
+    return dt if dt in (SSIM_F16, SSIM_F32) else None
+
+
+def ssim_windows(w, h):
+    """(nwx, nwy): the windows Vp8Hip.frames_ssim has in a plane of w x h (vp8hip_ssim_windows; on the host, no GPU): vp8_ssim2's 8x8
+    windows on the 4-pixel grid, the last aligned one left out as the reference leaves it out -- (w - 5) // 4 columns for w > 8, else
+    none, and likewise rows.  ValueError for a size outside 1..16383."""
+    nwx, nwy = c_int(), c_int()
+    if load_hip().vp8hip_ssim_windows(int(w), int(h), ctypes.byref(nwx), ctypes.byref(nwy)):
+        raise ValueError(f"ssim_windows: {w}x{h}: refused (sizes 1..16383)")
+    return nwx.value, nwy.value
+
+
+def _ssim_plane_windows(w, h, planes):
+    """-> [(nwx, nwy)] of the planes of `planes` ("y", "u", "v" or the mask) of a picture of w x h, in bit order; a plane that lacks
+    windows one way has none: (0, 0); None for no plane or an unknown one"""
+    mask = _plane_mask(planes, HIST_PLANES, False)
+    if mask is None:
+        return None
+    out = []
+    for b in range(3):
+        if mask >> b & 1:
+            nwx, nwy = ssim_windows((w + 1) // 2 if b else w, (h + 1) // 2 if b else h)
+            out.append((nwx, nwy) if nwx and nwy else (0, 0))
+    return out
+
+
+def ssim_sizes(w, h, planes=("y", "u", "v"), map_dtype=None):
+    """(bytes of one job's scores, bytes of its map) of Vp8Hip.frames_ssim at a display size of w x h (vp8hip_ssim_scores_size, and
+    what vp8hip_ssim_map_size gives on a context of that size): 16 a plane, and the planes' windows back to back in map_dtype
+    (SSIM_F16 / SSIM_F32 or the torch / numpy type's name; None: no map, 0 bytes).  (0, 0) for no plane or an unknown one, or an
+    unknown type."""
+    wins = _ssim_plane_windows(int(w), int(h), planes)
+    dt = None if map_dtype is None else _ssim_dtype(map_dtype)
+    if wins is None or (map_dtype is not None and dt is None):
+        return 0, 0
+    return int(load_hip().vp8hip_ssim_scores_size(len(wins))), 0 if dt is None else sum(a * b for a, b in wins) * (0, 2, 4)[dt]
+
+
+def split_ssim_map(t, w, h, planes=("y", "u", "v")):
+    """the flat map [n, elems] of Vp8Hip.frames_ssim at a display size of w x h -> a list of views [n, nwy, nwx], one per plane asked
+    for, in bit order (a plane without windows: [n, 0, 0])"""
+    wins = _ssim_plane_windows(int(w), int(h), planes)
+    if wins is None or t.ndim != 2 or t.shape[1] != sum(a * b for a, b in wins):
+        raise ValueError(f"split_ssim_map: planes {planes!r} of {w}x{h} are not a map of {tuple(t.shape)}")
+    out, off = [], 0
+    for nwx, nwy in wins:
+        out.append(t[:, off:off + nwx * nwy].reshape(t.shape[0], nwy, nwx))
+        off += nwx * nwy
+    return out
+
+
+def ssim_mean(scores):
+    """the scores [n, P, 2] of Vp8Hip.frames_ssim (a torch tensor or an array) -> float64 [n, P]: total / 2^32 / count, what
+    vp8_ssim2 returns to within 2^-33 + N * 2^-52; NaN where the count is 0 (the reference's 0 / 0)"""
+    s = np.asarray(scores.cpu() if hasattr(scores, "cpu") else scores).astype(np.int64)
+    if s.ndim < 1 or s.shape[-1] != 2:
+        raise ValueError("ssim_mean: scores are [..., 2]: total, count")
+    total, count = s[..., 0].astype(np.float64), s[..., 1].astype(np.float64)     # (|total| < 2^57: the conversion rounds, 2^-53 relative)
+    out = np.full(total.shape, np.nan)
+    np.divide(total / 4294967296.0, count, out=out, where=count != 0)
+    return out
+
+
+def ssim_combined(means, how="ssimg"):
+    """the per-plane means [..., 3] (Y, U, V) as one figure, by the two weightings of vp8/encoder/ssim.c: "ssimg" = (4a + b + c) / 6
+    (vp8_calc_ssimg), "ssim" = 0.8a + 0.1(b + c) (vp8_calc_ssim)"""
+    m = np.asarray(means, np.float64)
+    if m.ndim < 1 or m.shape[-1] != 3 or how not in ("ssimg", "ssim"):
+        raise ValueError("ssim_combined: means [..., 3] and \"ssimg\" or \"ssim\"")
+    a, b, c = m[..., 0], m[..., 1], m[..., 2]
+    return (a * 4 + b + c) / 6 if how == "ssimg" else a * 0.8 + 0.1 * (b + c)
+
+
 GATHER_FILTERS = {"nearest": 0, "bilinear": 1}              # VP8HIP_GATHER_NEAREST, BILINEAR
 GATHER_LAYOUTS = {"planar": 0, "channels_last": 1}            # VP8HIP_GATHER_PLANAR, CHANNELS_LAST
 
@@ -639,6 +720,10 @@ class HistJob(ctypes.Structure):            # vp8hip_hist_job, include/vp8hip.h
     _fields_ = [("fb", ctypes.c_int32), ("ref_fb", ctypes.c_int32)]
 
 
+class SsimParams(ctypes.Structure):         # vp8hip_ssim, include/vp8hip.h
+    _fields_ = [("planes", ctypes.c_uint), ("map_dtype", c_int)]
+
+
 class VisParams(ctypes.Structure):         # vp8hip_vis, include/vp8hip.h
     _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
                 ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
@@ -736,6 +821,13 @@ def load_hip():
         L.vp8hip_slots_hist_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_uint, c_void_p, c_size_t]
         L.vp8hip_trace_wear_hist_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_uint, c_void_p, c_size_t, c_int, c_void_p, c_size_t]
         L.vp8hip_trace_cover_hist_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.c_uint, c_void_p, c_size_t, c_int, c_void_p, c_size_t]
+        L.vp8hip_ssim_windows.argtypes = [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+        L.vp8hip_ssim_scores_size.argtypes = [c_int]
+        L.vp8hip_ssim_scores_size.restype = c_size_t
+        L.vp8hip_ssim_map_size.argtypes = [c_void_p, ctypes.POINTER(SsimParams)]
+        L.vp8hip_ssim_map_size.restype = c_size_t
+        L.vp8hip_ssim_share.argtypes = [c_void_p, c_int, ctypes.c_uint]
+        L.vp8hip_frames_ssim_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(SsimParams), c_void_p, c_size_t, c_void_p, c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1428,6 +1520,46 @@ class Vp8Hip:
         "seen" is how many anchor pixels survive into the frame.  `out` must not overlap the pool.  Stream ordering: as
         frames_scaled."""
         return self._entries_hist("trace_cover_hist", count, idx, planes, out)
+
+    def frames_ssim(self, jobs, planes=("y", "u", "v"), map_dtype=None, out_scores=None, out_map=None):
+        """The structural similarity of picture pairs on the context's device (vp8hip_frames_ssim_async): vp8_ssim2's 8x8 windows on
+        the 4-pixel grid over the display-size planes, in the reference's integer definition.  `jobs`: a list of (fb, ref_fb), any
+        order, repeats allowed, fb == ref_fb legal.  planes: "y", "u", "v" (or the mask), in that order.  Returns the scores, a
+        torch.int64 tensor [n, P, 2]: [i, p, 0] the sum over plane p's windows of the window value in Q32 (rounded half to even),
+        [i, p, 1] the number of windows -- ssim_mean gives the means, ssim_combined the reference's two weightings --; the same bits
+        in every run.  With map_dtype (torch.float16 / torch.float32, or SSIM_F16 / SSIM_F32) returns (scores, map): the window
+        values themselves, a tensor [n, elems] of that type, the planes back to back, each a dense [nwy, nwx] (split_ssim_map gives
+        the views; ssim_windows the sizes).  Each frame buffer is read in the form it has; nothing is converted or allocated.
+        `out_scores`, `out_map`: tensors of those shapes and types, each job dense, stride(0) free.  Stream ordering, the `import
+        torch` first rule and the remark on record_stream: as frames_scaled."""
+        who = "frames_ssim"
+        items = [tuple(int(v) for v in j) if isinstance(j, (tuple, list)) else None for j in jobs]
+        if any(j is None or len(j) != 2 for j in items):
+            raise ValueError(f"{who}: jobs are (fb, ref_fb)")
+        n, mask, nplanes = self._hist_args(who, items, planes, HIST_PLANES)
+        if any(fb < 0 or ref < 0 for fb, ref in items):
+            raise ValueError(f"{who}: a negative frame buffer")
+        dt = 0 if map_dtype is None else _ssim_dtype(map_dtype)
+        if dt is None or (out_map is not None and not dt):
+            raise ValueError(f"{who}: map_dtype {map_dtype!r} (float16 or float32; out_map needs one)")
+        p = SsimParams(mask, dt)
+        outs = [("out_scores", out_scores, "int64", (n, nplanes, 2))]
+        if dt:
+            size = int(self.L.vp8hip_ssim_map_size(self.h, ctypes.byref(p)))
+            if not size:
+                raise ValueError(f"{who}: planes {planes!r} of {self.width}x{self.height} have no windows: no map")
+            outs.append(("out_map", out_map, _SSIM_DTYPES[dt], (n, size // (0, 2, 4)[dt])))
+        arr = (HistJob * n)(*items)
+        made = self._to_torch(who, outs, lambda sp, ss, mp=None, ms=0: self.L.vp8hip_frames_ssim_async(self.h, arr, n, ctypes.byref(p), sp, ss, mp, ms),
+                              "vp8hip_frames_ssim_async")
+        return tuple(made) if dt else made[0]
+
+    def ssim_share(self, n, planes=("y", "u", "v")):
+        """how many workgroups share each job of a frames_ssim call of n jobs over `planes` (vp8hip_ssim_share): 1 -- a workgroup
+        owns a job and stores its scores -- or more -- the scores are zeroed first and the workgroups add to them.  The results do
+        not depend on it."""
+        mask = _plane_mask(planes, HIST_PLANES, False)
+        return int(self.L.vp8hip_ssim_share(self.h, int(n), mask or 0))
 
     def trace_residual(self, pool, jobs, width=None, height=None, dtype=None, matrix="bt601", order="rgb", scale=None, out=None):
         """The accumulated residual of `jobs` -- a list of (fb, entry, anchor_fb): the frame buffer that holds a frame, the entry of

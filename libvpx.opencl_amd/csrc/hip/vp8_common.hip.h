@@ -268,6 +268,39 @@ struct HistEntryLaunch {
     int idx[HIST_MAX_JOBS];       // pool entry of job k of the launch
 };
 
+// One launch of vp8hip_frames_ssim_async (vp8_ssim.hip), as the host's plan (vp8hip_ssim.hip) left it.  A plane's windows are cut
+// into bands of SSIM_BAND_ROWS window rows and a band into pieces of SSIM_BAND_COLS window columns; a job's pieces, the planes asked
+// for one after the other, are dealt to the gridDim.x workgroups that share the job.  Where that is more than one and scores are
+// asked for, vp8_ssim_fill_kernel has run first and the workgroups add their sums with global atomics
+#define SSIM_MAX_JOBS 256         // jobs per launch (kernel arguments: 8 bytes each)
+#define SSIM_BAND_ROWS 16         // window rows a piece owns: it stages SSIM_BAND_ROWS + 1 cell rows, the last one the halo
+#define SSIM_BAND_COLS 63         // window columns a piece owns: it stages SSIM_BAND_COLS + 1 cell columns, the last one the halo
+#define SSIM_F16 1                // VP8HIP_SSIM_F16, _F32
+#define SSIM_F32 2
+struct SsimPlane {                // a plane asked for, in bit order
+    int pl;                       // 0 Y, 1 U, 2 V
+    int nwx, nwy;                 // its windows
+    int px;                       // pieces a band is cut into
+    int first;                    // the job's pieces before this plane's
+    int map_off;                  // elements of a job's map before this plane's
+};
+struct SsimLaunch {
+    int dw, dh;                   // the display size
+    int mb_cols, mb_rows;
+    int y_off, u_off, v_off, y_stride, uv_stride;    // the raster form: the planes' origins in a frame buffer and their strides
+    int S;                        // workgroups that share a job's pieces (gridDim.x)
+    int np;                       // planes asked for
+    int pieces;                   // of a job, all planes
+    int scores;                   // 1: scores are written
+    int map_dtype;                // 0: no map; SSIM_F16 / SSIM_F32
+    SsimPlane p[3];
+    HistFrameJob j[SSIM_MAX_JOBS];    // (ref is never -1)
+};
+struct SsimFill {                 // what vp8_ssim_fill_kernel writes into every job's scores: {0, count} per plane
+    int np;
+    long long count[3];
+};
+
 #define WAVE 64
 
 // Macroblock tiles of the one-MB-row-per-lane pipeline (vp8_keyframe_simt.hip has the layout): three 128-byte lines per macroblock.

@@ -1,0 +1,49 @@
+// The display-size planes of a frame buffer in whichever form it has, for the kernels that read pictures and make no tensor of them
+// (vp8_hist.hip, vp8_ssim.hip): a piece of sixteen columns of a row (hist_read16) and one aligned dword of four (frame_read4), from
+// the raster form directly, from the tiles through ScaleSrc<SCALE_FROM_TILES> (vp8_scale_src.hip.h: the one place that knows the
+// tiles); a frame buffer never written reads as zeros and no address is formed.  The launch L says where the planes lie: dw, dh,
+// mb_cols, mb_rows, y_off, u_off, v_off, y_stride, uv_stride (HistFrameLaunch, SsimLaunch).
+#pragma once
+#include "vp8_scale_src.hip.h"
+
+struct HistFrame {
+    const uint8_t *raster, *tiles;
+    int form;                                    // SCALE_FROM_* (the same for every lane)
+};
+
+// columns x .. x + 15 of row y of plane PL (x a multiple of 16 below the plane's width pw), low byte first
+template <int PL>
+__device__ __forceinline__ u32x4_t hist_read16(const HistFrame &F, const HistFrameLaunch &L, int x, int y, int pw)
+{
+    u32x4_t v = {0u, 0u, 0u, 0u};
+    if (F.form == SCALE_FROM_RASTER) {
+        const int off = PL == 0 ? L.y_off : PL == 1 ? L.u_off : L.v_off;
+        v = *(const GLOBAL_AS u32x4_t *)((g_cu8p)F.raster + off + (long)y * (PL ? L.uv_stride : L.y_stride) + x);
+    } else if (F.form == SCALE_FROM_TILES) {
+        // (the tile's layout as vp8_scale_kernel hands it to ScaleSrc)
+        const ScaleSrc<SCALE_FROM_TILES> S{(g_cu8p)F.tiles, (L.mb_cols + 1) * VP8_TILE_BYTES, (PL ? 8 : 16) * L.mb_cols - 1,
+                                           (PL ? 8 : 16) * L.mb_rows - 1, PL ? 3 : 4, PL ? 4 : 12, PL ? 256 + 32 * (PL - 1) : 0,
+                                           PL ? 320 + 32 * (PL - 1) : 192};
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (x + 4 * i < pw) v[i] = S.template atN<4>(x + 4 * i, y);     // (pw <= the aligned width, a multiple of 8: the dword is inside it)
+    }
+    return v;
+}
+
+// columns x .. x + 3 of row y of plane PL (x a multiple of 4, x + 3 inside the plane: inside the aligned area), low byte first
+template <int PL, class Launch>
+__device__ __forceinline__ unsigned frame_read4(const HistFrame &F, const Launch &L, int x, int y)
+{
+    if (F.form == SCALE_FROM_RASTER) {
+        const int off = PL == 0 ? L.y_off : PL == 1 ? L.u_off : L.v_off;
+        return *(g_cu32p)((g_cu8p)F.raster + off + (long)y * (PL ? L.uv_stride : L.y_stride) + x);
+    }
+    if (F.form == SCALE_FROM_TILES) {
+        const ScaleSrc<SCALE_FROM_TILES> S{(g_cu8p)F.tiles, (L.mb_cols + 1) * VP8_TILE_BYTES, (PL ? 8 : 16) * L.mb_cols - 1,
+                                           (PL ? 8 : 16) * L.mb_rows - 1, PL ? 3 : 4, PL ? 4 : 12, PL ? 256 + 32 * (PL - 1) : 0,
+                                           PL ? 320 + 32 * (PL - 1) : 192};
+        return S.template atN<4>(x, y);
+    }
+    return 0u;
+}

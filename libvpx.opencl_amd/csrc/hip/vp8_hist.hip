@@ -17,7 +17,7 @@
 // FOUR SOURCES.
 //   pictures   a lane takes sixteen neighbouring columns of a row of one plane, Y, U, V one after the other through the same LDS:
 //              from the raster form one 16-byte load (rows of every plane start on 16-byte boundaries and end in a border wider than
-//              the piece), from the tiles four aligned dwords (ScaleSrc<SCALE_FROM_TILES>::atN<4>, vp8_scale_src.hip.h: the one
+//              the piece), from the tiles four aligned dwords (hist_read16, vp8_frame_read.hip.h; ScaleSrc<SCALE_FROM_TILES>::atN<4>, vp8_scale_src.hip.h: the one
 //              place that knows the tiles); a frame buffer never written reads as zeros and no address is formed.  The two frames
 //              of a pair are read independently, each in its form.  Columns past the plane's width are loaded where the aligned
 //              area has them and never counted.
@@ -28,7 +28,7 @@
 //              (load4_dword_aligned, vp8_trace_read.hip.h), the tail dword by dword, and WearPlanes / CoverPlanes say what a dword's
 //              planes are.  Pool values are data and never addresses.
 // Workgroups share a job by rows (tensor_share), as the invert's do.  Nothing but the outputs is written.
-#include "vp8_scale_src.hip.h"
+#include "vp8_frame_read.hip.h"
 #include "vp8_side_src.hip.h"
 #include "vp8_trace_read.hip.h"
 #include "vp8hip.h"
@@ -148,31 +148,6 @@ extern "C" __global__ void __launch_bounds__(256) vp8_hist_fill_kernel(uint8_t *
 #ifndef HIST_FRAME_LREP
 #define HIST_FRAME_LREP 4            // (-DHIST_FRAME_LREP=1: the variant DESIGN 4.20 measures the lane copies against)
 #endif
-struct HistFrame {
-    const uint8_t *raster, *tiles;
-    int form;                                    // SCALE_FROM_* (the same for every lane)
-};
-
-// columns x .. x + 15 of row y of plane PL (x a multiple of 16 below the plane's width pw), low byte first
-template <int PL>
-__device__ __forceinline__ u32x4_t hist_read16(const HistFrame &F, const HistFrameLaunch &L, int x, int y, int pw)
-{
-    u32x4_t v = {0u, 0u, 0u, 0u};
-    if (F.form == SCALE_FROM_RASTER) {
-        const int off = PL == 0 ? L.y_off : PL == 1 ? L.u_off : L.v_off;
-        v = *(const GLOBAL_AS u32x4_t *)((g_cu8p)F.raster + off + (long)y * (PL ? L.uv_stride : L.y_stride) + x);
-    } else if (F.form == SCALE_FROM_TILES) {
-        // (the tile's layout as vp8_scale_kernel hands it to ScaleSrc)
-        const ScaleSrc<SCALE_FROM_TILES> S{(g_cu8p)F.tiles, (L.mb_cols + 1) * VP8_TILE_BYTES, (PL ? 8 : 16) * L.mb_cols - 1,
-                                           (PL ? 8 : 16) * L.mb_rows - 1, PL ? 3 : 4, PL ? 4 : 12, PL ? 256 + 32 * (PL - 1) : 0,
-                                           PL ? 320 + 32 * (PL - 1) : 192};
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            if (x + 4 * i < pw) v[i] = S.template atN<4>(x + 4 * i, y);     // (pw <= the aligned width, a multiple of 8: the dword is inside it)
-    }
-    return v;
-}
-
 // |a - b| byte by byte
 __device__ __forceinline__ unsigned hist_absdiff4(unsigned a, unsigned b)
 {
