@@ -912,6 +912,82 @@ size_t vp8hip_ssim_map_size(const vp8hip_ctx *ctx, const vp8hip_ssim *p);
 int  vp8hip_ssim_share(const vp8hip_ctx *ctx, int n, unsigned planes);
 int  vp8hip_frames_ssim_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int n, const vp8hip_ssim *p, void *scores, size_t scores_stride,
                               void *map, size_t map_stride);
+/* BLOCK MOTION SEARCH between pictures.  What the stream codes of motion (vp8hip_frames_side_async, the traces) exists only for
+ * inter macroblocks, only between a frame and its references, and is a rate-distortion choice.  vp8hip_frames_motion_async computes,
+ * per macroblock of ANY picture pair, the best whole-pixel displacement and what that match costs: the reference's exhaustive
+ * search, vp8_full_search_sad_c (vp8/encoder/mcomp.c) over vp8_sad16x16_c, with vp8_variance16x16_c at the result, bit for bit.
+ * Jobs are vp8hip_hist_job (fb, ref_fb), any n, in any order, with repeats: fb holds the blocks (the reference's `what`), ref_fb is
+ * searched (`in_what`); ref_fb < 0 is refused; fb == ref_fb is legal.  Luma only, 16x16 only, whole pixels only.
+ *
+ * PICTURES.  A = 16 * mb_cols and B = 16 * mb_rows are the coded luma size.  S(F)(y, x), 0 <= y < B, 0 <= x < A, is the decoded luma of
+ * frame buffer F over the coded area, read in a form F has -- raster where it exists, else tiles; the two of a pair independently;
+ * a buffer never written reads as zeros.  E(F)(y, x) = S(F)(clamp(y, 0, B - 1), clamp(x, 0, A - 1)) for any y, x: the edge
+ * replication the reference's border extension gives, by coordinate clamps -- the raster form's borders are never read, and both
+ * forms give the same bits.
+ *
+ * Per macroblock (my, mx), with the distance d = p->distance in 1..64:
+ *   BOUNDS  cmin = -(16 mx + 16), cmax = 16 (mb_cols - 1 - mx) + 16, rmin = -(16 my + 16), rmax = 16 (mb_rows - 1 - my) + 16: the
+ *           reference's mv_col_min .. mv_row_max with VP8BORDERINPIXELS - 16 = 16 (vp8/encoder/encodeframe.c).
+ *   CENTRE  (cy, cx) in whole pixels: (0, 0) where `centre` is NULL; otherwise read from the caller's tensor in device memory,
+ *           [2][mb_rows][mb_cols] of int16, channel 0 = x, channel 1 = y, job i's at centre + i * centre_stride BYTES (both multiples
+ *           of 2), and clamped, cx to [cmin, cmax], cy to [rmin, rmax].  The value is data, never an address.  A caller seeds the
+ *           search with vp8hip_frames_side_async's vectors (>> 3) or with a coarser search of its own.  A centre tensor is refused on
+ *           a context of more than 255 macroblocks a side, where a clamped centre << 3 would leave int16.
+ *   CANDIDATES, in this order: the centre; then r from max(cy - d, rmin) up to but NOT including min(cy + d, rmax) and inside it c
+ *           from max(cx - d, cmin) up to but NOT including min(cx + d, cmax).  The exclusive upper ends are the reference's loop
+ *           (r < row_max, c < col_max): the row cy + d and the column cx + d are never searched, nor are the row rmax and the
+ *           column cmax unless the centre lies on them.  That omission is the reference's and is kept.
+ *   VALUE   of the candidate (r, c): sum over y, x in 0..15 of |S(fb)(16 my + y, 16 mx + x) - E(ref_fb)(16 my + r + y, 16 mx + c + x)|
+ *           plus, with a cost table, ((cost[0][r - cy + d] + cost[1][c - cx + d]) * sad_per_bit + 128) >> 8: mvsad_err_cost with the
+ *           cost centre at the search centre.  p->cost is a HOST pointer to int32 [2][2 d + 1] (row costs, then column costs; the last
+ *           entry of each, index 2 d, is never reached), entries 0..65535, copied at the call; sad_per_bit is 0..255.  cost == NULL
+ *           or sad_per_bit == 0: no cost term (and cost is not read).
+ *   BEST    the first candidate in that order whose value is strictly below all before it (the reference's `thissad < bestsad`): on a
+ *           flat block the centre, among equal values of the loop the first in raster order.  The reduction is by the key (value,
+ *           position in the order): the same bits in every run, whatever order lanes and waves arrive in.
+ *
+ * OUTPUTS, either of which may be NULL, not both; both dense per job on the macroblock grid:
+ *   mv      [2][mb_rows][mb_cols] of int16, job i at mv + i * mv_stride BYTES (both multiples of 2): channel 0 = c_best << 3,
+ *           channel 1 = r_best << 3 -- the units and the channel order of vp8hip_frames_side_async's I16 tensor, so that the two can
+ *           be compared or mixed element for element.  vp8hip_motion_mv_size(ctx) = 4 * mb_rows * mb_cols (0 for a NULL or
+ *           unconfigured ctx); it is the centre tensor's size too.
+ *   stats   [popcount(p->planes)][mb_rows][mb_cols] of uint32, job i at stats + i * stats_stride BYTES (both multiples of 4), the
+ *           planes in the order of their bits:
+ *             VP8HIP_MOTION_SAD     the best value, cost term included;
+ *             VP8HIP_MOTION_SAD0    the plain sum of absolute differences at the vector (0, 0), whatever the centre;
+ *             VP8HIP_MOTION_SSE     the sum of squared differences at the best candidate;
+ *             VP8HIP_MOTION_VAR     sse - (uint32)(((int64)sum * sum) >> 8) at the best candidate, sum the signed sum of differences:
+ *                                   vp8_variance16x16_c, written in 64 bits.  The reference's `int` product overflows for
+ *                                   |sum| > 46340 (a block within about 75 levels of 0 against one within about 75 of 255); there the
+ *                                   two differ, and this is the one without the overflow;
+ *             VP8HIP_MOTION_SRCVAR  the same formula for the block of fb against the constant 128: the spatial activity the
+ *                                   reference's encoder takes from vp8_variance16x16(src, VP8_VAR_OFFS, 0); |sum| <= 32768.
+ *           vp8hip_motion_stats_size(ctx, p) = 4 * popcount * mb_rows * mb_cols; 0 for what the call refuses on p alone (planes == 0
+ *           included) and for a NULL or unconfigured ctx.  p->planes is not read where stats is NULL, except for unknown bits.
+ *
+ * The call is its neighbours: enqueued on the context's stream -- a later writer of a frame buffer runs behind it, an earlier
+ * vp8hip_decode is seen --; nothing is converted, no raster pool is made and no device memory is added; no frame buffer is written;
+ * only bytes inside [mv + i * mv_stride, + size) and [stats + i * stats_stride, + size) are written.  It returns -2 with nothing
+ * enqueued for n < 1; an fb or ref_fb out of range (ref_fb < 0 included); a distance outside 1..64; plane bits other than the
+ * five; stats with planes == 0; both outputs NULL; a cost entry outside 0..65535 (where the table is read) or a sad_per_bit outside
+ * 0..255; a stride below the size; a pointer or stride not aligned (mv: 2, stats: 4, centre: 2); an output or a centre tensor that
+ * is not device memory of the context's device or that cannot hold n jobs; outputs that overlap each other or the centre tensor; a
+ * centre tensor on more than 255 macroblocks a side. */
+#define VP8HIP_MOTION_SAD    1   /* bit order = plane order */
+#define VP8HIP_MOTION_SAD0   2
+#define VP8HIP_MOTION_SSE    4
+#define VP8HIP_MOTION_VAR    8
+#define VP8HIP_MOTION_SRCVAR 16
+typedef struct vp8hip_motion {
+    int distance;              /* 1..64 */
+    int sad_per_bit;           /* 0..255; 0: no cost term */
+    unsigned planes;           /* VP8HIP_MOTION_* bits of stats; may be 0 where stats is NULL */
+    const int32_t *cost;       /* host memory, int32 [2][2 * distance + 1], or NULL: no cost term */
+} vp8hip_motion;
+size_t vp8hip_motion_mv_size(const vp8hip_ctx *ctx);
+size_t vp8hip_motion_stats_size(const vp8hip_ctx *ctx, const vp8hip_motion *p);
+int  vp8hip_frames_motion_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int n, const vp8hip_motion *p, const void *centre,
+                                size_t centre_stride, void *mv, size_t mv_stride, void *stats, size_t stats_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

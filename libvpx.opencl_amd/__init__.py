@@ -536,6 +536,21 @@ def split_ssim_map(t, w, h, planes=("y", "u", "v")):
     return out
 
 
+MOTION_PLANES = {"sad": 1, "sad0": 2, "sse": 4, "var": 8, "srcvar": 16}      # VP8HIP_MOTION_*: bit order = plane order
+MOTION_MAX_DISTANCE = 64
+
+
+def motion_sizes(mb_cols, mb_rows, planes=("sad",)):
+    """(bytes of one job's mv tensor, bytes of its stats) of Vp8Hip.frames_motion on a grid of mb_cols x mb_rows macroblocks (what
+    vp8hip_motion_mv_size and vp8hip_motion_stats_size give on a context of that size): int16 [2, mb_rows, mb_cols] -- the centre
+    tensor's size too -- and uint32 [P, mb_rows, mb_cols]; the latter 0 for no plane or an unknown one, both 0 for an empty grid"""
+    mask = _plane_mask(planes, MOTION_PLANES, True)
+    cells = int(mb_cols) * int(mb_rows)
+    if int(mb_cols) < 1 or int(mb_rows) < 1:
+        return 0, 0
+    return 4 * cells, 0 if not mask else 4 * bin(mask).count("1") * cells
+
+
 def ssim_mean(scores):
     """the scores [n, P, 2] of Vp8Hip.frames_ssim (a torch tensor or an array) -> float64 [n, P]: total / 2^32 / count, what
     vp8_ssim2 returns to within 2^-33 + N * 2^-52; NaN where the count is 0 (the reference's 0 / 0)"""
@@ -724,6 +739,10 @@ class SsimParams(ctypes.Structure):         # vp8hip_ssim, include/vp8hip.h
     _fields_ = [("planes", ctypes.c_uint), ("map_dtype", c_int)]
 
 
+class MotionParams(ctypes.Structure):       # vp8hip_motion, include/vp8hip.h
+    _fields_ = [("distance", c_int), ("sad_per_bit", c_int), ("planes", ctypes.c_uint), ("cost", ctypes.POINTER(ctypes.c_int32))]
+
+
 class VisParams(ctypes.Structure):         # vp8hip_vis, include/vp8hip.h
     _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
                 ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
@@ -828,6 +847,12 @@ def load_hip():
         L.vp8hip_ssim_map_size.restype = c_size_t
         L.vp8hip_ssim_share.argtypes = [c_void_p, c_int, ctypes.c_uint]
         L.vp8hip_frames_ssim_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(SsimParams), c_void_p, c_size_t, c_void_p, c_size_t]
+        L.vp8hip_motion_mv_size.argtypes = [c_void_p]
+        L.vp8hip_motion_mv_size.restype = c_size_t
+        L.vp8hip_motion_stats_size.argtypes = [c_void_p, ctypes.POINTER(MotionParams)]
+        L.vp8hip_motion_stats_size.restype = c_size_t
+        L.vp8hip_frames_motion_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(MotionParams), c_void_p, c_size_t, c_void_p, c_size_t,
+                                                 c_void_p, c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1553,6 +1578,57 @@ class Vp8Hip:
         made = self._to_torch(who, outs, lambda sp, ss, mp=None, ms=0: self.L.vp8hip_frames_ssim_async(self.h, arr, n, ctypes.byref(p), sp, ss, mp, ms),
                               "vp8hip_frames_ssim_async")
         return tuple(made) if dt else made[0]
+
+    def frames_motion(self, jobs, distance=16, centre=None, cost=None, sad_per_bit=0, planes=("sad",), out_mv=None, out_stats=None):
+        """Full-search block motion between picture pairs on the context's device (vp8hip_frames_motion_async): per macroblock of fb
+        the whole-pixel vector into ref_fb that the reference's vp8_full_search_sad_c finds within `distance` (1..64) of the centre,
+        bit for bit.  `jobs`: a list of (fb, ref_fb), any order, repeats allowed, fb == ref_fb legal.  Returns (mv, stats): mv a
+        torch.int16 tensor [n, 2, mb_rows, mb_cols], channel 0 = x, 1 = y, in 1/8 pel like frames_side's vectors; stats a
+        torch.int32 tensor [n, P, mb_rows, mb_cols] holding uint32 bits, the planes of `planes` ("sad": the best value; "sad0": the
+        SAD at (0, 0); "sse" and "var" at the best vector; "srcvar": the block's activity; or the mask) in bit order -- None
+        where planes is empty.  `centre`: a torch.int16 tensor [n, 2, mb_rows, mb_cols] of search centres in whole pixels (x, y) on
+        the device, each job dense; None: (0, 0).  `cost`: int32 [2, 2 * distance + 1], row costs then column costs (0..65535), with
+        sad_per_bit (0..255) the reference's mvsad_err_cost around the centre; None or sad_per_bit 0: plain SAD.  Each frame buffer
+        is read in the form it has; nothing is converted or allocated.  `out_mv`, `out_stats`: tensors of those shapes and types,
+        each job dense, stride(0) free.  Stream ordering, the `import torch` first rule and the remark on record_stream: as
+        frames_scaled."""
+        who = "frames_motion"
+        items = [tuple(int(v) for v in j) if isinstance(j, (tuple, list)) else None for j in jobs]
+        if any(j is None or len(j) != 2 for j in items):
+            raise ValueError(f"{who}: jobs are (fb, ref_fb)")
+        mask = _plane_mask(planes, MOTION_PLANES, True)
+        if mask is None:
+            raise ValueError(f"{who}: planes {planes!r} (of {', '.join(MOTION_PLANES)})")
+        if len(items) < 1:
+            raise ValueError(f"{who}: no jobs")
+        if any(fb < 0 or ref < 0 for fb, ref in items):
+            raise ValueError(f"{who}: a negative frame buffer")
+        d, spb = int(distance), int(sad_per_bit)
+        if not 1 <= d <= MOTION_MAX_DISTANCE or not 0 <= spb <= 255:
+            raise ValueError(f"{who}: distance {distance} (1..{MOTION_MAX_DISTANCE}), sad_per_bit {sad_per_bit} (0..255)")
+        if out_stats is not None and not mask:
+            raise ValueError(f"{who}: out_stats without planes")
+        table = None
+        if cost is not None:
+            table = np.ascontiguousarray(cost, dtype=np.int32)
+            if table.shape != (2, 2 * d + 1) or (table < 0).any() or (table > 65535).any():
+                raise ValueError(f"{who}: cost is int32 [2, {2 * d + 1}] of 0..65535")
+        n, rows, cols = len(items), self.g.aligned_h // 16, self.g.aligned_w // 16
+        p = MotionParams(d, spb, mask, None if table is None else table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        cptr, cstride = None, 0
+        if centre is not None:
+            torch, dev = self._torch_device(who)
+            if not self._dense(centre, torch.int16, (n, 2, rows, cols), dev):
+                raise ValueError(f"{who}: centre must be an int16 tensor {[n, 2, rows, cols]}, each job dense, on {dev}")
+            cptr, cstride = c_void_p(centre.data_ptr()), centre.stride(0) * 2
+        outs = [("out_mv", out_mv, "int16", (n, 2, rows, cols))]
+        if mask:
+            outs.append(("out_stats", out_stats, "int32", (n, bin(mask).count("1"), rows, cols)))
+        arr = (HistJob * n)(*items)
+        made = self._to_torch(who, outs, lambda vp, vs, sp=None, ss=0: self.L.vp8hip_frames_motion_async(self.h, arr, n, ctypes.byref(p), cptr, cstride,
+                                                                                                         vp, vs, sp, ss),
+                              "vp8hip_frames_motion_async")
+        return made[0], (made[1] if mask else None)
 
     def ssim_share(self, n, planes=("y", "u", "v")):
         """how many workgroups share each job of a frames_ssim call of n jobs over `planes` (vp8hip_ssim_share): 1 -- a workgroup

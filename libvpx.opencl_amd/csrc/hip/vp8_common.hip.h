@@ -301,6 +301,32 @@ struct SsimFill {                 // what vp8_ssim_fill_kernel writes into every
     long long count[3];
 };
 
+// One launch of vp8hip_frames_motion_async (vp8_motion.hip), as the host's plan (vp8hip_motion.hip) left it.  A workgroup owns one
+// macroblock of one job: it stages the search window -- `rows` rows of `pitch` dwords of the edge-replicated reference picture,
+// its first byte the candidate (cy - d, cx - d) -- and the block, and deals the candidates to its lanes as items of MOTION_ROWS
+// candidate rows by four candidate columns: `groups` x `nq` of them
+#define MOTION_MAX_JOBS 256       // jobs per launch (kernel arguments: 8 bytes each)
+#define MOTION_MAX_D 64
+#define MOTION_ROWS 4             // candidate rows an item takes: a window row in registers serves up to four of them
+#define MOTION_SAD 1              // VP8HIP_MOTION_*
+#define MOTION_SAD0 2
+#define MOTION_SSE 4
+#define MOTION_VAR 8
+#define MOTION_SRCVAR 16
+struct MotionLaunch {
+    int dw, dh;                   // the display size (not read: the search is over the coded area)
+    int mb_cols, mb_rows;
+    int y_off, u_off, v_off, y_stride, uv_stride;    // the raster form: the planes' origins in a frame buffer and their strides
+    int d;                        // the distance, 1..MOTION_MAX_D
+    int nq, groups;               // items across (four candidate columns each) and down (MOTION_ROWS candidate rows each)
+    int pitch, rows;              // the window in LDS: dwords per row (nq + 4 at least) and rows (MOTION_ROWS * groups + 15)
+    int spb;                      // sad_per_bit; 0: no cost term
+    unsigned planes;              // MOTION_* bits of the stats; 0: none
+    int mv, centre;               // 1: vectors are written / centres are read
+    unsigned short cost[2][2 * MOTION_MAX_D + 2];    // [0]: by row, [1]: by column, index = candidate - centre + d
+    HistFrameJob j[MOTION_MAX_JOBS];    // (ref is never -1)
+};
+
 #define WAVE 64
 
 // Macroblock tiles of the one-MB-row-per-lane pipeline (vp8_keyframe_simt.hip has the layout): three 128-byte lines per macroblock.

@@ -1,5 +1,6 @@
 // The display-size planes of a frame buffer in whichever form it has, for the kernels that read pictures and make no tensor of them
-// (vp8_hist.hip, vp8_ssim.hip): a piece of sixteen columns of a row (hist_read16) and one aligned dword of four (frame_read4), from
+// (vp8_hist.hip, vp8_ssim.hip, vp8_motion.hip): a piece of sixteen columns of a row (hist_read16), one aligned dword of four
+// (frame_read4) and one of the coded luma area extended by edge replication (frame_edge4), from
 // the raster form directly, from the tiles through ScaleSrc<SCALE_FROM_TILES> (vp8_scale_src.hip.h: the one place that knows the
 // tiles); a frame buffer never written reads as zeros and no address is formed.  The launch L says where the planes lie: dw, dh,
 // mb_cols, mb_rows, y_off, u_off, v_off, y_stride, uv_stride (HistFrameLaunch, SsimLaunch).
@@ -46,4 +47,25 @@ __device__ __forceinline__ unsigned frame_read4(const HistFrame &F, const Launch
         return S.template atN<4>(x, y);
     }
     return 0u;
+}
+
+// columns x .. x + 3 of row y of the luma plane's CODED area (16 * mb_cols x 16 * mb_rows) extended by edge replication, for any row
+// y and any multiple of 4 x, low byte first: E(y, x) = S(clamp(y), clamp(x)), by coordinate clamps -- the raster form's borders are
+// never read, both forms give the same bytes.  The coded width is a multiple of 16, so an aligned dword lies wholly inside the
+// area or wholly outside it (then: the row's first or last byte, four times).  FORM is F's (SCALE_FROM_RASTER or _TILES: the
+// caller branches once, not per dword); one load whatever x is, and selects: nothing here diverges
+template <int FORM, class Launch>
+__device__ __forceinline__ unsigned frame_edge4(const HistFrame &F, const Launch &L, int x, int y)
+{
+    const int aw = 16 * L.mb_cols, ah = 16 * L.mb_rows;
+    const int xe = min(max(x, 0), aw - 4);
+    y = min(max(y, 0), ah - 1);
+    unsigned v;
+    if constexpr (FORM == SCALE_FROM_RASTER) {
+        v = *(g_cu32p)((g_cu8p)F.raster + L.y_off + (long)y * L.y_stride + xe);
+    } else {
+        const ScaleSrc<SCALE_FROM_TILES> S{(g_cu8p)F.tiles, (L.mb_cols + 1) * VP8_TILE_BYTES, aw - 1, ah - 1, 4, 12, 0, 192};
+        v = S.template atN<4>(xe, y);
+    }
+    return x < 0 ? (v & 0xffu) * 0x01010101u : x >= aw ? (v >> 24) * 0x01010101u : v;
 }

@@ -15,6 +15,7 @@
 //   vp8hip_hist.hip     vp8hip_frames_hist_async, vp8hip_slots_hist_async, vp8hip_trace_wear_hist_async, vp8hip_trace_cover_hist_async:
 //                       byte histograms of pictures, slots and pool entries (vp8_hist.hip)
 //   vp8hip_ssim.hip     vp8hip_frames_ssim_async: the structural similarity of picture pairs (vp8_ssim.hip)
+//   vp8hip_motion.hip   vp8hip_frames_motion_async: full-search block motion between picture pairs (vp8_motion.hip)
 //   vp8hip_handover.hip the checks those calls share
 // and vp8hip_res.hip.h: the owning types of the context's buffers, events and streams.
 #pragma once

@@ -131,13 +131,42 @@ KERNEL(cvt_f32_i32, I2("v_cvt_f32_i32"), D2("v_cvt_f32_i32"))
 KERNEL(mov_b32, I2("v_mov_b32"), D2("v_mov_b32"))
 KERNEL(mov_dpp_wave_shr, IDPP, DDPP)
 
+// v_qsad_pk_u16_u8 (the motion search's inner loop, vp8_motion.hip): 64-bit destination, window and accumulator.  The destination
+// may not overlap a source (the compiler's early-clobber rule), so an accumulator ping-pongs between two register pairs: four
+// independent chains over eight pairs, or one chain over two.  128 instructions per iteration, as KERNEL's.
+#define IQ                                                                                                   \
+    "v_qsad_pk_u16_u8 %1, %8, %9, %0\n v_qsad_pk_u16_u8 %3, %8, %9, %2\n v_qsad_pk_u16_u8 %5, %8, %9, %4\n v_qsad_pk_u16_u8 %7, %8, %9, %6\n" \
+    "v_qsad_pk_u16_u8 %0, %8, %9, %1\n v_qsad_pk_u16_u8 %2, %8, %9, %3\n v_qsad_pk_u16_u8 %4, %8, %9, %5\n v_qsad_pk_u16_u8 %6, %8, %9, %7\n"
+#define DQ "v_qsad_pk_u16_u8 %1, %2, %3, %0\n v_qsad_pk_u16_u8 %0, %2, %3, %1\n"
+#define X4(S) S S S S
+__global__ void __launch_bounds__(256) k_qsad_pk_u16_u8(unsigned long long *out, int iters, int dep, unsigned seed)
+{
+    unsigned long long q[8];
+    for (int i = 0; i < 8; i++) q[i] = (unsigned long long)(seed * (threadIdx.x + 1)) + i * 0x0101010101ull;
+    const unsigned long long w = (unsigned long long)seed << 32 | (seed * 2654435761u);
+    const unsigned a = seed | 0x00030003u;
+    unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    if (!dep) {
+        for (int it = 0; it < iters; it++)
+            asm volatile(X4(X4(IQ)) : "+v"(q[0]), "+v"(q[1]), "+v"(q[2]), "+v"(q[3]), "+v"(q[4]), "+v"(q[5]), "+v"(q[6]), "+v"(q[7]) : "v"(w), "v"(a));
+    } else {
+        for (int it = 0; it < iters; it++) asm volatile(X4(X4(X4(DQ))) : "+v"(q[0]), "+v"(q[1]) : "v"(w), "v"(a));
+    }
+    unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    unsigned long long s = 0;
+    for (int i = 0; i < 8; i++) s ^= q[i];
+    if (threadIdx.x % 64 == 0) out[(blockIdx.x * blockDim.x + threadIdx.x) / 64] = (t1 - t0) + (s == 0x12345 ? 1 : 0);
+}
+
 typedef void (*kern_t)(unsigned long long *, int, int, unsigned);
 struct Entry { const char *name; kern_t k; };
 #define E(N) { #N, k_##N }
 static Entry entries[] = { E(add_u32), E(xor_b32), E(pk_add_u16), E(pk_sub_i16_clamp), E(pk_max_i16), E(pk_mul_lo_u16), E(pk_ashrrev_i16),
     E(pk_mad_i16), E(perm_b32), E(alignbyte_b32), E(lerp_u8), E(sad_u8), E(mul_i32_i24), E(mad_i32_i24), E(mul_hi_i32_i24),
     E(mul_lo_u32), E(mul_hi_i32), E(bfe_i32), E(and_or_b32), E(add3_u32), E(med3_i32), E(dot2_i32_i16), E(dot4_i32_i8),
-    E(pk_fma_f32_na), E(and_b32), E(lshlrev_b32), E(ashrrev_i32), E(sub_u32), E(max_i32), E(min_u32), E(mul_u32_u24), E(add_u16), E(mul_f32), E(fma_f32), E(fmac_f32), E(pk_add_f16), E(bfi_b32), E(lshl_add_u32), E(or3_b32), E(max3_i32), E(cvt_f32_i32), E(mov_b32), E(mov_dpp_wave_shr) };
+    E(pk_fma_f32_na), E(and_b32), E(lshlrev_b32), E(ashrrev_i32), E(sub_u32), E(max_i32), E(min_u32), E(mul_u32_u24), E(add_u16), E(mul_f32), E(fma_f32), E(fmac_f32), E(pk_add_f16), E(bfi_b32), E(lshl_add_u32), E(or3_b32), E(max3_i32), E(cvt_f32_i32), E(mov_b32), E(mov_dpp_wave_shr), E(qsad_pk_u16_u8) };
 
 int main()
 {
