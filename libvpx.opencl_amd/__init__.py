@@ -192,6 +192,7 @@ class Parser:
         self.refs = Refs()
         self.L.vp8_refs_init(ctypes.byref(self.refs))
         self.dims = None
+        self._undo = None
 
     def close(self):
         if self.p:
@@ -218,6 +219,8 @@ class Parser:
     def begin(self, data):
         """-> (hdr, dims_changed).  Acquires refs.new_idx like the reference's get_free_fb."""
         hdr = FrameHdr()
+        self._undo = None
+        before = Refs.from_buffer_copy(self.refs), self.dims
         if self.L.vp8_refs_get_free(ctypes.byref(self.refs)) < 0:
             raise RuntimeError("no free frame buffer")
         self._frame_data = data          # the parser borrows the compressed frame until decode_mbs has run (vp8_parser.h)
@@ -229,7 +232,17 @@ class Parser:
         if changed:
             self.dims = (hdr.width, hdr.height)
             self.L.vp8_refs_on_alloc(ctypes.byref(self.refs))
+        self._undo = before
         return hdr, changed
+
+    def abandon(self):
+        """The frame begin() opened is not going to be decoded now: the bookkeeping goes back to what it was before begin() -- the
+        buffer it took is free again and, where the frame brought a new size, neither the size nor the reallocation has
+        happened -- so that begin() on the same frame does all of it again (and reports the change of size again)."""
+        if self._undo is not None:
+            saved, self.dims = self._undo
+            ctypes.memmove(ctypes.byref(self.refs), ctypes.byref(saved), ctypes.sizeof(Refs))
+            self._undo = None
 
     def export_entropy(self):
         """After begin() on a key frame: the frame's vp8hip_entropy_frame (offsets relative to the frame's first byte); the
@@ -937,6 +950,7 @@ class Vp8Hip:
         """Feeder writes straight into the pinned staging of `slot`; returns hdr (not yet uploaded)."""
         hdr, changed = parser.begin(data)
         if (hdr.width, hdr.height) != (self.width, self.height):
+            parser.abandon()             # (so that the same call on the same parser works once the context is configured)
             raise RuntimeError("dimension change: reconfigure the context first")
         ph, pm, pc, pv = self.ir_map(slot)
         parser.decode_mbs(pm, pc, pv)
@@ -955,6 +969,7 @@ class Vp8Hip:
         (one copy; nothing on the device touches the slot before the pixel kernels read it); returns (hdr, bytes uploaded)."""
         hdr, changed = parser.begin(data)
         if (hdr.width, hdr.height) != (self.width, self.height):
+            parser.abandon()             # (so that the same call on the same parser works once the context is configured)
             raise RuntimeError("dimension change: reconfigure the context first")
         ph, pm, pb, pv, cap = self.ir_map_compact(slot)
         nb, _ = parser.decode_mbs_compact(pm, pb, cap, pv)

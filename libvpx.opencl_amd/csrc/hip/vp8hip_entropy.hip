@@ -66,6 +66,10 @@ static int entropy_stage(vp8hip_ctx *c, int count, const vp8hip_entropy_frame *f
         if (h.mb_cols != c->dg.mb_cols || h.mb_rows != c->dg.mb_rows)
             return fail(c, -2, "vp8hip_entropy_decode: frame %d is %dx%d MBs, context configured for %dx%d", i, h.mb_cols, h.mb_rows,
                         c->dg.mb_cols, c->dg.mb_rows);
+        // (the same macroblocks and another display size: the context's digests, downloads and tensors crop by its own size)
+        if (h.width != c->width || h.height != c->height)
+            return fail(c, -2, "vp8hip_entropy_decode: frame %d is %dx%d, context configured for %dx%d", i, h.width, h.height,
+                        c->width, c->height);
         bool ok = (f.num_tok == 1 || f.num_tok == 2 || f.num_tok == 4 || f.num_tok == 8) && f.data_off <= data_bytes &&
                   f.first_pos <= f.first_end && f.first_end <= data_bytes - f.data_off && data_bytes - f.data_off >= f.first_end && f.first_range >= 128 && f.first_range <= 255 &&
                   f.first_bits >= -8 && f.first_bits <= 24;

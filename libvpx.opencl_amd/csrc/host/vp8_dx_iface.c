@@ -253,8 +253,7 @@ static vpx_codec_err_t vp8_decode(vpx_codec_alg_priv_t *p, const uint8_t *data, 
         }
         p->width = hdr.width;
         p->height = hdr.height;
-        p->si.w = hdr.width;
-        p->si.h = hdr.height;
+        /* (p->si stays what the first key frame said, as in the reference: vp8_dx_iface.c:364 peeks once) */
         vp8_refs_on_alloc(&p->refs);
         memset(p->fb_corrupted, 0, sizeof p->fb_corrupted);
     }

@@ -626,6 +626,7 @@ static void read_kf_modes(vp8_parser *p, mbinfo *m)            /* decodemv.c:50-
     const mbinfo *above = m - p->mi_stride, *left = m - 1;
     m->ref_frame = VP8IR_INTRA_FRAME;
     m->mv = 0;
+    m->need_clamp = 0;           /* (a key frame of the size before: the macroblock may have been an inter one with a flag) */
     if (!vp8br_get(br, kf_ymode_prob[0]))
         m->y_mode = VP8IR_B_PRED;
     else if (!vp8br_get(br, kf_ymode_prob[1]))

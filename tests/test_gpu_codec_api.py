@@ -3,58 +3,15 @@ tools do not reach: VP8_COPY_REFERENCE / VP8_SET_REFERENCE (vp8/vp8_dx_iface.c:6
 VP8D_GET_LAST_REF_UPDATES / _USED / VP8D_GET_FRAME_CORRUPTED (:653-720) and VPX_CODEC_USE_INPUT_FRAGMENTS
 (:416-417; vp8/decoder/onyxd_if.c:336-366, decodframe.c:501-592)."""
 import ctypes
-import hashlib
 import os
 
 import pytest
 
+from stream_testlib import (VP8_ALTR_FRAME, VP8_COPY_REFERENCE, VP8_GOLD_FRAME, VP8_LAST_FRAME, VP8_SET_REFERENCE, VPX_DECODER_ABI_VERSION,
+                            VPX_IMG_FMT_I420, VpxImage, VpxRefFrame, codec_lib as _lib, image_md5 as _md5, image_plane as _plane)  # noqa: F401 (other test files take them from here)
 from vp8_testlib import ROOT, golden_md5, ivf_path, load_package
 
 pytestmark = pytest.mark.gpu
-
-VPX_DECODER_ABI_VERSION = 2 + 2 + 1
-VPX_IMG_FMT_I420 = 0x100 | 2
-VP8_SET_REFERENCE, VP8_COPY_REFERENCE = 1, 2
-VP8_LAST_FRAME, VP8_GOLD_FRAME, VP8_ALTR_FRAME = 1, 2, 4
-
-
-class VpxImage(ctypes.Structure):        # include/vpx/vpx_image.h (vpx/vpx_image.h:103-147 in the reference)
-    _fields_ = [("fmt", ctypes.c_int), ("w", ctypes.c_uint), ("h", ctypes.c_uint), ("d_w", ctypes.c_uint),
-                ("d_h", ctypes.c_uint), ("x_chroma_shift", ctypes.c_uint), ("y_chroma_shift", ctypes.c_uint),
-                ("planes", ctypes.POINTER(ctypes.c_ubyte) * 4), ("stride", ctypes.c_int * 4), ("bps", ctypes.c_int),
-                ("user_priv", ctypes.c_void_p), ("img_data", ctypes.c_void_p), ("img_data_owner", ctypes.c_int),
-                ("self_allocd", ctypes.c_int)]
-
-
-class VpxRefFrame(ctypes.Structure):     # include/vpx/vp8.h (vpx/vp8.h:94-98)
-    _fields_ = [("frame_type", ctypes.c_int), ("img", VpxImage)]
-
-
-def _lib():
-    L = ctypes.CDLL(os.path.join(ROOT, "libvpx.opencl_amd", "lib", "libvpx_hip.so"))
-    L.vpx_codec_vp8_dx.restype = ctypes.c_void_p
-    L.vpx_codec_dec_init_ver.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_int]
-    L.vpx_codec_decode.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_long]
-    L.vpx_codec_get_frame.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
-    L.vpx_codec_get_frame.restype = ctypes.POINTER(VpxImage)
-    L.vpx_codec_control_.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    L.vpx_codec_destroy.argtypes = [ctypes.c_void_p]
-    L.vpx_img_alloc.argtypes = [ctypes.POINTER(VpxImage), ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint]
-    L.vpx_img_alloc.restype = ctypes.POINTER(VpxImage)
-    L.vpx_img_free.argtypes = [ctypes.POINTER(VpxImage)]
-    return L
-
-
-def _plane(img, k, w, h):
-    st = img.stride[k]
-    return b"".join(ctypes.string_at(ctypes.addressof(img.planes[k].contents) + r * st, w) for r in range(h))
-
-
-def _md5(img):
-    w, h = img.d_w, img.d_h
-    m = hashlib.md5()
-    m.update(_plane(img, 0, w, h)); m.update(_plane(img, 1, (w + 1) // 2, (h + 1) // 2)); m.update(_plane(img, 2, (w + 1) // 2, (h + 1) // 2))
-    return m.hexdigest()
 
 
 def test_copy_and_set_reference():

@@ -14,8 +14,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from stream_testlib import inter_sequence
 from vp8_testlib import GOLDEN, ROOT, load_package, oracle_decode, synth_ir
-from vp8_writer import write_inter_frame, write_ivf, write_key_frame
+from vp8_writer import write_ivf, write_key_frame
 
 REF_MD5 = os.path.join(ROOT, "oracle", "_ref", "ref_md5")
 LISTINGS = os.path.join(GOLDEN, "writer_ref_md5.json")
@@ -96,49 +97,6 @@ def test_reference_decodes_written_streams_like_the_oracle(pkg, case, tmp_path, 
     oracle_decode(hdr, mbs, coef, mvs, buf, (None, None, None))
     mine = pkg.frame_md5(buf, g, hdr.width, hdr.height)
     assert ref == [mine, mine]
-
-
-# ---- inter frames: every inter mode, all three references with sign biases, split vectors, and the segment map's three lives
-# (coded, kept with new data, kept untouched) -- content the reference ENCODER never produces (it codes no map on inter frames)
-def inter_sequence(w, h, seed, plan, lp=0, dense=0.25, big=False):
-    """A key frame and one inter frame per entry of plan ("keep": segmentation on, nothing coded; "data": new segment data, map
-    kept; "map": new map, data kept; "both"; "off": segmentation off).  Returns the frames and, per frame, the IR the stream was
-    written from as a decoder is to read it back: (hdr, mbs, coef, mvs, segment map known)."""
-    rng = np.random.default_rng(seed)
-    hdr, mbs, coef, mvs = synth_ir(w, h, seed, inter=False, dense=dense, big=big, segmented=True)
-    hdr.num_token_partitions = 1 << lp
-    frames, expect = [write_key_frame(hdr, mbs, coef, log2_parts=lp)], [(hdr, mbs, coef, mvs, True)]
-    segmap, absd = mbs[:, 4].copy(), hdr.mb_segment_abs_delta
-    segq, seglf = list(hdr.segment_quant), list(hdr.segment_lf)
-    known = True
-    for i, step in enumerate(plan):
-        hdr, mbs, coef, mvs = synth_ir(w, h, seed * 100 + i + 1, inter=True, dense=dense, big=big, segmented=step != "off")
-        hdr.num_token_partitions = 1 << lp
-        hdr.refresh_last = int(rng.integers(0, 4) > 0)
-        hdr.refresh_golden, hdr.refresh_alt = int(rng.integers(0, 3) == 0), int(rng.integers(0, 3) == 0)
-        hdr.copy_buffer_to_gf = 0 if hdr.refresh_golden else int(rng.integers(0, 3))
-        hdr.copy_buffer_to_arf = 0 if hdr.refresh_alt else int(rng.integers(0, 3))
-        hdr.sign_bias_golden, hdr.sign_bias_alt = int(rng.integers(0, 2)), int(rng.integers(0, 2))
-        hdr.show_frame = int(rng.integers(0, 5) > 0)
-        um = step in ("map", "both")
-        ud = step in ("data", "both")
-        if step != "off":
-            if not um:
-                mbs[:, 4] = segmap
-            if not ud:
-                hdr.mb_segment_abs_delta = absd
-                for k in range(4):
-                    hdr.segment_quant[k], hdr.segment_lf[k] = segq[k], seglf[k]
-        data, mbs2, mvs2 = write_inter_frame(hdr, mbs, coef, mvs, log2_parts=lp, update_map=um, update_data=ud)
-        if um:
-            segmap, known = mbs[:, 4].copy(), True
-        if ud:
-            absd, segq, seglf = hdr.mb_segment_abs_delta, list(hdr.segment_quant), list(hdr.segment_lf)
-        if step == "off":
-            known = False                               # (what a later frame that keeps "the" map sees is the decoder's business)
-        frames.append(data)
-        expect.append((hdr, mbs2, coef, mvs2, known))
-    return frames, expect
 
 
 INTER_CASES = [  # width, height, seed, plan, log2 partitions, big coefficients

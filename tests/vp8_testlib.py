@@ -72,26 +72,43 @@ def oracle_decode(hdr, mbs, coef, mvs, dst, refs, stages=7):
                                dst.ctypes.data, rp, stages)
 
 
+def oracle_frames(frames, stages=7, lose=None):
+    """Feeder + oracle over a list of compressed frames of any sizes: yields, per frame, (hdr, changed, mbs, coef, mvs, the buffer
+    the frame was decoded into, the buffer shown for it or None).  A key frame of a new size gets four fresh zeroed buffers, as
+    vp8_alloc_frame_buffers gives the reference (alloccommon.c:59-152).  The buffers are the decoder's own: copy what is to last.
+    lose: the feeder conceals errors (vp8_parser_set_error_concealment), and the packets of these 1-based numbers never arrive."""
+    P = load_package()
+    parser = P.Parser()
+    if lose is not None:
+        parser.set_error_concealment(True)
+    bufs = None
+    try:
+        for k, data in enumerate(frames, 1):
+            hdr, changed, mbs, coef, mvs = P.parse_to_numpy(parser, b"" if lose and k in lose else data)
+            if lose is not None:
+                parser.final_hdr(hdr)
+            if changed:
+                g = P.geom(hdr.width, hdr.height)
+                bufs = [np.zeros(g.frame_size, np.uint8) for _ in range(4)]
+            r = parser.refs
+            oracle_decode(hdr, mbs, coef, mvs, bufs[r.new_idx], (bufs[r.lst_idx], bufs[r.gld_idx], bufs[r.alt_idx]), stages)
+            new = r.new_idx
+            parser.swap(hdr)
+            yield hdr, changed, mbs, coef, mvs, bufs[new], bufs[parser.refs.show_idx] if hdr.show_frame else None
+    finally:
+        parser.close()
+
+
 def oracle_decode_ivf(name, stages=7, keep_frames=False):
     """Feeder + oracle over a whole fixture: per-shown-frame MD5s (and optionally every frame buffer)."""
     P = load_package()
     w, h, frames = P.read_ivf(ivf_path(name))
-    parser = P.Parser()
-    out, kept, bufs, g = [], [], None, None
-    for data in frames:
-        hdr, changed, mbs, coef, mvs = P.parse_to_numpy(parser, data)
-        if changed:
-            g = P.geom(hdr.width, hdr.height)
-            bufs = [np.zeros(g.frame_size, np.uint8) for _ in range(4)]
-        r = parser.refs
-        oracle_decode(hdr, mbs, coef, mvs, bufs[r.new_idx], (bufs[r.lst_idx], bufs[r.gld_idx], bufs[r.alt_idx]), stages)
-        new = r.new_idx
-        parser.swap(hdr)
+    out, kept = [], []
+    for hdr, changed, mbs, coef, mvs, new, shown in oracle_frames(frames, stages):
         if keep_frames:
-            kept.append((hdr, mbs, coef, mvs, bufs[new].copy()))
-        if hdr.show_frame:
-            out.append(P.frame_md5(bufs[parser.refs.show_idx], g, hdr.width, hdr.height))
-    parser.close()
+            kept.append((hdr, mbs, coef, mvs, new.copy()))
+        if shown is not None:
+            out.append(P.frame_md5(shown, P.geom(hdr.width, hdr.height), hdr.width, hdr.height))
     return (out, kept) if keep_frames else out
 
 
@@ -336,12 +353,23 @@ def _pp_planes(g):
 def oracle_postproc_ivf(name, flags, level, noise):
     """Feeder + oracle + oracle post-processing over a fixture: per-shown-frame MD5s of the post-processed output."""
     P = load_package()
-    _, kept = oracle_decode_ivf(name, keep_frames=True)
+    return [md5 for md5, _, _ in oracle_postproc_frames(P.read_ivf(ivf_path(name))[2], flags, level, noise)[0]]
+
+
+def oracle_postproc_frames(frames, flags, level, noise):
+    """Feeder + oracle + oracle post-processing over a list of compressed frames of any sizes -> ([(MD5 of the post-processed
+    output, 1-based packet number, (width, height))] per shown frame, the OraclePostproc with its counters).  The post-processing
+    state -- noise table, last quantisers, rand() -- outlives a change of size as postproc_state outlives vp8_alloc_frame_buffers;
+    the picture shown before does not: the new size's post_proc_buffer starts as zeros here (in the reference it is whatever the
+    allocator hands out, so a frame MFQE blends right after a change of size has no defined value there)."""
+    P = load_package()
     ctypes.CDLL(None).srand(1)
     pp = OraclePostproc(flags, level, noise)
     out = []
-    for hdr, mbs, coef, mvs, frame in kept:
-        if hdr.show_frame:
+    for k, (hdr, changed, mbs, coef, mvs, new, shown) in enumerate(oracle_frames(frames), 1):
+        if changed:
+            pp.post = None
+        if shown is not None:
             g = P.geom(hdr.width, hdr.height)
-            out.append(P.frame_md5(pp.frame(frame, g, hdr.filter_level, hdr, mbs, mvs), g, hdr.width, hdr.height))
-    return out
+            out.append((P.frame_md5(pp.frame(shown, g, hdr.filter_level, hdr, mbs, mvs), g, hdr.width, hdr.height), k, (hdr.width, hdr.height)))
+    return out, pp
