@@ -1496,6 +1496,27 @@ class Vp8Hip:
         dense, stride(0) free -- filled by fn(pointer, stride in bytes) between the stream waits"""
         return self._to_torch(who, [("out", out, "int32", (n, nplanes, 256))], fn, call)[0]
 
+    @staticmethod
+    def _pair_jobs(who, jobs, planes, table, none_ok=False, ref_optional=False):
+        """-> (the HistJob array, how many jobs, the plane mask) of a call over picture pairs (frames_hist, frames_ssim, frames_motion);
+        ValueError, in this order, for a job that is no (fb, ref_fb) -- ref_optional: or a bare frame buffer, and ref_fb may be
+        None --, for an unknown plane or -- unless none_ok -- no plane, for no job and for a negative frame buffer"""
+        items = []
+        for j in jobs:
+            if ref_optional:
+                j = (j, None) if isinstance(j, (int, np.integer)) else tuple(j)
+            if not isinstance(j, (tuple, list)) or len(j) != 2:
+                raise ValueError(f"{who}: jobs are {'frame buffers or ' if ref_optional else ''}(fb, ref_fb)")
+            items.append((int(j[0]), -1 if ref_optional and j[1] is None else int(j[1])))
+        mask = _plane_mask(planes, table, none_ok)
+        if mask is None:
+            raise ValueError(f"{who}: planes {planes!r} ({'of' if none_ok else 'at least one of'} {', '.join(table)})")
+        if not items:
+            raise ValueError(f"{who}: no jobs")
+        if any(fb < 0 or ref < (-1 if ref_optional else 0) for fb, ref in items):
+            raise ValueError(f"{who}: a negative frame buffer{' (ref_fb: None or -1 for none)' if ref_optional else ''}")
+        return (HistJob * len(items))(*items), len(items), mask
+
     def frames_hist(self, jobs, planes=("y", "u", "v"), out=None):
         """Byte histograms of pictures on the context's device (vp8hip_frames_hist_async): a torch.int32 tensor [n, P, 256].  `jobs`:
         a list of frame buffers, or of (fb, ref_fb) with ref_fb None or -1 for none (any order, repeats allowed).  Without a
@@ -1505,17 +1526,8 @@ class Vp8Hip:
         allocated.  Counts are below 2^28.  Stream ordering, the `import torch` first rule and the remark on record_stream: as
         frames_scaled."""
         who = "frames_hist"
-        items = []
-        for j in jobs:
-            j = (j, None) if isinstance(j, (int, np.integer)) else tuple(j)
-            if len(j) != 2:
-                raise ValueError(f"{who}: jobs are frame buffers or (fb, ref_fb)")
-            items.append((int(j[0]), -1 if j[1] is None else int(j[1])))
-        n, mask, nplanes = self._hist_args(who, items, planes, HIST_PLANES)
-        if any(fb < 0 or ref < -1 for fb, ref in items):
-            raise ValueError(f"{who}: a negative frame buffer (ref_fb: None or -1 for none)")
-        arr = (HistJob * n)(*items)
-        return self._hist(who, "vp8hip_frames_hist_async", n, nplanes, out,
+        arr, n, mask = self._pair_jobs(who, jobs, planes, HIST_PLANES, ref_optional=True)
+        return self._hist(who, "vp8hip_frames_hist_async", n, bin(mask).count("1"), out,
                           lambda ptr, stride: self.L.vp8hip_frames_hist_async(self.h, arr, n, mask, ptr, stride))
 
     def slots_hist(self, slots, planes, out=None):
@@ -1573,12 +1585,8 @@ class Vp8Hip:
         `out_scores`, `out_map`: tensors of those shapes and types, each job dense, stride(0) free.  Stream ordering, the `import
         torch` first rule and the remark on record_stream: as frames_scaled."""
         who = "frames_ssim"
-        items = [tuple(int(v) for v in j) if isinstance(j, (tuple, list)) else None for j in jobs]
-        if any(j is None or len(j) != 2 for j in items):
-            raise ValueError(f"{who}: jobs are (fb, ref_fb)")
-        n, mask, nplanes = self._hist_args(who, items, planes, HIST_PLANES)
-        if any(fb < 0 or ref < 0 for fb, ref in items):
-            raise ValueError(f"{who}: a negative frame buffer")
+        arr, n, mask = self._pair_jobs(who, jobs, planes, HIST_PLANES)
+        nplanes = bin(mask).count("1")
         dt = 0 if map_dtype is None else _ssim_dtype(map_dtype)
         if dt is None or (out_map is not None and not dt):
             raise ValueError(f"{who}: map_dtype {map_dtype!r} (float16 or float32; out_map needs one)")
@@ -1589,7 +1597,6 @@ class Vp8Hip:
             if not size:
                 raise ValueError(f"{who}: planes {planes!r} of {self.width}x{self.height} have no windows: no map")
             outs.append(("out_map", out_map, _SSIM_DTYPES[dt], (n, size // (0, 2, 4)[dt])))
-        arr = (HistJob * n)(*items)
         made = self._to_torch(who, outs, lambda sp, ss, mp=None, ms=0: self.L.vp8hip_frames_ssim_async(self.h, arr, n, ctypes.byref(p), sp, ss, mp, ms),
                               "vp8hip_frames_ssim_async")
         return tuple(made) if dt else made[0]
@@ -1608,16 +1615,7 @@ class Vp8Hip:
         each job dense, stride(0) free.  Stream ordering, the `import torch` first rule and the remark on record_stream: as
         frames_scaled."""
         who = "frames_motion"
-        items = [tuple(int(v) for v in j) if isinstance(j, (tuple, list)) else None for j in jobs]
-        if any(j is None or len(j) != 2 for j in items):
-            raise ValueError(f"{who}: jobs are (fb, ref_fb)")
-        mask = _plane_mask(planes, MOTION_PLANES, True)
-        if mask is None:
-            raise ValueError(f"{who}: planes {planes!r} (of {', '.join(MOTION_PLANES)})")
-        if len(items) < 1:
-            raise ValueError(f"{who}: no jobs")
-        if any(fb < 0 or ref < 0 for fb, ref in items):
-            raise ValueError(f"{who}: a negative frame buffer")
+        arr, n, mask = self._pair_jobs(who, jobs, planes, MOTION_PLANES, none_ok=True)
         d, spb = int(distance), int(sad_per_bit)
         if not 1 <= d <= MOTION_MAX_DISTANCE or not 0 <= spb <= 255:
             raise ValueError(f"{who}: distance {distance} (1..{MOTION_MAX_DISTANCE}), sad_per_bit {sad_per_bit} (0..255)")
@@ -1628,7 +1626,7 @@ class Vp8Hip:
             table = np.ascontiguousarray(cost, dtype=np.int32)
             if table.shape != (2, 2 * d + 1) or (table < 0).any() or (table > 65535).any():
                 raise ValueError(f"{who}: cost is int32 [2, {2 * d + 1}] of 0..65535")
-        n, rows, cols = len(items), self.g.aligned_h // 16, self.g.aligned_w // 16
+        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
         p = MotionParams(d, spb, mask, None if table is None else table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
         cptr, cstride = None, 0
         if centre is not None:
@@ -1639,7 +1637,6 @@ class Vp8Hip:
         outs = [("out_mv", out_mv, "int16", (n, 2, rows, cols))]
         if mask:
             outs.append(("out_stats", out_stats, "int32", (n, bin(mask).count("1"), rows, cols)))
-        arr = (HistJob * n)(*items)
         made = self._to_torch(who, outs, lambda vp, vs, sp=None, ss=0: self.L.vp8hip_frames_motion_async(self.h, arr, n, ctypes.byref(p), cptr, cstride,
                                                                                                          vp, vs, sp, ss),
                               "vp8hip_frames_motion_async")

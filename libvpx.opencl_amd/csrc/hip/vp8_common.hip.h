@@ -235,6 +235,14 @@ struct InvertLaunch {
     InvertJob j[INVERT_MAX_JOBS];
 };
 
+// Where the planes of the context's frame buffers lie, for the kernels that read pictures and make no tensor of them
+// (vp8_frame_read.hip.h): what a launch of the byte histograms, of the structural similarity and of the motion search begins with
+struct FramePlanes {
+    int dw, dh;                   // the display size
+    int mb_cols, mb_rows;
+    int y_off, u_off, v_off, y_stride, uv_stride;    // the raster form: the planes' origins in a frame buffer and their strides
+};
+
 // One launch of the byte histograms (vp8_hist.hip), as the host's plans (vp8hip_hist.hip) left it: vp8hip_frames_hist_async,
 // vp8hip_slots_hist_async, vp8hip_trace_wear_hist_async and vp8hip_trace_cover_hist_async.  gridDim.x workgroups share a job; where
 // that is more than one, vp8_hist_fill_kernel has run first and the workgroups add their counts with global atomics
@@ -246,10 +254,7 @@ struct HistFrameJob {
     int fb;                       // the frame: frame buffer << 2 | form (SCALE_FROM_*), as of the call
     int ref;                      // the frame it is compared with, the same way; -1: none
 };
-struct HistFrameLaunch {
-    int dw, dh;                   // the display size
-    int mb_cols, mb_rows;
-    int y_off, u_off, v_off, y_stride, uv_stride;    // the raster form: the planes' origins in a frame buffer and their strides
+struct HistFrameLaunch : FramePlanes {
     int S;                        // workgroups that share a job's rows (gridDim.x)
     unsigned planes;              // VP8HIP_HIST_Y | _U | _V
     HistFrameJob j[HIST_MAX_JOBS];
@@ -284,10 +289,7 @@ struct SsimPlane {                // a plane asked for, in bit order
     int first;                    // the job's pieces before this plane's
     int map_off;                  // elements of a job's map before this plane's
 };
-struct SsimLaunch {
-    int dw, dh;                   // the display size
-    int mb_cols, mb_rows;
-    int y_off, u_off, v_off, y_stride, uv_stride;    // the raster form: the planes' origins in a frame buffer and their strides
+struct SsimLaunch : FramePlanes {
     int S;                        // workgroups that share a job's pieces (gridDim.x)
     int np;                       // planes asked for
     int pieces;                   // of a job, all planes
@@ -313,10 +315,7 @@ struct SsimFill {                 // what vp8_ssim_fill_kernel writes into every
 #define MOTION_SSE 4
 #define MOTION_VAR 8
 #define MOTION_SRCVAR 16
-struct MotionLaunch {
-    int dw, dh;                   // the display size (not read: the search is over the coded area)
-    int mb_cols, mb_rows;
-    int y_off, u_off, v_off, y_stride, uv_stride;    // the raster form: the planes' origins in a frame buffer and their strides
+struct MotionLaunch : FramePlanes {  // (dw, dh are not read: the search is over the coded area)
     int d;                        // the distance, 1..MOTION_MAX_D
     int nq, groups;               // items across (four candidate columns each) and down (MOTION_ROWS candidate rows each)
     int pitch, rows;              // the window in LDS: dwords per row (nq + 4 at least) and rows (MOTION_ROWS * groups + 15)
@@ -326,6 +325,13 @@ struct MotionLaunch {
     unsigned short cost[2][2 * MOTION_MAX_D + 2];    // [0]: by row, [1]: by column, index = candidate - centre + d
     HistFrameJob j[MOTION_MAX_JOBS];    // (ref is never -1)
 };
+// the three launches' layout in the kernels' arguments: the base takes 36 bytes and the first member lies right behind it (offsetof
+// past a base of plain ints is what the warning calls conditionally supported: it is supported here)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(sizeof(FramePlanes) == 36 && sizeof(HistFrameLaunch) == 2092 && sizeof(SsimLaunch) == 2176 && sizeof(MotionLaunch) == 2640, "");
+static_assert(offsetof(HistFrameLaunch, S) == 36 && offsetof(SsimLaunch, S) == 36 && offsetof(MotionLaunch, d) == 36, "");
+#pragma clang diagnostic pop
 
 #define WAVE 64
 

@@ -213,8 +213,7 @@ vp8_hist_frames_kernel(const uint8_t *__restrict__ raster, size_t fb_stride, con
     const HistFrameJob J = L.j[blockIdx.y];
     const bool pair = J.ref >= 0;
     const int rf = pair ? J.ref : J.fb;
-    const HistFrame C{raster + fb_stride * (size_t)(J.fb >> 2), tiles + tile_frame * (size_t)(J.fb >> 2), J.fb & 3};
-    const HistFrame R{raster + fb_stride * (size_t)(rf >> 2), tiles + tile_frame * (size_t)(rf >> 2), rf & 3};
+    const HistFrame C = frame_of(raster, fb_stride, tiles, tile_frame, J.fb), R = frame_of(raster, fb_stride, tiles, tile_frame, rf);
     GLOBAL_AS unsigned *out = (GLOBAL_AS unsigned *)(dst + dst_stride * blockIdx.y);
     if (L.planes & VP8HIP_HIST_Y) { hist_frame_plane<0>(H, C, R, pair, L, out); out += HIST_BINS; }
     if (L.planes & VP8HIP_HIST_U) { hist_frame_plane<1>(H, C, R, pair, L, out); out += HIST_BINS; }

@@ -97,8 +97,7 @@ vp8_motion_frames_kernel(const uint8_t *__restrict__ raster, size_t fb_stride, c
     const int tid = (int)threadIdx.x, nthreads = (int)blockDim.x;
     const int nmb = L.mb_cols * L.mb_rows, mb = (int)blockIdx.x, my = mb / L.mb_cols, mx = mb - my * L.mb_cols;
     const HistFrameJob J = L.j[blockIdx.y];
-    const HistFrame C{raster + fb_stride * (size_t)(J.fb >> 2), tiles + tile_frame * (size_t)(J.fb >> 2), J.fb & 3};
-    const HistFrame R{raster + fb_stride * (size_t)(J.ref >> 2), tiles + tile_frame * (size_t)(J.ref >> 2), J.ref & 3};
+    const HistFrame C = frame_of(raster, fb_stride, tiles, tile_frame, J.fb), R = frame_of(raster, fb_stride, tiles, tile_frame, J.ref);
     const int d = L.d, pitch = L.pitch;
 
     // (everything down to the staging is the same for every lane)

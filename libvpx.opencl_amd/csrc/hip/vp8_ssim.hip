@@ -99,8 +99,7 @@ vp8_ssim_frames_kernel(const uint8_t *__restrict__ raster, size_t fb_stride, con
     __shared__ u32x4_t cells[SSIM_CELL_ROWS * SSIM_CELL_COLS];
     __shared__ long long wave_sum[4][3];
     const HistFrameJob J = L.j[blockIdx.y];
-    const HistFrame C{raster + fb_stride * (size_t)(J.fb >> 2), tiles + tile_frame * (size_t)(J.fb >> 2), J.fb & 3};
-    const HistFrame R{raster + fb_stride * (size_t)(J.ref >> 2), tiles + tile_frame * (size_t)(J.ref >> 2), J.ref & 3};
+    const HistFrame C = frame_of(raster, fb_stride, tiles, tile_frame, J.fb), R = frame_of(raster, fb_stride, tiles, tile_frame, J.ref);
     uint8_t *const m = map + map_stride * blockIdx.y;
     long long acc[3] = {0, 0, 0};
 

@@ -16,7 +16,8 @@
 //                       byte histograms of pictures, slots and pool entries (vp8_hist.hip)
 //   vp8hip_ssim.hip     vp8hip_frames_ssim_async: the structural similarity of picture pairs (vp8_ssim.hip)
 //   vp8hip_motion.hip   vp8hip_frames_motion_async: full-search block motion between picture pairs (vp8_motion.hip)
-//   vp8hip_handover.hip the checks those calls share
+//   vp8hip_handover.hip what those calls share: the checks of their lists, of picture pairs and of destinations, and the planes'
+//                       geometry for the three calls that read picture pairs (hist, ssim, motion)
 // and vp8hip_res.hip.h: the owning types of the context's buffers, events and streams.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -197,13 +198,23 @@ static inline int vp8hip_frame_form(const vp8hip_ctx *c, int fb)
     const uint8_t st = c->fb_state[(size_t)fb];
     return (st & FB_RASTER) && c->fb_block ? SCALE_FROM_RASTER : (st & FB_TILES) ? SCALE_FROM_TILES : SCALE_FROM_ZERO;
 }
+// ... and how a launch names it to such a reader: frame buffer << 2 | that form, as of the call (the frame buffers of a job each
+// in a form of their own)
+static inline int vp8hip_frame_ref(const vp8hip_ctx *c, int fb) { return fb << 2 | vp8hip_frame_form(c, fb); }
 
 // vp8hip_handover.hip: what the calls that write tensors into the caller's device memory share.  The checks return 0, or -2
 // with the error set (its text begins with `who`); vp8hip_check_dst: stride >= size, destination and stride aligned to the
-// element, then vp8hip_check_device_span: device memory of the context's device, the n frames inside one allocation.
+// element, then vp8hip_check_device_span: device memory of the context's device, the n frames inside one allocation;
+// vp8hip_check_named_dst: the same for a call of several destinations, its texts begun with "`who` (`name`)".
+// vp8hip_check_pairs: fb, then ref_fb of each of n picture pairs (ref_optional: a ref_fb of exactly -1 names none);
+// vp8hip_frame_planes: where the planes of the context's frame buffers lie, for the kernels that read such pairs.
 #define VP8HIP_MAX_OUT_SIZE 16383       // the largest width / height of an output
 #define VP8HIP_GATHER_MAX_CHANNELS 4096 // the most channels of a tensor vp8hip_trace_gather_async moves
+#define VP8HIP_HIST_YUV (VP8HIP_HIST_Y | VP8HIP_HIST_U | VP8HIP_HIST_V)
 int vp8hip_check_fbs(vp8hip_ctx *c, const char *who, const int *fbs, int n);
+int vp8hip_check_pairs(vp8hip_ctx *c, const char *who, const vp8hip_hist_job *jobs, int n, bool ref_optional);
+void vp8hip_frame_planes(const vp8hip_ctx *c, FramePlanes &L);
+int vp8hip_check_named_dst(vp8hip_ctx *c, const char *who, const char *name, const void *dst, size_t dst_stride, size_t size, size_t elem_size, int n);
 int vp8hip_check_slots(vp8hip_ctx *c, const char *who, const int *slots, int n);
 bool vp8hip_out_grid(const vp8hip_ctx *c, int dst_w, int dst_h, int cells, int &gw, int &gh);
 int vp8hip_check_device_span(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, int n);

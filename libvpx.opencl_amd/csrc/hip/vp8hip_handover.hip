@@ -1,7 +1,10 @@
 // What the calls that hand something to a device consumer share on the host (vp8hip_frames_scale_async, _rgb_async, _side_async,
-// _residual_async, _coef_async, and of vp8hip_trace.hip vp8hip_frames_trace_async, vp8hip_trace_flow_async, _residual_async, _gather_async, vp8hip_frames_wear_async, vp8hip_trace_wear_async): the checks of their lists, of the output grid and of a destination in the caller's device memory, and what a
-// kernel needs of a slot's quantiser header.  Every check returns 0, or -2 with the error set, its text begun with `who`, the
-// calling function's name; none enqueues anything.
+// _residual_async, _coef_async, of vp8hip_trace.hip vp8hip_frames_trace_async, vp8hip_trace_flow_async, _residual_async,
+// _gather_async, vp8hip_frames_wear_async, vp8hip_trace_wear_async, and the three that read picture pairs, vp8hip_frames_hist_async,
+// _ssim_async and _motion_async): the checks of their lists, of picture pairs, of the output grid and of a destination in the
+// caller's device memory, named where a call has several; where the planes of the frame buffers lie; and what a kernel needs of a
+// slot's quantiser header.  Every check returns 0, or -2 with the error set, its text begun with `who`, the calling function's
+// name; none enqueues anything.
 #include "vp8hip_ctx.hip.h"
 
 // n frame buffers of the context
@@ -10,6 +13,26 @@ int vp8hip_check_fbs(vp8hip_ctx *c, const char *who, const int *fbs, int n)
     for (int i = 0; i < n; i++)
         if (fbs[i] < 0 || fbs[i] >= (int)c->fb.size()) return fail(c, -2, "%s: frame buffer %d out of range", who, fbs[i]);
     return 0;
+}
+
+// n picture pairs of the context, job by job fb, then ref_fb; ref_optional: a ref_fb of exactly -1 names none
+int vp8hip_check_pairs(vp8hip_ctx *c, const char *who, const vp8hip_hist_job *jobs, int n, bool ref_optional)
+{
+    for (int i = 0; i < n; i++) {
+        if (int rc = vp8hip_check_fbs(c, who, &jobs[i].fb, 1)) return rc;
+        if (ref_optional && jobs[i].ref_fb == -1) continue;
+        if (int rc = vp8hip_check_fbs(c, who, &jobs[i].ref_fb, 1)) return rc;
+    }
+    return 0;
+}
+
+// where the planes of the context's frame buffers lie, for the kernels that read them in either form (vp8_frame_read.hip.h)
+void vp8hip_frame_planes(const vp8hip_ctx *c, FramePlanes &L)
+{
+    L.dw = c->width; L.dh = c->height;
+    L.mb_cols = c->dg.mb_cols; L.mb_rows = c->dg.mb_rows;
+    L.y_off = c->dg.y_off; L.u_off = c->dg.u_off; L.v_off = c->dg.v_off;
+    L.y_stride = c->dg.y_stride; L.uv_stride = c->dg.uv_stride;
 }
 
 // n IR slots of the context, each holding a frame of the context's size (as of its last upload / copy / entropy launch)
@@ -72,6 +95,14 @@ int vp8hip_check_dst(vp8hip_ctx *c, const char *who, const void *dst, size_t dst
     if ((uintptr_t)dst % elem_size || dst_stride % elem_size)
         return fail(c, -2, "%s: destination %p / stride %zu not aligned to the %zu-byte element", who, dst, dst_stride, elem_size);
     return vp8hip_check_device_span(c, who, dst, dst_stride, size, n);
+}
+
+// ... of a call that has several destinations: the texts begin with "`who` (`name`)"
+int vp8hip_check_named_dst(vp8hip_ctx *c, const char *who, const char *name, const void *dst, size_t dst_stride, size_t size, size_t elem_size, int n)
+{
+    char who_dst[64];
+    snprintf(who_dst, sizeof(who_dst), "%s (%s)", who, name);
+    return vp8hip_check_dst(c, who_dst, dst, dst_stride, size, elem_size, n);
 }
 
 // the quantiser index of each segment (mb_init_dequantizer, vp8/decoder/decodframe.c), segment s in bits 7s .. 7s + 6

@@ -31,9 +31,7 @@ extern "C" size_t vp8hip_hist_size(int planes_popcount)
 static int hist_check_out(vp8hip_ctx *c, const char *who, unsigned planes, unsigned valid, void *dst, size_t dst_stride, int n)
 {
     if (!planes || (planes & ~valid)) return fail(c, -2, "%s: planes 0x%x (at least one of 0x%x)", who, planes, valid);
-    char who_dst[64];
-    snprintf(who_dst, sizeof(who_dst), "%s (dst)", who);
-    return vp8hip_check_dst(c, who_dst, dst, dst_stride, vp8hip_hist_size(__builtin_popcount(planes)), 4, n);
+    return vp8hip_check_named_dst(c, who, "dst", dst, dst_stride, vp8hip_hist_size(__builtin_popcount(planes)), 4, n);
 }
 
 // workgroups that share a job of `quads` groups in `rows` rows, in a call of n jobs
@@ -60,29 +58,21 @@ extern "C" int vp8hip_frames_hist_async(vp8hip_ctx *c, const vp8hip_hist_job *jo
 {
     const char *who = "vp8hip_frames_hist_async";
     if (!c || !jobs || n < 1 || !dst || !c->width || c->fb.empty()) return fail(c, -2, "%s: bad arguments", who);
-    for (int i = 0; i < n; i++) {
-        if (int rc = vp8hip_check_fbs(c, who, &jobs[i].fb, 1)) return rc;
-        if (jobs[i].ref_fb != -1)
-            if (int rc = vp8hip_check_fbs(c, who, &jobs[i].ref_fb, 1)) return rc;
-    }
-    if (int rc = hist_check_out(c, who, planes, VP8HIP_HIST_Y | VP8HIP_HIST_U | VP8HIP_HIST_V, dst, dst_stride, n)) return rc;
+    if (int rc = vp8hip_check_pairs(c, who, jobs, n, true)) return rc;
+    if (int rc = hist_check_out(c, who, planes, VP8HIP_HIST_YUV, dst, dst_stride, n)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
 
     HistFrameLaunch L;
-    memset(&L, 0, offsetof(HistFrameLaunch, j));
-    L.dw = c->width; L.dh = c->height;
-    L.mb_cols = c->dg.mb_cols; L.mb_rows = c->dg.mb_rows;
-    L.y_off = c->dg.y_off; L.u_off = c->dg.u_off; L.v_off = c->dg.v_off;
-    L.y_stride = c->dg.y_stride; L.uv_stride = c->dg.uv_stride;
+    memset(&L, 0, sizeof(L) - sizeof(L.j));
+    vp8hip_frame_planes(c, L);
     L.S = hist_share(n, (long long)((L.dw + 15) >> 4) * L.dh, (L.dh + 1) >> 1);
     L.planes = planes;
     for (int i0 = 0; i0 < n; i0 += HIST_MAX_JOBS) {
         const int m = n - i0 < HIST_MAX_JOBS ? n - i0 : HIST_MAX_JOBS;
         for (int k = 0; k < m; k++) {
             const vp8hip_hist_job &job = jobs[i0 + k];
-            // each frame buffer in a form it has: raster where it exists, else tiles; the two of a job independently
-            L.j[k].fb = job.fb << 2 | vp8hip_frame_form(c, job.fb);
-            L.j[k].ref = job.ref_fb < 0 ? -1 : job.ref_fb << 2 | vp8hip_frame_form(c, job.ref_fb);
+            L.j[k].fb = vp8hip_frame_ref(c, job.fb);
+            L.j[k].ref = job.ref_fb < 0 ? -1 : vp8hip_frame_ref(c, job.ref_fb);
         }
         uint8_t *d = (uint8_t *)dst + dst_stride * (size_t)i0;
         if (int rc = hist_fill(c, (unsigned)L.S, planes, d, dst_stride, m)) return rc;

@@ -12,13 +12,6 @@ extern "C" __global__ void vp8_motion_frames_kernel(const uint8_t *raster, size_
 #define MOTION_PLANES (VP8HIP_MOTION_SAD | VP8HIP_MOTION_SAD0 | VP8HIP_MOTION_SSE | VP8HIP_MOTION_VAR | VP8HIP_MOTION_SRCVAR)
 #define MOTION_LDS_FIXED (8 + 64 + 2 * (2 * MOTION_MAX_D + 2))      // dwords in front of the window (vp8_motion.hip: MOTION_LDS_WINDOW)
 
-static int motion_popcount(unsigned planes)
-{
-    int np = 0;
-    for (unsigned b = planes; b; b &= b - 1) np++;
-    return np;
-}
-
 // what the call refuses on p alone
 static bool motion_params_ok(const vp8hip_motion *p)
 {
@@ -33,7 +26,7 @@ extern "C" size_t vp8hip_motion_mv_size(const vp8hip_ctx *c)
 extern "C" size_t vp8hip_motion_stats_size(const vp8hip_ctx *c, const vp8hip_motion *p)
 {
     if (!c || !c->width || !motion_params_ok(p) || !p->planes) return 0;
-    return (size_t)4 * motion_popcount(p->planes) * c->dg.mb_cols * c->dg.mb_rows;
+    return (size_t)4 * __builtin_popcount(p->planes) * c->dg.mb_cols * c->dg.mb_rows;
 }
 
 extern "C" int vp8hip_frames_motion_async(vp8hip_ctx *c, const vp8hip_hist_job *jobs, int n, const vp8hip_motion *p, const void *centre,
@@ -41,17 +34,14 @@ extern "C" int vp8hip_frames_motion_async(vp8hip_ctx *c, const vp8hip_hist_job *
 {
     const char *who = "vp8hip_frames_motion_async";
     if (!c || !jobs || n < 1 || !p || (!mv && !stats) || !c->width || c->fb.empty()) return fail(c, -2, "%s: bad arguments", who);
-    for (int i = 0; i < n; i++) {
-        if (int rc = vp8hip_check_fbs(c, who, &jobs[i].fb, 1)) return rc;
-        if (int rc = vp8hip_check_fbs(c, who, &jobs[i].ref_fb, 1)) return rc;
-    }
+    if (int rc = vp8hip_check_pairs(c, who, jobs, n, false)) return rc;
     if (!motion_params_ok(p))
         return fail(c, -2, "%s: distance %d (1..%d), sad_per_bit %d (0..255), planes 0x%x (of 0x%x)", who, p->distance, MOTION_MAX_D, p->sad_per_bit,
                     p->planes, MOTION_PLANES);
     if (stats && !p->planes) return fail(c, -2, "%s: stats without planes", who);
     const int d = p->distance;
     MotionLaunch L;
-    memset(&L, 0, offsetof(MotionLaunch, j));
+    memset(&L, 0, sizeof(L) - sizeof(L.j));
     if (p->cost && p->sad_per_bit) {
         for (int k = 0; k < 2; k++)
             for (int i = 0; i <= 2 * d; i++) {
@@ -66,21 +56,18 @@ extern "C" int vp8hip_frames_motion_async(vp8hip_ctx *c, const vp8hip_hist_job *
         return fail(c, -2, "%s: a centre tensor on more than 255 macroblocks a side", who);
     const size_t mv_size = vp8hip_motion_mv_size(c), stats_size = vp8hip_motion_stats_size(c, p);
     if (mv)
-        if (int rc = vp8hip_check_dst(c, "vp8hip_frames_motion_async (mv)", mv, mv_stride, mv_size, 2, n)) return rc;
+        if (int rc = vp8hip_check_named_dst(c, who, "mv", mv, mv_stride, mv_size, 2, n)) return rc;
     if (stats)
-        if (int rc = vp8hip_check_dst(c, "vp8hip_frames_motion_async (stats)", stats, stats_stride, stats_size, 4, n)) return rc;
+        if (int rc = vp8hip_check_named_dst(c, who, "stats", stats, stats_stride, stats_size, 4, n)) return rc;
     if (centre)
-        if (int rc = vp8hip_check_dst(c, "vp8hip_frames_motion_async (centre)", centre, centre_stride, mv_size, 2, n)) return rc;
+        if (int rc = vp8hip_check_named_dst(c, who, "centre", centre, centre_stride, mv_size, 2, n)) return rc;
     if (mv && stats && vp8hip_spans_overlap(mv, mv_stride, n, stats, stats_stride, n)) return fail(c, -2, "%s: mv and stats overlap", who);
     if (mv && centre && vp8hip_spans_overlap(mv, mv_stride, n, centre, centre_stride, n)) return fail(c, -2, "%s: mv and centre overlap", who);
     if (stats && centre && vp8hip_spans_overlap(stats, stats_stride, n, centre, centre_stride, n))
         return fail(c, -2, "%s: stats and centre overlap", who);
     HIPCHK(c, hipSetDevice(c->device));
 
-    L.dw = c->width; L.dh = c->height;
-    L.mb_cols = c->dg.mb_cols; L.mb_rows = c->dg.mb_rows;
-    L.y_off = c->dg.y_off; L.u_off = c->dg.u_off; L.v_off = c->dg.v_off;
-    L.y_stride = c->dg.y_stride; L.uv_stride = c->dg.uv_stride;
+    vp8hip_frame_planes(c, L);
     L.d = d;
     L.nq = (2 * d + 3) / 4;
     L.groups = (2 * d + MOTION_ROWS - 1) / MOTION_ROWS;
@@ -98,9 +85,8 @@ extern "C" int vp8hip_frames_motion_async(vp8hip_ctx *c, const vp8hip_hist_job *
     for (int i0 = 0; i0 < n; i0 += MOTION_MAX_JOBS) {
         const int m = n - i0 < MOTION_MAX_JOBS ? n - i0 : MOTION_MAX_JOBS;
         for (int k = 0; k < m; k++) {
-            // each frame buffer in a form it has: raster where it exists, else tiles; the two of a job independently
-            L.j[k].fb = jobs[i0 + k].fb << 2 | vp8hip_frame_form(c, jobs[i0 + k].fb);
-            L.j[k].ref = jobs[i0 + k].ref_fb << 2 | vp8hip_frame_form(c, jobs[i0 + k].ref_fb);
+            L.j[k].fb = vp8hip_frame_ref(c, jobs[i0 + k].fb);
+            L.j[k].ref = vp8hip_frame_ref(c, jobs[i0 + k].ref_fb);
         }
         const uint8_t *dc = centre ? (const uint8_t *)centre + centre_stride * (size_t)i0 : nullptr;
         uint8_t *dv = mv ? (uint8_t *)mv + mv_stride * (size_t)i0 : nullptr;

@@ -134,7 +134,7 @@ extern "C" int vp8hip_frames_rgb_async(vp8hip_ctx *c, const int *fbs, int n, con
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = n - i0 < chunk ? n - i0 : chunk;
         if (from_frames) {
-            for (int k = 0; k < m; k++) L.fb[k] = fbs[i0 + k] << 2 | vp8hip_frame_form(c, fbs[i0 + k]);
+            for (int k = 0; k < m; k++) L.fb[k] = vp8hip_frame_ref(c, fbs[i0 + k]);
         } else {
             if (int rc = vp8hip_scale_enqueue(c, fbs + i0, m, S, scale_lds, c->d_rgb, istride)) return rc;
             for (int k = 0; k < m; k++) L.fb[k] = SCALE_FROM_PACKED;

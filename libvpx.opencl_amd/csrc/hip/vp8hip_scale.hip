@@ -78,7 +78,7 @@ int vp8hip_scale_plan(const vp8hip_ctx *c, int dw, int dh, int filter, ScaleLaun
 // exists, else tiles; never converted
 int vp8hip_scale_enqueue(vp8hip_ctx *c, const int *fbs, int m, ScaleLaunch &L, int lds, void *dst, size_t dst_stride)
 {
-    for (int k = 0; k < m; k++) L.fb[k] = fbs[k] << 2 | vp8hip_frame_form(c, fbs[k]);
+    for (int k = 0; k < m; k++) L.fb[k] = vp8hip_frame_ref(c, fbs[k]);
     hipLaunchKernelGGL(vp8_scale_kernel, dim3((unsigned)L.blocks, (unsigned)m), dim3(256), (unsigned)lds, c->stream, (const uint8_t *)c->fb_block,
                        c->fb_stride, (const uint8_t *)c->tile_block, c->tile_frame, (uint8_t *)dst, dst_stride, L);
     HIPCHK(c, hipGetLastError());

@@ -10,7 +10,6 @@ extern "C" __global__ void vp8_ssim_frames_kernel(const uint8_t *raster, size_t 
                                                   size_t scores_stride, uint8_t *map, size_t map_stride, SsimLaunch L);
 
 #define SSIM_CHIP_WGS 2048                      // workgroups a call aims at: calls of fewer jobs share a job's pieces among several
-#define SSIM_PLANES (VP8HIP_HIST_Y | VP8HIP_HIST_U | VP8HIP_HIST_V)
 
 extern "C" int vp8hip_ssim_windows(int w, int h, int *nwx, int *nwy)
 {
@@ -28,7 +27,7 @@ extern "C" size_t vp8hip_ssim_scores_size(int planes_popcount)
 // the planes of `planes` on context c, their windows, pieces and places in a job's map; false for planes the call refuses
 static bool ssim_planes(const vp8hip_ctx *c, unsigned planes, SsimLaunch &L, size_t &map_elems)
 {
-    if (!c || !c->width || !planes || (planes & ~SSIM_PLANES)) return false;
+    if (!c || !c->width || !planes || (planes & ~VP8HIP_HIST_YUV)) return false;
     L.np = L.pieces = 0;
     map_elems = 0;
     for (int pl = 0; pl < 3; pl++) {
@@ -74,29 +73,23 @@ extern "C" int vp8hip_frames_ssim_async(vp8hip_ctx *c, const vp8hip_hist_job *jo
 {
     const char *who = "vp8hip_frames_ssim_async";
     if (!c || !jobs || n < 1 || !p || (!scores && !map) || !c->width || c->fb.empty()) return fail(c, -2, "%s: bad arguments", who);
-    for (int i = 0; i < n; i++) {
-        if (int rc = vp8hip_check_fbs(c, who, &jobs[i].fb, 1)) return rc;
-        if (int rc = vp8hip_check_fbs(c, who, &jobs[i].ref_fb, 1)) return rc;
-    }
+    if (int rc = vp8hip_check_pairs(c, who, jobs, n, false)) return rc;
     SsimLaunch L;
-    memset(&L, 0, offsetof(SsimLaunch, j));
+    memset(&L, 0, sizeof(L) - sizeof(L.j));
     size_t map_elems = 0;
-    if (!ssim_planes(c, p->planes, L, map_elems)) return fail(c, -2, "%s: planes 0x%x (at least one of 0x%x)", who, p->planes, SSIM_PLANES);
+    if (!ssim_planes(c, p->planes, L, map_elems)) return fail(c, -2, "%s: planes 0x%x (at least one of 0x%x)", who, p->planes, VP8HIP_HIST_YUV);
     const int dt = p->map_dtype;
     if (dt != VP8HIP_SSIM_F16 && dt != VP8HIP_SSIM_F32 && (dt != 0 || map)) return fail(c, -2, "%s: map_dtype %d", who, dt);
     if (map && !map_elems) return fail(c, -2, "%s: a map of planes without windows", who);
     const size_t es = dt == VP8HIP_SSIM_F32 ? 4 : 2, map_size = map_elems * es, scores_size = vp8hip_ssim_scores_size(L.np);
     if (scores)
-        if (int rc = vp8hip_check_dst(c, "vp8hip_frames_ssim_async (scores)", scores, scores_stride, scores_size, 8, n)) return rc;
+        if (int rc = vp8hip_check_named_dst(c, who, "scores", scores, scores_stride, scores_size, 8, n)) return rc;
     if (map)
-        if (int rc = vp8hip_check_dst(c, "vp8hip_frames_ssim_async (map)", map, map_stride, map_size, es, n)) return rc;
+        if (int rc = vp8hip_check_named_dst(c, who, "map", map, map_stride, map_size, es, n)) return rc;
     if (scores && map && vp8hip_spans_overlap(scores, scores_stride, n, map, map_stride, n)) return fail(c, -2, "%s: scores and map overlap", who);
     HIPCHK(c, hipSetDevice(c->device));
 
-    L.dw = c->width; L.dh = c->height;
-    L.mb_cols = c->dg.mb_cols; L.mb_rows = c->dg.mb_rows;
-    L.y_off = c->dg.y_off; L.u_off = c->dg.u_off; L.v_off = c->dg.v_off;
-    L.y_stride = c->dg.y_stride; L.uv_stride = c->dg.uv_stride;
+    vp8hip_frame_planes(c, L);
     L.S = ssim_share(n, L.pieces);
     L.scores = scores != nullptr;
     L.map_dtype = map ? dt : 0;
@@ -106,9 +99,8 @@ extern "C" int vp8hip_frames_ssim_async(vp8hip_ctx *c, const vp8hip_hist_job *jo
     for (int i0 = 0; i0 < n; i0 += SSIM_MAX_JOBS) {
         const int m = n - i0 < SSIM_MAX_JOBS ? n - i0 : SSIM_MAX_JOBS;
         for (int k = 0; k < m; k++) {
-            // each frame buffer in a form it has: raster where it exists, else tiles; the two of a job independently
-            L.j[k].fb = jobs[i0 + k].fb << 2 | vp8hip_frame_form(c, jobs[i0 + k].fb);
-            L.j[k].ref = jobs[i0 + k].ref_fb << 2 | vp8hip_frame_form(c, jobs[i0 + k].ref_fb);
+            L.j[k].fb = vp8hip_frame_ref(c, jobs[i0 + k].fb);
+            L.j[k].ref = vp8hip_frame_ref(c, jobs[i0 + k].ref_fb);
         }
         uint8_t *ds = scores ? (uint8_t *)scores + scores_stride * (size_t)i0 : nullptr;
         uint8_t *dm = map ? (uint8_t *)map + map_stride * (size_t)i0 : nullptr;

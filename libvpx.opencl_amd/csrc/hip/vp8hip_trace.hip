@@ -397,9 +397,9 @@ extern "C" int vp8hip_trace_residual_async(vp8hip_ctx *c, const vp8hip_anchor_jo
         for (int k = 0; k < m; k++) {
             const vp8hip_anchor_job &job = jobs[i0 + k];
             // each frame buffer in a form it has: raster where it exists, else tiles; the two of a job independently
-            L.j[k].fb = job.fb << 2 | vp8hip_frame_form(c, job.fb);
+            L.j[k].fb = vp8hip_frame_ref(c, job.fb);
             L.j[k].trace = job.trace;
-            L.j[k].anchor = job.anchor_fb << 2 | vp8hip_frame_form(c, job.anchor_fb);
+            L.j[k].anchor = vp8hip_frame_ref(c, job.anchor_fb);
         }
         hipLaunchKernelGGL(kernels[p->dtype], dim3((unsigned)L.g.S, (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)c->fb_block, c->fb_stride,
                            (const uint8_t *)c->tile_block, c->tile_frame, (const uint8_t *)pool, pool_stride,

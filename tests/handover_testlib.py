@@ -1,13 +1,16 @@
 """What the GPU tests of the calls that hand something to a device consumer as tensors share (test_gpu_scale.py, test_gpu_rgb.py,
-test_gpu_side.py, test_gpu_residual.py): frames into frame buffers and into IR slots, bit patterns, guarded destinations, the
-destinations every call refuses and the writers that come after a call.  torch is imported here before anything loads
-libvp8hip.so: one HIP runtime per process."""
+test_gpu_side.py, test_gpu_residual.py, test_gpu_coef.py, the trace tests through trace_testlib.py, and the three that read picture
+pairs, test_gpu_hist.py, test_gpu_ssim.py and test_gpu_motion.py): frames into frame buffers and into IR slots, pictures into frame
+buffer images, bit patterns, guarded destinations, the destinations every call refuses, the writers that come after a call and the
+decode a call over picture pairs is ordered against.  torch is imported here before anything loads libvp8hip.so: one HIP runtime
+per process."""
 import ctypes
 
 import torch
 import numpy as np
 
 from vp8_testlib import ivf_path
+import scale_reference as SC
 
 TORCH_DTYPE = {"u8": torch.uint8, "i16": torch.int16, "f16": torch.float16, "f32": torch.float32}
 BITS = {"u8": np.uint8, "i16": np.uint16, "f16": np.uint16, "f32": np.uint32}
@@ -81,6 +84,34 @@ def large_launch(P, ctx, name, n, monkeypatch):
         ctx.ir_copy(i, i % len(frames))
     ctx.decode([(i, i, None) for i in range(n)], P.STAGE_ALL)
     return len(frames)
+
+
+def picture_into(buf, g, planes):
+    """display-size planes (y, u, v) into the frame buffer image `buf`; what lies around them stays"""
+    for view, p in zip(SC.planes(buf, g), planes):
+        view[:p.shape[0], :p.shape[1]] = p
+    return buf
+
+
+def two_key_frames_queued(P):
+    """-> (ctx, parser): the two key frames of kf_640x360 in slots 0 and 1 of a context of two frame buffers; frame 1 is decoded
+    into frame buffer 1 and waited for, the decode of frame 0 into frame buffer 0 is queued and not waited for"""
+    w, h, frames = P.read_ivf(ivf_path("kf_640x360"))
+    ctx = P.Vp8Hip(0)
+    parser = P.Parser()
+    try:
+        ctx.configure(w, h, 2, 2)
+        for i in range(2):
+            hdr, _ = ctx.parse_into_slot_compact(parser, frames[i], i)
+            parser.swap(hdr)
+        ctx.decode([(1, 1, None)], P.STAGE_ALL)
+        ctx.sync()
+        ctx.decode([(0, 0, None)], P.STAGE_ALL)
+    except BaseException:
+        parser.close()
+        ctx.close()
+        raise
+    return ctx, parser
 
 
 class Producer:

@@ -10,11 +10,9 @@ import torch  # noqa: F401  (first: the library then shares torch's HIP runtime)
 import numpy as np
 import pytest
 
-from vp8_testlib import ivf_path
 from handover_testlib import (Producer, assert_destinations_refused, assert_guards_intact, guarded, large_launch, later_writers_producer,
-                              write_later_frames)
+                              picture_into, two_key_frames_queued, write_later_frames)
 import hist_reference as H
-import scale_reference as SC
 import side_reference as S
 import trace_reference as R
 import wear_reference as W
@@ -35,13 +33,6 @@ def counts(t):
     return t.cpu().numpy().view(np.uint32)
 
 
-def picture_into(buf, g, w, h, planes):
-    """display-size planes (y, u, v) into the frame buffer image `buf`; what lies around them stays"""
-    for view, p in zip(SC.planes(buf, g), planes):
-        view[:p.shape[0], :p.shape[1]] = p
-    return buf
-
-
 @pytest.mark.parametrize("size", SIZES)
 def test_pictures_from_raster(pkg, size):
     """uploaded frame buffers in the geom() layout at sizes whose widths are and are not multiples of 4 and 16, with odd chroma widths
@@ -60,8 +51,8 @@ def test_pictures_from_raster(pkg, size):
         ramp = [(np.arange(ph * pw) * k % 256).astype(np.uint8).reshape(ph, pw) for k, (pw, ph) in ((1, (w, h)), (3, (cw, ch)), (7, (cw, ch)))]
         flat = [np.full((h, w), 37, np.uint8), np.full((ch, cw), 255, np.uint8), np.full((ch, cw), 0, np.uint8)]
         bufs = [rng.integers(0, 256, g.frame_size, dtype=np.uint8),
-                picture_into(np.full(g.frame_size, 0x77, np.uint8), g, w, h, ramp),
-                picture_into(np.full(g.frame_size, 200, np.uint8), g, w, h, flat),
+                picture_into(np.full(g.frame_size, 0x77, np.uint8), g, ramp),
+                picture_into(np.full(g.frame_size, 200, np.uint8), g, flat),
                 rng.integers(0, 256, g.frame_size, dtype=np.uint8)]
         for k, b in enumerate(bufs):
             ctx.upload_frame(k, b)
@@ -494,18 +485,9 @@ def test_ordering_against_a_decode_into_the_same_frame_buffer(pkg):
     """frames_hist, then at once a decode of another frame into the same frame buffer: the histogram is that of the picture that was
     there at the call; and an earlier decode is seen without a sync"""
     P = pkg
-    w, h, frames = P.read_ivf(ivf_path("kf_640x360"))
-    ctx = P.Vp8Hip(0)
-    parser = P.Parser()
+    ctx, parser = two_key_frames_queued(P)
     try:
-        ctx.configure(w, h, 2, 2)
-        for i in range(2):
-            hdr, _ = ctx.parse_into_slot_compact(parser, frames[i], i)
-            parser.swap(hdr)
-        ctx.decode([(1, 1, None)], P.STAGE_ALL)
-        ctx.sync()
-        second = H.frames(ctx.download_planes(1))
-        ctx.decode([(0, 0, None)], P.STAGE_ALL)
+        w, h = ctx.width, ctx.height
         out = ctx.frames_hist([0, (0, 1)])               # behind the decode of frame 0 ...
         ctx.decode([(1, 0, None)], P.STAGE_ALL)          # ... and in front of the decode of frame 1 into the same frame buffer
         got = counts(out)
@@ -513,7 +495,7 @@ def test_ordering_against_a_decode_into_the_same_frame_buffer(pkg):
         ctx.decode([(0, 0, None)], P.STAGE_ALL)
         ctx.sync()
         planes0, planes1 = ctx.download_planes(0), ctx.download_planes(1)
-        first = H.frames(planes0)
+        first, second = H.frames(planes0), H.frames(planes1)         # (frame buffer 1 holds frame 1 throughout)
         assert not np.array_equal(first, second)
         assert np.array_equal(got[0], first) and np.array_equal(got[1], H.frames(planes0, planes1))
         assert np.array_equal(after[0], second) and after[1, 0, 0] == w * h and not after[1, :, 1:].any()
@@ -555,3 +537,65 @@ def test_no_new_device_memory_and_sources_untouched(pkg):
         assert np.array_equal(again[0], ir[0]) and np.array_equal(again[1], ir[1])
     finally:
         prod.close()
+
+
+def test_pair_refusal_texts(pkg):
+    """What vp8hip_last_error says after each refusal of the three calls over picture pairs (vp8hip_frames_hist_async, _ssim_async,
+    _motion_async), and, by two faults at once, which check comes first: the texts the library gave before the three calls shared
+    their host path.  48x32 with two frame buffers -- 3 x 2 macroblocks, the smallest size at which every check is reachable;
+    every call here is refused and nothing is enqueued.  (The alignment refusal prints a pointer and is left out.)"""
+    P = pkg
+    ctx = P.Vp8Hip(0)
+    try:
+        ctx.configure(48, 32, 2, 1)
+        L, vp = ctx.L, ctypes.c_void_p
+        mem = torch.empty((4096,), dtype=torch.uint8, device="cuda:0")
+        d = mem.data_ptr()
+        assert d % 16 == 0 and P.hist_size(3) == 3072 and P.ssim_sizes(48, 32, 7, 2) == (48, 304) and P.motion_sizes(3, 2, 31) == (24, 120)
+
+        def hist(job=(0, 1), n=1, planes=7, stride=3072):
+            return L.vp8hip_frames_hist_async(ctx.h, (P.HistJob * 1)(job), n, planes, vp(d), stride)
+
+        def ssim(job=(0, 1), n=1, planes=7, sc=d, ss=48, mp=d + 1024, ms=304):
+            return L.vp8hip_frames_ssim_async(ctx.h, (P.HistJob * 1)(job), n, ctypes.byref(P.SsimParams(planes, 2)), vp(sc), ss, vp(mp), ms)
+
+        def motion(job=(0, 1), n=1, planes=31, mv=d, ms=24, st=d + 1024, ss=120, cen=None, cs=24):
+            return L.vp8hip_frames_motion_async(ctx.h, (P.HistJob * 1)(job), n, ctypes.byref(P.MotionParams(4, 0, planes, None)),
+                                                vp(cen) if cen else None, cs, vp(mv) if mv else None, ms, vp(st) if st else None, ss)
+        params = "distance 4 (1..64), sad_per_bit 0 (0..255), planes 0x20 (of 0x1f)"
+        cases = [(hist, "vp8hip_frames_hist_async", [
+                      (dict(job=(0, -1), planes=0), ": planes 0x0 (at least one of 0x7)"),          # ref_fb -1: none, accepted
+                      (dict(planes=0), ": planes 0x0 (at least one of 0x7)"),
+                      (dict(planes=8), ": planes 0x8 (at least one of 0x7)"),
+                      (dict(stride=3068), " (dst): stride 3068 below the frame's 3072 bytes"),
+                      (dict(job=(5, 7), planes=8), ": frame buffer 5 out of range"),
+                      (dict(planes=0xf, stride=3068), ": planes 0xf (at least one of 0x7)")]),
+                 (ssim, "vp8hip_frames_ssim_async", [
+                      (dict(job=(0, -1)), ": frame buffer -1 out of range"),
+                      (dict(planes=0), ": planes 0x0 (at least one of 0x7)"),
+                      (dict(planes=8), ": planes 0x8 (at least one of 0x7)"),
+                      (dict(ss=40), " (scores): stride 40 below the frame's 48 bytes"),
+                      (dict(ms=300), " (map): stride 300 below the frame's 304 bytes"),
+                      (dict(mp=d + 16), ": scores and map overlap"),
+                      (dict(job=(5, 7), planes=8), ": frame buffer 5 out of range"),
+                      (dict(planes=0xf, ss=40), ": planes 0xf (at least one of 0x7)")]),
+                 (motion, "vp8hip_frames_motion_async", [
+                      (dict(job=(0, -1)), ": frame buffer -1 out of range"),
+                      (dict(planes=0), ": stats without planes"),
+                      (dict(planes=32), ": " + params),
+                      (dict(ms=22), " (mv): stride 22 below the frame's 24 bytes"),
+                      (dict(ss=116), " (stats): stride 116 below the frame's 120 bytes"),
+                      (dict(cen=d + 2048, cs=22), " (centre): stride 22 below the frame's 24 bytes"),
+                      (dict(st=d + 8), ": mv and stats overlap"),
+                      (dict(cen=d + 2), ": mv and centre overlap"),
+                      (dict(cen=d + 1028), ": stats and centre overlap"),
+                      (dict(job=(5, 7), planes=32), ": frame buffer 5 out of range"),
+                      (dict(planes=32, ms=22), ": " + params)])]
+        for call, who, own in cases:
+            shared = [(dict(n=0), ": bad arguments"), (dict(job=(2, 0)), ": frame buffer 2 out of range"), (dict(job=(0, 3)), ": frame buffer 3 out of range"),
+                      (dict(job=(0, -2)), ": frame buffer -2 out of range"), (dict(job=(-1, 0)), ": frame buffer -1 out of range")]
+            for kw, text in shared + own:
+                assert call(**kw) == -2, (who, kw)
+                assert L.vp8hip_last_error(ctx.h).decode() == who + text, (who, kw)
+    finally:
+        ctx.close()

@@ -10,8 +10,7 @@ import torch  # noqa: F401  (first: the library then shares torch's HIP runtime)
 import numpy as np
 import pytest
 
-from vp8_testlib import ivf_path
-from handover_testlib import assert_destinations_refused, assert_guards_intact, decode_stream, guarded, large_launch
+from handover_testlib import assert_destinations_refused, assert_guards_intact, decode_stream, guarded, large_launch, two_key_frames_queued
 import scale_reference as SC
 import motion_reference as MR
 
@@ -411,17 +410,8 @@ def test_ordering_against_a_decode_into_the_same_frame_buffer(pkg):
     """frames_motion, then at once a decode of another frame into one of the pair's frame buffers: the vectors are those of the
     pictures that were there at the call; and an earlier decode is seen without a sync"""
     P = pkg
-    w, h, frames = P.read_ivf(ivf_path("kf_640x360"))
-    ctx = P.Vp8Hip(0)
-    parser = P.Parser()
+    ctx, parser = two_key_frames_queued(P)
     try:
-        ctx.configure(w, h, 2, 2)
-        for i in range(2):
-            hdr, _ = ctx.parse_into_slot_compact(parser, frames[i], i)
-            parser.swap(hdr)
-        ctx.decode([(1, 1, None)], P.STAGE_ALL)
-        ctx.sync()
-        ctx.decode([(0, 0, None)], P.STAGE_ALL)
         out = ctx.frames_motion([(0, 1), (1, 0)], 4, planes=31)          # behind the decode of frame 0 ...
         ctx.decode([(1, 0, None)], P.STAGE_ALL)                           # ... and in front of the decode of frame 1 into the same frame buffer
         got_mv, got_st = out[0].cpu().numpy(), stats_bits(out[1])

@@ -10,8 +10,8 @@ import torch  # noqa: F401  (first: the library then shares torch's HIP runtime)
 import numpy as np
 import pytest
 
-from vp8_testlib import ivf_path
-from handover_testlib import assert_destinations_refused, assert_guards_intact, decode_stream, guarded, large_launch
+from handover_testlib import (assert_destinations_refused, assert_guards_intact, decode_stream, guarded, large_launch, picture_into,
+                              two_key_frames_queued)
 import scale_reference as SC
 import ssim_reference as SR
 
@@ -79,13 +79,6 @@ def raw_call(ctx, P, jobs, mask, dt, scores=None, scores_stride=0, mp=None, map_
     vp = ctypes.c_void_p
     return ctx.L.vp8hip_frames_ssim_async(ctx.h, arr, len(jobs) if n is None else n, ctypes.byref(P.SsimParams(mask, dt)),
                                           vp(scores) if scores else None, scores_stride, vp(mp) if mp else None, map_stride)
-
-
-def picture_into(buf, g, planes):
-    """display-size planes (y, u, v) into the frame buffer image `buf`; what lies around them stays"""
-    for view, p in zip(SC.planes(buf, g), planes):
-        view[:p.shape[0], :p.shape[1]] = p
-    return buf
 
 
 def upload_pictures(ctx, w, h, seed):
@@ -402,17 +395,8 @@ def test_ordering_against_a_decode_into_the_same_frame_buffer(pkg):
     """frames_ssim, then at once a decode of another frame into one of the pair's frame buffers: the scores are those of the pictures
     that were there at the call; and an earlier decode is seen without a sync"""
     P = pkg
-    w, h, frames = P.read_ivf(ivf_path("kf_640x360"))
-    ctx = P.Vp8Hip(0)
-    parser = P.Parser()
+    ctx, parser = two_key_frames_queued(P)
     try:
-        ctx.configure(w, h, 2, 2)
-        for i in range(2):
-            hdr, _ = ctx.parse_into_slot_compact(parser, frames[i], i)
-            parser.swap(hdr)
-        ctx.decode([(1, 1, None)], P.STAGE_ALL)
-        ctx.sync()
-        ctx.decode([(0, 0, None)], P.STAGE_ALL)
         out = ctx.frames_ssim([(0, 1), (1, 0)], 7, torch.float32)        # behind the decode of frame 0 ...
         ctx.decode([(1, 0, None)], P.STAGE_ALL)                           # ... and in front of the decode of frame 1 into the same frame buffer
         got, bits = out[0].cpu().numpy(), map_bits(out[1])
