@@ -988,6 +988,92 @@ size_t vp8hip_motion_mv_size(const vp8hip_ctx *ctx);
 size_t vp8hip_motion_stats_size(const vp8hip_ctx *ctx, const vp8hip_motion *p);
 int  vp8hip_frames_motion_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int n, const vp8hip_motion *p, const void *centre,
                                 size_t centre_stride, void *mv, size_t mv_stride, void *stats, size_t stats_stride);
+/* SUB-PIXEL REFINEMENT of block motion between pictures.  vp8hip_frames_motion_async's vectors are whole pixels; everything else
+ * that carries motion here (vp8hip_frames_side_async, the traces, the flow tensors) has quarter-pel precision in 1/8-pel units.
+ * vp8hip_frames_subpel_async is the step the reference always makes behind its whole-pixel search: vp8_find_best_sub_pixel_step
+ * (vp8/encoder/mcomp.c; at precision 2 vp8_find_best_half_pixel_step, the same code cut short) over
+ * vp8_sub_pixel_variance16x16_c, bit for bit.  Jobs are vp8hip_hist_job (fb, ref_fb) exactly as for vp8hip_frames_motion_async, and
+ * so are the pictures S(F), E(F), A, B and how a frame buffer is read; ref_fb < 0 is refused, fb == ref_fb is legal.  Luma only,
+ * 16x16 only.
+ *
+ * Per macroblock (my, mx), with the motion call's BOUNDS cmin, cmax, rmin, rmax:
+ *   START   (sy, sx) in whole pixels: (0, 0) where `start` is NULL; otherwise read from the caller's tensor in device memory,
+ *           [2][mb_rows][mb_cols] of int16, channel 0 = x, channel 1 = y, in 1/8 PEL -- vp8hip_frames_motion_async's mv output as it
+ *           stands --, job i's at start + i * start_stride BYTES (both multiples of 2); each component is shifted >> 3
+ *           arithmetically, then clamped, sx to [cmin, cmax], sy to [rmin, rmax].  The value is data, never an address.  A start
+ *           tensor is refused on a context of more than 255 macroblocks a side, where 8 * a clamped start would leave int16.
+ *   PREDICTION at a vector v = (vy, vx) in 1/8 pel, both components even: with the base (by, bx) = (vy >> 3, vx >> 3)
+ *           (arithmetic shifts) and the offsets (oy, ox) = (vy & 7, vx & 7), and Y = 16 my + by, X = 16 mx + bx,
+ *             H(y, x) = (E(ref_fb)(Y + y, X + x) * (128 - 16 ox) + E(ref_fb)(Y + y, X + x + 1) * 16 ox + 64) >> 7, y in 0..16, x in 0..15,
+ *             P(y, x) = (H(y, x) * (128 - 16 oy) + H(y + 1, x) * 16 oy + 64) >> 7,                            y, x in 0..15:
+ *           vp8_sub_pixel_variance16x16_c's predictor with vp8_bilinear_filters[o] = {128 - 16 o, 16 o}, the horizontal pass
+ *           rounded before the vertical one.  Both passes are always made, also at offset 0 (the filter {128, 0}: the input comes
+ *           through).  Over the eleven candidates below the pixels touched lie in rows and columns s - 1 .. s + 16 of the block's
+ *           position at the start: 18 x 18.
+ *   DIST(v) = sse - (uint32)(((int64)sum * sum) >> 8), sse and sum the sums over y, x in 0..15 of the squared and of the signed
+ *           difference between S(fb)(16 my + y, 16 mx + x) and P(y, x): vp8_variance16x16_c, written in 64 bits as
+ *           VP8HIP_MOTION_VAR is.  The reference's `int` product overflows for |sum| > 46340; there the two differ, and this is the
+ *           one without the overflow.
+ *   COST(v) = ((cost[0][iy] + cost[1][ix]) * error_per_bit + 128) >> 8 with a cost table -- the reference's mv_err_cost --, else 0;
+ *           iy = clamp((vy - ry) >> 1, -R, R) + R and ix = clamp((vx - rx) >> 1, -R, R) + R (arithmetic shifts), (ry, rx) the
+ *           REFERENCE VECTOR the cost is counted from: (0, 0) where `ref` is NULL, otherwise read from a tensor of start's shape
+ *           and units (any int16; job i's at ref + i * ref_stride BYTES), and read only where there is a cost term.  The clamp to
+ *           +-R is this library's: the reference would read outside its table there.  p->cost is a HOST pointer to int32
+ *           [2][2 R + 1] (row costs, then column costs), entries 0..65535, with R = p->cost_range in 1..1023 (the reference's mv_max);
+ *           p->error_per_bit is 0..16383, so the product stays inside int32.  cost == NULL or error_per_bit == 0: no cost term, and
+ *           neither the table nor cost_range nor `ref` is read.  The table is copied at the call: the caller may change it on
+ *           return, and two calls queued back to back with different tables each see their own.
+ *   ORDER   the reference's.  With v0 = (8 sy, 8 sx) the best starts as v0, valued DIST + COST like every candidate.  Stage 1, with
+ *           h = 4 around c = v0: left c + (0, -h), right c + (0, +h), up c + (-h, 0), down c + (+h, 0) are valued in that order, and
+ *           each replaces the best only when STRICTLY below it; then one diagonal c + (up < down ? -h : +h, left < right ? -h : +h)
+ *           -- the reference's whichdir = (left < right ? 0 : 1) + (up < down ? 0 : 2): 0 up-left, 1 up-right, 2 down-left, 3
+ *           down-right; the comparisons are between the four values themselves, ties go right and down -- is valued and replaces
+ *           the best when strictly below it.  Stage 2 is the same with h = 2 around c = the best of stage 1.  p->precision == 2
+ *           stops after stage 1, p->precision == 4 runs both: six or eleven evaluations.  No bounds are applied to the sub-pixel
+ *           candidates (the reference's step applies none): a vector can end 6/8 pel past a UMV bound, and E is defined there.
+ *
+ * OUTPUTS, either of which may be NULL, not both; both dense per job on the macroblock grid:
+ *   mv      [2][mb_rows][mb_cols] of int16, job i at mv + i * mv_stride BYTES (both multiples of 2): channel 0 = x, channel 1 = y of
+ *           the best vector in 1/8 pel: comparable element for element with vp8hip_frames_side_async's I16 tensor and with
+ *           vp8hip_frames_motion_async's.  vp8hip_subpel_mv_size(ctx) = 4 * mb_rows * mb_cols (0 for a NULL or unconfigured ctx); it
+ *           is the size of the start and of the ref tensor too.
+ *   stats   [popcount(p->planes)][mb_rows][mb_cols] of uint32, job i at stats + i * stats_stride BYTES (both multiples of 4), the
+ *           planes in the order of their bits:
+ *             VP8HIP_SUBPEL_VAL     the best value, cost term included: what the reference's function returns;
+ *             VP8HIP_SUBPEL_VAR     DIST at the best vector (the reference's *distortion);
+ *             VP8HIP_SUBPEL_SSE     sse at the best vector (*sse1);
+ *             VP8HIP_SUBPEL_VAR0    DIST at v0: what the refinement started from.
+ *           vp8hip_subpel_stats_size(ctx, p) = 4 * popcount * mb_rows * mb_cols; 0 for a precision, an error_per_bit or planes the
+ *           call refuses (planes == 0 included) and for a NULL or unconfigured ctx.  p->planes is not read where stats is NULL,
+ *           except for unknown bits.
+ *
+ * The call is its neighbours: enqueued on the context's stream -- a later writer of a frame buffer runs behind it, an earlier
+ * vp8hip_decode is seen --; nothing is converted, no raster pool is made; no frame buffer is written; only bytes inside
+ * [mv + i * mv_stride, + size) and [stats + i * stats_stride, + size) are written.  Without a cost term it adds no device memory.
+ * With one, the table (up to 8188 bytes as uint16) goes to a copy the context owns: 8 KB of device memory, made by the first call
+ * that has a table and freed with the context -- the call's one allocation; the table travels there in the arguments of small
+ * launches ahead of the kernel, so nothing is synchronised.  It returns -2 with nothing enqueued for n < 1; an fb or ref_fb out of
+ * range (ref_fb < 0 included); a precision other than 2 and 4; an error_per_bit outside 0..16383; plane bits other than the four;
+ * stats with planes == 0; both outputs NULL; where the table is read, a cost_range outside 1..1023 or an entry outside 0..65535; a
+ * stride below the size; a pointer or stride not aligned (mv, start, ref: 2, stats: 4); an output, a start or a ref tensor that is
+ * not device memory of the context's device or that cannot hold n jobs; outputs that overlap each other or the start or the ref
+ * tensor (start and ref may be the same memory); a start tensor on more than 255 macroblocks a side. */
+#define VP8HIP_SUBPEL_VAL    1   /* bit order = plane order */
+#define VP8HIP_SUBPEL_VAR    2
+#define VP8HIP_SUBPEL_SSE    4
+#define VP8HIP_SUBPEL_VAR0   8
+typedef struct vp8hip_subpel {
+    int precision;             /* 2: the half-pixel stage alone; 4: both stages */
+    int error_per_bit;         /* 0..16383; 0: no cost term */
+    int cost_range;            /* R, 1..1023: a row of the table has 2 R + 1 entries; read with the table */
+    unsigned planes;           /* VP8HIP_SUBPEL_* bits of stats; may be 0 where stats is NULL */
+    const int32_t *cost;       /* host memory, int32 [2][2 * cost_range + 1], or NULL: no cost term */
+} vp8hip_subpel;
+size_t vp8hip_subpel_mv_size(const vp8hip_ctx *ctx);
+size_t vp8hip_subpel_stats_size(const vp8hip_ctx *ctx, const vp8hip_subpel *p);
+int  vp8hip_frames_subpel_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int n, const vp8hip_subpel *p, const void *start,
+                                size_t start_stride, const void *ref, size_t ref_stride, void *mv, size_t mv_stride, void *stats,
+                                size_t stats_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

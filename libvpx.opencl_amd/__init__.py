@@ -564,6 +564,23 @@ def motion_sizes(mb_cols, mb_rows, planes=("sad",)):
     return 4 * cells, 0 if not mask else 4 * bin(mask).count("1") * cells
 
 
+SUBPEL_PLANES = {"val": 1, "var": 2, "sse": 4, "var0": 8}      # VP8HIP_SUBPEL_*: bit order = plane order
+SUBPEL_MAX_COST_RANGE = 1023
+SUBPEL_MAX_ERROR_PER_BIT = 16383
+
+
+def subpel_sizes(mb_cols, mb_rows, planes=("val",)):
+    """(bytes of one job's mv tensor, bytes of its stats) of Vp8Hip.frames_subpel on a grid of mb_cols x mb_rows macroblocks (what
+    vp8hip_subpel_mv_size and vp8hip_subpel_stats_size give on a context of that size): int16 [2, mb_rows, mb_cols] -- the start and
+    the ref tensor's size too -- and uint32 [P, mb_rows, mb_cols]; the latter 0 for no plane or an unknown one, both 0 for an empty
+    grid"""
+    mask = _plane_mask(planes, SUBPEL_PLANES, True)
+    cells = int(mb_cols) * int(mb_rows)
+    if int(mb_cols) < 1 or int(mb_rows) < 1:
+        return 0, 0
+    return 4 * cells, 0 if not mask else 4 * bin(mask).count("1") * cells
+
+
 def ssim_mean(scores):
     """the scores [n, P, 2] of Vp8Hip.frames_ssim (a torch tensor or an array) -> float64 [n, P]: total / 2^32 / count, what
     vp8_ssim2 returns to within 2^-33 + N * 2^-52; NaN where the count is 0 (the reference's 0 / 0)"""
@@ -756,6 +773,11 @@ class MotionParams(ctypes.Structure):       # vp8hip_motion, include/vp8hip.h
     _fields_ = [("distance", c_int), ("sad_per_bit", c_int), ("planes", ctypes.c_uint), ("cost", ctypes.POINTER(ctypes.c_int32))]
 
 
+class SubpelParams(ctypes.Structure):       # vp8hip_subpel, include/vp8hip.h
+    _fields_ = [("precision", c_int), ("error_per_bit", c_int), ("cost_range", c_int), ("planes", ctypes.c_uint),
+                ("cost", ctypes.POINTER(ctypes.c_int32))]
+
+
 class VisParams(ctypes.Structure):         # vp8hip_vis, include/vp8hip.h
     _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
                 ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
@@ -866,6 +888,12 @@ def load_hip():
         L.vp8hip_motion_stats_size.restype = c_size_t
         L.vp8hip_frames_motion_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(MotionParams), c_void_p, c_size_t, c_void_p, c_size_t,
                                                  c_void_p, c_size_t]
+        L.vp8hip_subpel_mv_size.argtypes = [c_void_p]
+        L.vp8hip_subpel_mv_size.restype = c_size_t
+        L.vp8hip_subpel_stats_size.argtypes = [c_void_p, ctypes.POINTER(SubpelParams)]
+        L.vp8hip_subpel_stats_size.restype = c_size_t
+        L.vp8hip_frames_subpel_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(SubpelParams), c_void_p, c_size_t, c_void_p, c_size_t,
+                                                 c_void_p, c_size_t, c_void_p, c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1498,7 +1526,7 @@ class Vp8Hip:
 
     @staticmethod
     def _pair_jobs(who, jobs, planes, table, none_ok=False, ref_optional=False):
-        """-> (the HistJob array, how many jobs, the plane mask) of a call over picture pairs (frames_hist, frames_ssim, frames_motion);
+        """-> (the HistJob array, how many jobs, the plane mask) of a call over picture pairs (frames_hist, frames_ssim, frames_motion, frames_subpel);
         ValueError, in this order, for a job that is no (fb, ref_fb) -- ref_optional: or a bare frame buffer, and ref_fb may be
         None --, for an unknown plane or -- unless none_ok -- no plane, for no job and for a negative frame buffer"""
         items = []
@@ -1640,6 +1668,53 @@ class Vp8Hip:
         made = self._to_torch(who, outs, lambda vp, vs, sp=None, ss=0: self.L.vp8hip_frames_motion_async(self.h, arr, n, ctypes.byref(p), cptr, cstride,
                                                                                                          vp, vs, sp, ss),
                               "vp8hip_frames_motion_async")
+        return made[0], (made[1] if mask else None)
+
+    def frames_subpel(self, jobs, start=None, ref=None, cost=None, error_per_bit=0, precision=4, planes=("val",), out_mv=None, out_stats=None):
+        """Sub-pixel refinement of block motion between picture pairs on the context's device (vp8hip_frames_subpel_async): per
+        macroblock of fb the vector into ref_fb that the reference's vp8_find_best_sub_pixel_step (precision 4: half, then quarter
+        pel; precision 2: vp8_find_best_half_pixel_step) finds around a whole-pixel start, bit for bit.  `jobs`: a list of
+        (fb, ref_fb), any order, repeats allowed, fb == ref_fb legal.  Returns (mv, stats): mv a torch.int16 tensor
+        [n, 2, mb_rows, mb_cols], channel 0 = x, 1 = y, in 1/8 pel like frames_side's and frames_motion's vectors; stats a
+        torch.int32 tensor [n, P, mb_rows, mb_cols] holding uint32 bits, the planes of `planes` ("val": the best value, cost
+        included; "var" and "sse" at the best vector; "var0": the variance at the start; or the mask) in bit order -- None where
+        planes is empty.  `start`: a torch.int16 tensor [n, 2, mb_rows, mb_cols] in 1/8 pel on the device, each job dense --
+        frames_motion's mv as it stands: frames_subpel(jobs, start=frames_motion(jobs)[0]) is the reference's two steps --; None:
+        (0, 0).  `cost`: int32 [2, 2 R + 1], row costs then column costs (0..65535), R = 1..1023, with error_per_bit (0..16383) the
+        reference's mv_err_cost counted from `ref`, a tensor of start's shape and units (None: (0, 0)); cost None or error_per_bit
+        0: the plain variance.  Each frame buffer is read in the form it has; nothing is converted, and only a call with a cost
+        table adds device memory: 8 KB, once per context.  `out_mv`, `out_stats`: tensors of those shapes and types, each job
+        dense, stride(0) free.  Stream ordering, the `import torch` first rule and the remark on record_stream: as frames_scaled."""
+        who = "frames_subpel"
+        arr, n, mask = self._pair_jobs(who, jobs, planes, SUBPEL_PLANES, none_ok=True)
+        epb, prec = int(error_per_bit), int(precision)
+        if prec not in (2, 4) or not 0 <= epb <= SUBPEL_MAX_ERROR_PER_BIT:
+            raise ValueError(f"{who}: precision {precision} (2 or 4), error_per_bit {error_per_bit} (0..{SUBPEL_MAX_ERROR_PER_BIT})")
+        if out_stats is not None and not mask:
+            raise ValueError(f"{who}: out_stats without planes")
+        table, rng = None, 0
+        if cost is not None:
+            table = np.ascontiguousarray(cost, dtype=np.int32)
+            rng = (table.shape[1] - 1) // 2 if table.ndim == 2 else 0
+            if table.ndim != 2 or table.shape != (2, 2 * rng + 1) or not 1 <= rng <= SUBPEL_MAX_COST_RANGE or (table < 0).any() or (table > 65535).any():
+                raise ValueError(f"{who}: cost is int32 [2, 2 R + 1] of 0..65535, R = 1..{SUBPEL_MAX_COST_RANGE}")
+        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
+        p = SubpelParams(prec, epb, rng, mask, None if table is None else table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        ins = []
+        for name, t in (("start", start), ("ref", ref)):
+            if t is None:
+                ins += [None, 0]
+                continue
+            torch, dev = self._torch_device(who)
+            if not self._dense(t, torch.int16, (n, 2, rows, cols), dev):
+                raise ValueError(f"{who}: {name} must be an int16 tensor {[n, 2, rows, cols]}, each job dense, on {dev}")
+            ins += [c_void_p(t.data_ptr()), t.stride(0) * 2]
+        outs = [("out_mv", out_mv, "int16", (n, 2, rows, cols))]
+        if mask:
+            outs.append(("out_stats", out_stats, "int32", (n, bin(mask).count("1"), rows, cols)))
+        made = self._to_torch(who, outs, lambda vp, vs, sp=None, ss=0: self.L.vp8hip_frames_subpel_async(self.h, arr, n, ctypes.byref(p), *ins, vp, vs,
+                                                                                                         sp, ss),
+                              "vp8hip_frames_subpel_async")
         return made[0], (made[1] if mask else None)
 
     def ssim_share(self, n, planes=("y", "u", "v")):

@@ -236,7 +236,8 @@ struct InvertLaunch {
 };
 
 // Where the planes of the context's frame buffers lie, for the kernels that read pictures and make no tensor of them
-// (vp8_frame_read.hip.h): what a launch of the byte histograms, of the structural similarity and of the motion search begins with
+// (vp8_frame_read.hip.h): what a launch of the byte histograms, of the structural similarity, of the motion search and of its
+// sub-pixel refinement begins with
 struct FramePlanes {
     int dw, dh;                   // the display size
     int mb_cols, mb_rows;
@@ -325,12 +326,39 @@ struct MotionLaunch : FramePlanes {  // (dw, dh are not read: the search is over
     unsigned short cost[2][2 * MOTION_MAX_D + 2];    // [0]: by row, [1]: by column, index = candidate - centre + d
     HistFrameJob j[MOTION_MAX_JOBS];    // (ref is never -1)
 };
-// the three launches' layout in the kernels' arguments: the base takes 36 bytes and the first member lies right behind it (offsetof
+
+// One launch of vp8hip_frames_subpel_async (vp8_subpel.hip), as the host's plan (vp8hip_subpel.hip) left it.  A wave owns one
+// macroblock of one job, SUBPEL_WAVES of them share a workgroup.  The cost table is not here: it lies in the context's device copy,
+// sent there in pieces that come with launches of vp8_subpel_table_kernel
+#define SUBPEL_MAX_JOBS 256       // jobs per launch (kernel arguments: 8 bytes each)
+#define SUBPEL_WAVES 4            // macroblocks (waves) a workgroup
+#define SUBPEL_MAX_RANGE 1023     // the largest cost_range: the reference's mv_max
+#define SUBPEL_TABLE_ENTRIES (2 * (2 * SUBPEL_MAX_RANGE + 1))     // of the context's copy: 8188 bytes
+#define SUBPEL_TABLE_PIECE 1792   // entries a launch of vp8_subpel_table_kernel carries
+#define SUBPEL_VAL 1              // VP8HIP_SUBPEL_*
+#define SUBPEL_VAR 2
+#define SUBPEL_SSE 4
+#define SUBPEL_VAR0 8
+struct SubpelLaunch : FramePlanes {  // (dw, dh are not read: the blocks are those of the coded area)
+    int precision;                // 2: the half-pixel stage alone; 4: both stages
+    int epb;                      // error_per_bit; 0: no cost term (the table and the reference vectors are not read)
+    int R;                        // cost_range: a row of the table has 2 R + 1 entries
+    unsigned planes;              // SUBPEL_* bits of the stats; 0: none
+    int mv, start, ref;           // 1: vectors are written / starts are read / reference vectors are read
+    HistFrameJob j[SUBPEL_MAX_JOBS];    // (ref is never -1)
+};
+struct SubpelTablePiece {
+    int first, n;                 // entries first .. first + n - 1 of the copy
+    unsigned short v[SUBPEL_TABLE_PIECE];
+};
+// the four launches' layout in the kernels' arguments: the base takes 36 bytes and the first member lies right behind it (offsetof
 // past a base of plain ints is what the warning calls conditionally supported: it is supported here)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winvalid-offsetof"
 static_assert(sizeof(FramePlanes) == 36 && sizeof(HistFrameLaunch) == 2092 && sizeof(SsimLaunch) == 2176 && sizeof(MotionLaunch) == 2640, "");
+static_assert(sizeof(SubpelLaunch) == 2112 && sizeof(SubpelTablePiece) == 3592, "");
 static_assert(offsetof(HistFrameLaunch, S) == 36 && offsetof(SsimLaunch, S) == 36 && offsetof(MotionLaunch, d) == 36, "");
+static_assert(offsetof(SubpelLaunch, precision) == 36, "");
 #pragma clang diagnostic pop
 
 #define WAVE 64

@@ -1,9 +1,9 @@
 // The display-size planes of a frame buffer in whichever form it has, for the kernels that read pictures and make no tensor of them
-// (vp8_hist.hip, vp8_ssim.hip, vp8_motion.hip): the frame of a job (frame_of), a piece of sixteen columns of a row (hist_read16), one
+// (vp8_hist.hip, vp8_ssim.hip, vp8_motion.hip, vp8_subpel.hip): the frame of a job (frame_of), a piece of sixteen columns of a row (hist_read16), one
 // aligned dword of four (frame_read4) and one of the coded luma area extended by edge replication (frame_edge4), from
 // the raster form directly, from the tiles through ScaleSrc<SCALE_FROM_TILES> (vp8_scale_src.hip.h: the one place that knows the
 // tiles; frame_tiles: the one place here that describes them to it); a frame buffer never written reads as zeros and no address is
-// formed.  FramePlanes (vp8_common.hip.h: what the three launches begin with) says where the planes lie.
+// formed.  FramePlanes (vp8_common.hip.h: what the four launches begin with) says where the planes lie.
 #pragma once
 #include "vp8_scale_src.hip.h"
 

@@ -16,8 +16,9 @@
 //                       byte histograms of pictures, slots and pool entries (vp8_hist.hip)
 //   vp8hip_ssim.hip     vp8hip_frames_ssim_async: the structural similarity of picture pairs (vp8_ssim.hip)
 //   vp8hip_motion.hip   vp8hip_frames_motion_async: full-search block motion between picture pairs (vp8_motion.hip)
+//   vp8hip_subpel.hip   vp8hip_frames_subpel_async: the sub-pixel refinement of such vectors (vp8_subpel.hip)
 //   vp8hip_handover.hip what those calls share: the checks of their lists, of picture pairs and of destinations, and the planes'
-//                       geometry for the three calls that read picture pairs (hist, ssim, motion)
+//                       geometry for the four calls that read picture pairs (hist, ssim, motion, subpel)
 // and vp8hip_res.hip.h: the owning types of the context's buffers, events and streams.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -161,6 +162,7 @@ struct vp8hip_ctx {
     bool ent_tables_loaded = false, ent_parts_off = false; int ent_lpw = 0;
     int ent_resident[3] = {};      // waves of vp8_entropy_kernel the device holds at once with 64 / 32 / 16 lanes carrying a frame (LDS)
     DevBuf<unsigned int> d_sched;  // vp8_keyframe_kernel's role / work counters
+    DevBuf<unsigned short> d_subpel_cost;            // vp8hip_frames_subpel_async: the cost table of the call (SUBPEL_TABLE_ENTRIES, made with the first table)
 };
 
 int vp8hip_fail(vp8hip_ctx *c, int code, const char *fmt, ...);
