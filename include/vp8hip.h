@@ -1074,6 +1074,80 @@ size_t vp8hip_subpel_stats_size(const vp8hip_ctx *ctx, const vp8hip_subpel *p);
 int  vp8hip_frames_subpel_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int n, const vp8hip_subpel *p, const void *start,
                                 size_t start_stride, const void *ref, size_t ref_stride, void *mv, size_t mv_stride, void *stats,
                                 size_t stats_stride);
+/* MOTION-COMPENSATED TEMPORAL FILTER of pictures (ARNR).  The two calls above end in vectors and error figures; this one makes a
+ * picture of them: the reference's alt-ref noise-reduction filter (vp8/encoder/temporal_filter.c), which blends the motion-
+ * compensated predictions from neighbouring pictures into a centre picture pixel by pixel, trusting a prediction less the further
+ * it lies from the centre's pixel -- vp8_temporal_filter_predictors_mb_c followed by vp8_temporal_filter_apply_c per source, then
+ * the normalisation by cpi->fixed_divide, bit for bit, for all three planes.
+ *
+ * PAIRS AND JOBS.  `pairs` is the very list a caller gave vp8hip_frames_motion_async / _subpel_async: pair k = (fb, ref_fb), ref_fb
+ * the SOURCE picture.  Job i filters the centre picture jobs[i].fb over the pairs first .. first + count - 1, in that order; count is
+ * 1..15 (the reference's arnr_max_frames); every pair in that range must have fb == jobs[i].fb.  Jobs may share or repeat pairs.  The
+ * centre itself takes part only where the caller lists the pair (fb, fb) (the reference always has it, at vector (0, 0) and error 0).
+ *
+ * INPUTS, in device memory, either of which may be NULL:
+ *   mv      pair k's tensor [2][mb_rows][mb_cols] of int16 at mv + k * mv_stride BYTES (both multiples of 2), channel 0 = x,
+ *           channel 1 = y, in 1/8 pel: vp8hip_frames_subpel_async's or vp8hip_frames_motion_async's output as it stands (the
+ *           reference's d->bmi.mv).  Any int16 value is legal, odd ones included; a vector is data, never an address.  NULL: (0, 0)
+ *           everywhere, the reference with ALT_REF_MC_ENABLED off.
+ *   err     pair k's plane [mb_rows][mb_cols] of uint32 at err + k * err_stride BYTES (both multiples of 4):
+ *           vp8hip_frames_subpel_async's VAL plane (the reference's bestsme).  The WEIGHT of source k for a macroblock is
+ *           W = err < thresh_low ? 2 : err < thresh_high ? 1 : 0, compared UNSIGNED; the reference compares an int, and the two agree
+ *           for every err below 2^31.  NULL: W = 2 everywhere.  A source whose W is 0 for a macroblock adds nothing to it.
+ *
+ * PICTURES.  S(F), E(F), A, B and how a frame buffer is read are as for vp8hip_frames_motion_async, now for all three planes: chroma's
+ * coded area is A/2 x B/2, extended by coordinate clamps as luma is.
+ *
+ * Per macroblock (my, mx), source k with vector (vy, vx) and weight W != 0:
+ *   LUMA    the prediction P is 16x16, its base (Y, X) = (16 my + (vy >> 3), 16 mx + (vx >> 3)) and its offsets (oy, ox) =
+ *           (vy & 7, vx & 7), arithmetic shifts.  Where both offsets are 0, P(y, x) = E(ref_fb)(Y + y, X + x) (vp8_copy_mem16x16).
+ *           Otherwise, with VP8HIP_TFILTER_SIXTAP, vp8_sixtap_predict16x16_c: with f = vp8_sub_pel_filters[ox],
+ *             H(y, x) = clamp255((sum over t in 0..5 of E(ref_fb)(Y + y, X + x + t - 2) * f[t] + 64) >> 7), y in -2..18, x in 0..15,
+ *           and with f = vp8_sub_pel_filters[oy], P(y, x) = clamp255((sum over t of H(y + t - 2, x) * f[t] + 64) >> 7): the
+ *           horizontal pass rounded and clamped to bytes before the vertical one, both always made, the pass-through filter
+ *           {0, 0, 128, 0, 0, 0} of offset 0 included.  With VP8HIP_TFILTER_BILINEAR, vp8_bilinear_predict16x16_c: 17 rows
+ *           H(y, x) = (E(Y + y, X + x) * (128 - 16 ox) + E(Y + y, X + x + 1) * 16 ox + 64) >> 7, then
+ *           P(y, x) = (H(y, x) * (128 - 16 oy) + H(y + 1, x) * 16 oy + 64) >> 7 (vp8_bilinear_filters).
+ *   CHROMA  the vector is (cy, cx) = (vy >> 1, vx >> 1), arithmetic: the temporal filter's own rule -- no full-pixel rounding, and
+ *           all eight phases occur.  U and V are 8x8, base (8 my + (cy >> 3), 8 mx + (cx >> 3)), offsets (cy & 7, cx & 7), through
+ *           the 8x8 functions in the same way (13 or 9 rows); whether they are copied is decided by the chroma offsets.
+ *   BLEND   per pixel of the three blocks, with s the centre's pixel from S(fb) and q the prediction's:
+ *             m = ((s - q)^2 * 3 + r) >> strength,  r = 1 << (strength - 1), and r = 0 at strength 0
+ *             m = (16 - min(m, 16)) * W;   count += m;   accumulator += m * q.
+ *           At strength 0 the reference shifts by -1, which C leaves undefined; r = 0 there (m = 3 (s - q)^2) is THIS LIBRARY'S
+ *           definition.
+ * After the last source: pixel = ((accumulator + (count >> 1)) * (count ? 0x80000 / count : 0)) >> 19 in uint32, its low byte --
+ * cpi->fixed_divide.  A count of 0 gives 0.  count <= 15 * 32 = 480, inside the reference's table of 512.
+ *
+ * OUTPUTS, in the caller's device memory; either may be NULL, not both:
+ *   dst     job i's picture at dst + i * dst_stride BYTES, packed I420 at the DISPLAY size, vp8hip_i420_size(w, h) bytes:
+ *           vp8hip_frames_scale_async's layout at the native size.  The coded area's right and bottom surplus is computed but not
+ *           stored.
+ *   cnt     the same geometry in uint16 at cnt + i * cnt_stride BYTES (both multiples of 2): the per-pixel count, the support the
+ *           pixel got; 32 per fully trusted source.  vp8hip_tfilter_count_size(ctx) = 2 * vp8hip_i420_size(w, h) (0 for a NULL or
+ *           unconfigured ctx).
+ *
+ * The call is its neighbours: enqueued on the context's stream -- a later writer of a frame buffer runs behind it, an earlier
+ * vp8hip_decode is seen --; nothing is converted, no raster pool is made and no device memory is added; no frame buffer is written;
+ * only bytes inside [dst + i * dst_stride, + size) and [cnt + i * cnt_stride, + size) are written; no atomics: the same bits in every
+ * run.  It returns -2 with nothing enqueued for n < 1 or npairs < 1; an fb or ref_fb out of range; a count outside 1..15; a range
+ * outside `pairs`; a pair whose fb is not the job's; a strength outside 0..6; an unknown filter; thresh_high < thresh_low; both
+ * outputs NULL; a stride below the size; a pointer or stride not aligned (mv: 2, err: 4, cnt: 2); an output, mv or err that is not
+ * device memory of the context's device or that cannot hold its n (outputs) or npairs (inputs) items; outputs that overlap each
+ * other or an input.  Writing the result back into a frame buffer, and RGB of the result, are not part of it. */
+#define VP8HIP_TFILTER_SIXTAP   0
+#define VP8HIP_TFILTER_BILINEAR 1
+typedef struct vp8hip_tfilter {
+    int strength;              /* 0..6: the reference's arnr_strength */
+    int filter;                /* VP8HIP_TFILTER_SIXTAP / _BILINEAR */
+    unsigned thresh_low;       /* the reference's THRESH_LOW, 10000 */
+    unsigned thresh_high;      /* the reference's THRESH_HIGH, 20000; >= thresh_low */
+} vp8hip_tfilter;
+typedef struct vp8hip_tfilter_job { int32_t fb, first, count; } vp8hip_tfilter_job;
+size_t vp8hip_tfilter_count_size(const vp8hip_ctx *ctx);
+int  vp8hip_frames_tfilter_async(vp8hip_ctx *ctx, const vp8hip_tfilter_job *jobs, int n, const vp8hip_hist_job *pairs, int npairs,
+                                 const vp8hip_tfilter *p, const void *mv, size_t mv_stride, const void *err, size_t err_stride,
+                                 void *dst, size_t dst_stride, void *cnt, size_t cnt_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

@@ -581,6 +581,19 @@ def subpel_sizes(mb_cols, mb_rows, planes=("val",)):
     return 4 * cells, 0 if not mask else 4 * bin(mask).count("1") * cells
 
 
+TFILTER_FILTERS = {"sixtap": 0, "bilinear": 1}                # VP8HIP_TFILTER_SIXTAP, _BILINEAR
+TFILTER_MAX_COUNT = 15                                        # sources a job: the reference's arnr_max_frames
+
+
+def tfilter_sizes(w, h):
+    """(bytes of one job's picture, bytes of its count plane) of Vp8Hip.frames_tfilter at the display size w x h: packed I420 in
+    uint8 (vp8hip_i420_size) and the same geometry in uint16 (vp8hip_tfilter_count_size); both 0 for a size outside 1..16383"""
+    if not (1 <= int(w) <= 16383 and 1 <= int(h) <= 16383):
+        return 0, 0
+    size = i420_size(int(w), int(h))
+    return size, 2 * size
+
+
 def ssim_mean(scores):
     """the scores [n, P, 2] of Vp8Hip.frames_ssim (a torch tensor or an array) -> float64 [n, P]: total / 2^32 / count, what
     vp8_ssim2 returns to within 2^-33 + N * 2^-52; NaN where the count is 0 (the reference's 0 / 0)"""
@@ -778,6 +791,14 @@ class SubpelParams(ctypes.Structure):       # vp8hip_subpel, include/vp8hip.h
                 ("cost", ctypes.POINTER(ctypes.c_int32))]
 
 
+class TfilterParams(ctypes.Structure):      # vp8hip_tfilter, include/vp8hip.h
+    _fields_ = [("strength", c_int), ("filter", c_int), ("thresh_low", ctypes.c_uint), ("thresh_high", ctypes.c_uint)]
+
+
+class TfilterJob(ctypes.Structure):         # vp8hip_tfilter_job, include/vp8hip.h
+    _fields_ = [("fb", ctypes.c_int32), ("first", ctypes.c_int32), ("count", ctypes.c_int32)]
+
+
 class VisParams(ctypes.Structure):         # vp8hip_vis, include/vp8hip.h
     _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
                 ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
@@ -894,6 +915,10 @@ def load_hip():
         L.vp8hip_subpel_stats_size.restype = c_size_t
         L.vp8hip_frames_subpel_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(SubpelParams), c_void_p, c_size_t, c_void_p, c_size_t,
                                                  c_void_p, c_size_t, c_void_p, c_size_t]
+        L.vp8hip_tfilter_count_size.argtypes = [c_void_p]
+        L.vp8hip_tfilter_count_size.restype = c_size_t
+        L.vp8hip_frames_tfilter_async.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(TfilterParams), c_void_p, c_size_t,
+                                                  c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1526,7 +1551,8 @@ class Vp8Hip:
 
     @staticmethod
     def _pair_jobs(who, jobs, planes, table, none_ok=False, ref_optional=False):
-        """-> (the HistJob array, how many jobs, the plane mask) of a call over picture pairs (frames_hist, frames_ssim, frames_motion, frames_subpel);
+        """-> (the HistJob array, how many jobs, the plane mask) of a call over picture pairs (frames_hist, frames_ssim, frames_motion, frames_subpel,
+        frames_tfilter);
         ValueError, in this order, for a job that is no (fb, ref_fb) -- ref_optional: or a bare frame buffer, and ref_fb may be
         None --, for an unknown plane or -- unless none_ok -- no plane, for no job and for a negative frame buffer"""
         items = []
@@ -1716,6 +1742,71 @@ class Vp8Hip:
                                                                                                          sp, ss),
                               "vp8hip_frames_subpel_async")
         return made[0], (made[1] if mask else None)
+
+    def frames_tfilter(self, jobs, pairs, mv=None, err=None, strength=3, filter="sixtap", thresh=(10000, 20000), want_count=False, out=None,
+                       out_count=None):
+        """The reference's motion-compensated temporal filter (ARNR) of pictures on the context's device
+        (vp8hip_frames_tfilter_async): each centre picture blended with the motion-compensated predictions from its sources, pixel by
+        pixel, a prediction trusted less the further it lies from the centre's pixel, bit for bit with
+        vp8/encoder/temporal_filter.c.  `pairs`: the list of (fb, ref_fb) given to frames_motion / frames_subpel, ref_fb the source.
+        `jobs`: a list of (fb, first, count): the centre fb over pairs first .. first + count - 1 (count 1..15), all of them pairs
+        of fb; jobs may share pairs; the centre takes part where (fb, fb) is listed.  `mv`: frames_subpel's (or frames_motion's)
+        torch.int16 tensor [npairs, 2, mb_rows, mb_cols] as it stands, None: (0, 0).  `err`: a torch.int32 tensor
+        [npairs, mb_rows, mb_cols] holding uint32 bits, or the [npairs, 1, mb_rows, mb_cols] stats of frames_subpel(planes=("val",))
+        as it stands; a source weighs 2 below thresh[0], 1 below thresh[1], else 0, per macroblock; None: 2.  strength: 0..6;
+        filter: "sixtap" or "bilinear".  Returns a torch.uint8 tensor [n, i420_size(width, height)] -- frames_scaled's layout at the
+        display size: split_i420 gives the planes -- and with want_count (or out_count) also the per-pixel count, a torch.int16
+        tensor of the same shape holding uint16 bits (32 per fully trusted source).  Each frame buffer is read in the form it has;
+        nothing is converted or allocated.  `out` as for frames_scaled (stride(1) == 1), `out_count` likewise.  Stream ordering, the
+        `import torch` first rule and the remark on record_stream: as frames_scaled."""
+        who = "frames_tfilter"
+        pairs = list(pairs)
+        parr, npairs, _ = self._pair_jobs(who, pairs, 0, {}, none_ok=True)
+        centres = [int(pair[0]) for pair in pairs]
+        items = []
+        for j in jobs:
+            if not isinstance(j, (tuple, list)) or len(j) != 3:
+                raise ValueError(f"{who}: jobs are (fb, first, count)")
+            items.append(tuple(int(v) for v in j))
+        if not items:
+            raise ValueError(f"{who}: no jobs")
+        for fb, first, count in items:
+            if fb < 0 or not 1 <= count <= TFILTER_MAX_COUNT or first < 0 or first + count > npairs:
+                raise ValueError(f"{who}: job {(fb, first, count)}: count 1..{TFILTER_MAX_COUNT}, pairs inside the list's {npairs}")
+            if any(c != fb for c in centres[first:first + count]):
+                raise ValueError(f"{who}: job {(fb, first, count)} takes a pair of another frame buffer")
+        n = len(items)
+        if isinstance(filter, str) and filter not in TFILTER_FILTERS:
+            raise ValueError(f"{who}: filter {filter!r} ({', '.join(TFILTER_FILTERS)})")
+        flt = TFILTER_FILTERS[filter] if isinstance(filter, str) else int(filter)
+        lo, hi = (int(t) for t in thresh)
+        if not 0 <= int(strength) <= 6 or flt not in (0, 1) or not 0 <= lo <= hi < 1 << 32:
+            raise ValueError(f"{who}: strength {strength} (0..6), filter {filter!r}, thresh {thresh!r} (0 <= low <= high < 2^32)")
+        p = TfilterParams(int(strength), flt, lo, hi)
+        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
+        ins = []
+        for name, t, kind, shapes in (("mv", mv, "int16", [(npairs, 2, rows, cols)]),
+                                      ("err", err, "int32", [(npairs, rows, cols), (npairs, 1, rows, cols)])):
+            if t is None:
+                ins += [None, 0]
+                continue
+            torch, dev = self._torch_device(who)
+            if not any(self._dense(t, getattr(torch, kind), shape, dev) for shape in shapes):
+                raise ValueError(f"{who}: {name} must be an {kind} tensor {' or '.join(str(list(sh)) for sh in shapes)}, each pair dense, on {dev}")
+            ins += [c_void_p(t.data_ptr()), t.stride(0) * t.element_size()]
+        size = int(self.L.vp8hip_i420_size(self.width, self.height))
+        counted = bool(want_count) or out_count is not None
+
+        def ok(out, dtype, shape, dev):
+            return out.dtype == dtype and out.dim() == 2 and tuple(out.shape) == tuple(shape) and out.stride(1) == 1 and out.device == dev
+        outs = [("out", out, "uint8", (n, size))]
+        if counted:
+            outs.append(("out_count", out_count, "int16", (n, size)))
+        jarr = (TfilterJob * n)(*items)
+        made = self._to_torch(who, outs, lambda dp, ds, cp=None, cs=0: self.L.vp8hip_frames_tfilter_async(self.h, jarr, n, parr, npairs, ctypes.byref(p),
+                                                                                                         *ins, dp, ds, cp, cs),
+                              "vp8hip_frames_tfilter_async", ok, "with stride(1) == 1")
+        return tuple(made) if counted else made[0]
 
     def ssim_share(self, n, planes=("y", "u", "v")):
         """how many workgroups share each job of a frames_ssim call of n jobs over `planes` (vp8hip_ssim_share): 1 -- a workgroup

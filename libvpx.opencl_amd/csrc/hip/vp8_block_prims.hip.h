@@ -105,15 +105,12 @@ __device__ __forceinline__ u32 sixtap_finish(v2u16 a01, v2u16 a23)     // two bi
     const v2u16 r23 = __builtin_elementwise_min(__builtin_elementwise_sub_sat(a23 >> 7, c64), c255);
     return __builtin_amdgcn_perm(__builtin_bit_cast(u32, r23), __builtin_bit_cast(u32, r01), 0x06040200u);
 }
-// first pass for four output pixels: s points at the pixel two left of the first one (nine pixels are read, as three
-// aligned dwords shifted into place)
-__device__ __forceinline__ u32 sixtap_hrow(g_cu8p s, const SixTaps &tx)
+// first pass for four output pixels from the three aligned dwords d0, d1, d2 that hold the nine pixels read: byte sh (0..3) of d0
+// is the pixel two left of the first one
+__device__ __forceinline__ u32 sixtap_hrow3(u32 d0, u32 d1, u32 d2, u32 sh, const SixTaps &tx)
 {
     auto asv = [](u32 v) { return __builtin_bit_cast(v2u16, v); };
     auto perm = [](u32 hi, u32 lo, u32 sel) { return __builtin_amdgcn_perm(hi, lo, sel); };
-    const u32 sh = (u32)(unsigned long)s & 3u;
-    g_cu32p rp = (g_cu32p)(s - sh);
-    const u32 d0 = rp[0], d1 = rp[1], d2 = rp[2];
     const u32 w0 = __builtin_amdgcn_alignbyte(d1, d0, sh), w1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
     const u32 w2 = __builtin_amdgcn_alignbyte(0u, d2, sh);
     // P[k] = pixels (k, k+1) of the row, one per 16-bit lane
@@ -125,6 +122,18 @@ __device__ __forceinline__ u32 sixtap_hrow(g_cu8p s, const SixTaps &tx)
 #pragma unroll
     for (int k = 0; k < 6; k++) { a01 += P[k] * tx.t[k]; a23 += P[k + 2] * tx.t[k]; }
     return sixtap_finish(a01, a23);
+}
+// ... from global memory: s points at the pixel two left of the first one (three aligned dwords are read and shifted into place)
+__device__ __forceinline__ u32 sixtap_hrow(g_cu8p s, const SixTaps &tx)
+{
+    const u32 sh = (u32)(unsigned long)s & 3u;
+    g_cu32p rp = (g_cu32p)(s - sh);
+    return sixtap_hrow3(rp[0], rp[1], rp[2], sh, tx);
+}
+// ... from a row staged in LDS (or anywhere else a plain pointer reaches): row[0] holds the pixel two left of the first one as byte sh
+__device__ __forceinline__ u32 sixtap_hrow_staged(const u32 *row, u32 sh, const SixTaps &tx)
+{
+    return sixtap_hrow3(row[0], row[1], row[2], sh, tx);
 }
 // second pass: H[k] = four first-pass pixels (bytes) of source row k - 2
 __device__ __forceinline__ u32 sixtap_vcol(const u32 H[6], const SixTaps &ty)

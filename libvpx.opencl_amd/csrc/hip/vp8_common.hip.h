@@ -351,7 +351,28 @@ struct SubpelTablePiece {
     int first, n;                 // entries first .. first + n - 1 of the copy
     unsigned short v[SUBPEL_TABLE_PIECE];
 };
-// the four launches' layout in the kernels' arguments: the base takes 36 bytes and the first member lies right behind it (offsetof
+// One launch of vp8hip_frames_tfilter_async (vp8_tfilter.hip), as the host's plan (vp8hip_tfilter.hip) left it.  A workgroup owns one
+// macroblock of one job and loops over the job's sources; a job's sources lie in ref[roff .. roff + count - 1], copied there pair
+// by pair (jobs that share pairs each have their own copy), so a launch takes jobs until either array is full
+#define TFILTER_MAX_JOBS 96       // jobs per launch (kernel arguments: 16 bytes each)
+#define TFILTER_MAX_REFS 480      // sources per launch (4 bytes each): 32 jobs of 15 at least
+#define TFILTER_MAX_COUNT 15      // sources a job: the reference's arnr_max_frames
+#define TFILTER_THREADS 128       // lanes 0..63: the luma block, four pixels each; 64..95: U and V; all of them stage and filter rows
+struct TfilterJob {
+    int fb;                       // the centre: frame buffer << 2 | form, as of the call
+    int first;                    // its first pair in the caller's list: where its vectors and errors lie
+    int count;                    // 1..TFILTER_MAX_COUNT
+    int roff;                     // its first source in TfilterLaunch::ref
+};
+struct TfilterLaunch : FramePlanes {
+    int strength;                 // 0..6
+    int filter;                   // 0: six-tap, 1: bilinear
+    unsigned lo, hi;              // the thresholds of the weight: err < lo: 2, err < hi: 1, else 0
+    int mv, err, dst, cnt;        // 1: vectors are read / errors are read / pictures are written / counts are written
+    TfilterJob j[TFILTER_MAX_JOBS];
+    int ref[TFILTER_MAX_REFS];    // the sources: frame buffer << 2 | form
+};
+// the five launches' layout in the kernels' arguments: the base takes 36 bytes and the first member lies right behind it (offsetof
 // past a base of plain ints is what the warning calls conditionally supported: it is supported here)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winvalid-offsetof"
@@ -359,6 +380,7 @@ static_assert(sizeof(FramePlanes) == 36 && sizeof(HistFrameLaunch) == 2092 && si
 static_assert(sizeof(SubpelLaunch) == 2112 && sizeof(SubpelTablePiece) == 3592, "");
 static_assert(offsetof(HistFrameLaunch, S) == 36 && offsetof(SsimLaunch, S) == 36 && offsetof(MotionLaunch, d) == 36, "");
 static_assert(offsetof(SubpelLaunch, precision) == 36, "");
+static_assert(sizeof(TfilterLaunch) == 3524 && offsetof(TfilterLaunch, strength) == 36, "");
 #pragma clang diagnostic pop
 
 #define WAVE 64

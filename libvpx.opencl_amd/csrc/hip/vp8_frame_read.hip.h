@@ -1,6 +1,6 @@
 // The display-size planes of a frame buffer in whichever form it has, for the kernels that read pictures and make no tensor of them
-// (vp8_hist.hip, vp8_ssim.hip, vp8_motion.hip, vp8_subpel.hip): the frame of a job (frame_of), a piece of sixteen columns of a row (hist_read16), one
-// aligned dword of four (frame_read4) and one of the coded luma area extended by edge replication (frame_edge4), from
+// (vp8_hist.hip, vp8_ssim.hip, vp8_motion.hip, vp8_subpel.hip, vp8_tfilter.hip): the frame of a job (frame_of), a piece of sixteen columns of a row
+// (hist_read16), one aligned dword of four (frame_read4) and one of a plane's coded area extended by edge replication (frame_edge4), from
 // the raster form directly, from the tiles through ScaleSrc<SCALE_FROM_TILES> (vp8_scale_src.hip.h: the one place that knows the
 // tiles; frame_tiles: the one place here that describes them to it); a frame buffer never written reads as zeros and no address is
 // formed.  FramePlanes (vp8_common.hip.h: what the four launches begin with) says where the planes lie.
@@ -56,19 +56,22 @@ __device__ __forceinline__ unsigned frame_read4(const HistFrame &F, const FrameP
     return 0u;
 }
 
-// columns x .. x + 3 of row y of the luma plane's CODED area (16 * mb_cols x 16 * mb_rows) extended by edge replication, for any row
-// y and any multiple of 4 x, low byte first: E(y, x) = S(clamp(y), clamp(x)), by coordinate clamps -- the raster form's borders are
-// never read, both forms give the same bytes.  The coded width is a multiple of 16, so an aligned dword lies wholly inside the
-// area or wholly outside it (then: the row's first or last byte, four times).  FORM is F's (SCALE_FROM_RASTER or _TILES: the
-// caller branches once, not per dword); one load whatever x is, and selects: nothing here diverges
-template <int FORM>
+// columns x .. x + 3 of row y of plane PL's CODED area (luma: 16 * mb_cols x 16 * mb_rows, chroma: half that each way) extended by
+// edge replication, for any row y and any multiple of 4 x, low byte first: E(y, x) = S(clamp(y), clamp(x)), by coordinate clamps --
+// the raster form's borders are never read, both forms give the same bytes.  The coded width is a multiple of 16 (chroma: of 8), so
+// an aligned dword lies wholly inside the area or wholly outside it (then: the row's first or last byte, four times).  FORM is F's
+// (SCALE_FROM_RASTER or _TILES: the caller branches once, not per dword); one load whatever x is, and selects: nothing here diverges
+template <int FORM, int PL = 0>
 __device__ __forceinline__ unsigned frame_edge4(const HistFrame &F, const FramePlanes &L, int x, int y)
 {
-    const int aw = 16 * L.mb_cols, ah = 16 * L.mb_rows;
+    const int aw = (PL ? 8 : 16) * L.mb_cols, ah = (PL ? 8 : 16) * L.mb_rows;
     const int xe = min(max(x, 0), aw - 4);
     y = min(max(y, 0), ah - 1);
     unsigned v;
-    if constexpr (FORM == SCALE_FROM_RASTER) v = *(g_cu32p)((g_cu8p)F.raster + L.y_off + (long)y * L.y_stride + xe);
-    else v = frame_tiles<0>(F, L).template atN<4>(xe, y);
+    if constexpr (FORM == SCALE_FROM_RASTER) {
+        const int off = PL == 0 ? L.y_off : PL == 1 ? L.u_off : L.v_off;
+        v = *(g_cu32p)((g_cu8p)F.raster + off + (long)y * (PL ? L.uv_stride : L.y_stride) + xe);
+    } else
+        v = frame_tiles<PL>(F, L).template atN<4>(xe, y);
     return x < 0 ? (v & 0xffu) * 0x01010101u : x >= aw ? (v >> 24) * 0x01010101u : v;
 }
