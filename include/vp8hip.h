@@ -1148,6 +1148,136 @@ size_t vp8hip_tfilter_count_size(const vp8hip_ctx *ctx);
 int  vp8hip_frames_tfilter_async(vp8hip_ctx *ctx, const vp8hip_tfilter_job *jobs, int n, const vp8hip_hist_job *pairs, int npairs,
                                  const vp8hip_tfilter *p, const void *mv, size_t mv_stride, const void *err, size_t err_stride,
                                  void *dst, size_t dst_stride, void *cnt, size_t cnt_stride);
+/* TRANSFORM AND QUANTISATION of the motion-compensated residual of picture pairs.  What the reference does with a 16x16 vector
+ * inside its mode decision and its encode loop is always the same five steps -- predict, subtract, forward DCT and Walsh transform,
+ * quantise, then dequantise, inverse-transform and add: vp8_encode_inter16x16 (vp8/encoder/encodemb.c) followed by
+ * vp8_inverse_transform_mby and vp8_dequant_idct_add_uv_block.  vp8hip_frames_quant_async makes them per macroblock of any picture
+ * pair, bit for bit, and hands out the levels, the end-of-block positions, the error figures and the reconstruction: from pictures
+ * to what an entropy coder, a requantiser or a rate-distortion estimate reads, without leaving the device.  SPLITMV, intra modes,
+ * the trellis (optimize_b), tokens and rate in bits, per-macroblock quantisers and the loop filter are not part of it.
+ *
+ * JOBS are vp8hip_hist_job (fb, ref_fb) exactly as for vp8hip_frames_subpel_async: fb is the SOURCE picture, ref_fb the REFERENCE it is
+ * predicted from; ref_fb < 0 is refused, fb == ref_fb is legal.  S(F), E(F), the coded area A x B and how a frame buffer in either
+ * form is read are vp8hip_frames_tfilter_async's, for all three planes.
+ *
+ * VECTORS.  mv is a device pointer, or NULL for (0, 0) everywhere: job i's tensor [2][mb_rows][mb_cols] of int16 at
+ * mv + i * mv_stride BYTES (both multiples of 2), channel 0 = x, channel 1 = y, in 1/8 pel -- vp8hip_frames_subpel_async's or
+ * vp8hip_frames_motion_async's output as it stands: the reference's mbmi.mv.  Any int16 is legal and is data, never an address.  No
+ * clamp to the UMV border is applied (the reference with need_to_clamp_mvs 0); E is defined everywhere.
+ *
+ * QUANTISER.  p->qindex, 0..127, applies to every job; where p->job_qindex is not NULL it is a HOST pointer to n bytes, copied at the
+ * call, job i's qindex (each 0..127; p->qindex is then not read).  p->delta[5] = y1dc, y2dc, y2ac, uvdc, uvac, each -15..15, as a
+ * frame header carries them, passed in explicitly: the rule of the reference's vp8_set_quantizer that y2dc is 4 - Q below Q 4 (and 0
+ * from there) is the CALLER'S to apply.  The factors are vp8hip_quant_factors(qindex, delta) below.  p->quantizer:
+ *   VP8HIP_QUANT_REGULAR  vp8_regular_quantize_b_c as the reference compiles it (EXACT_QUANT), over the improved_quant tables;
+ *   VP8HIP_QUANT_FAST     vp8_fast_quantize_b_c as compiled (without EXACT_FASTQUANT), over quant_fast, with no zero bin.
+ * The zero bin of the regular form is widened by three terms that keep the reference's names: p->zbin_over_quant,
+ * p->zbin_mode_boost, p->act_zbin_adj, each -1048576..1048576 (so that nothing below overflows an int; the reference's own values
+ * are 0..192, 0..12 and -1..4), combined as the reference's ZBIN_EXTRA macros combine them and truncated as its `(short)` does:
+ *   extra_Y = (short)((Y1 dequant ac * (zbin_over_quant + zbin_mode_boost + act_zbin_adj)) >> 7), extra_UV the same with UV dequant ac,
+ *   extra_Y2 = (short)((Y2 dequant ac * (zbin_over_quant / 2 + zbin_mode_boost + act_zbin_adj)) >> 7), the division C's (towards 0).
+ * They are not read by the fast form.  p->filter is VP8HIP_TFILTER_SIXTAP or VP8HIP_TFILTER_BILINEAR, with
+ * vp8hip_frames_tfilter_async's meaning.
+ *
+ * Per macroblock (my, mx) with the vector (vy, vx), in the reference's order:
+ *   1. PREDICTION, vp8_build_inter16x16_predictors_mb.  Luma is exactly vp8hip_frames_tfilter_async's LUMA paragraph: a copy, the
+ *      six-tap or the bilinear filter by the offsets (vy & 7, vx & 7).  Chroma is NOT that call's rule but the decoder's: each
+ *      component c of the luma vector becomes (c + (c < 0 ? -1 : 1)) / 2 with C's truncating division, no full-pixel mask; then base
+ *      >> 3 and offset & 7 through the 8x8 functions as there, and whether chroma is copied is decided by ITS offsets.  The
+ *      reference makes the += +-1 in a `short`, which wraps at 32767 and -32768; here it is made in int without the wrap: the two
+ *      differ for those two values only (32767 gives 16384 here and -16384 there, -32768 gives -16384 here and 16383 there).
+ *   2. RESIDUAL, vp8_subtract_mby_c and vp8_subtract_mbuv_c: source minus prediction, int16.
+ *   3. TRANSFORM, transform_mb for a 16x16 mode: vp8_short_fdct4x4_c on the 24 blocks -- block 4 r + c of luma at rows 4 r, columns
+ *      4 c of the macroblock, U 16 + 2 r + c, V 20 + 2 r + c likewise in their 8x8 --, with its four rounding constants and the
+ *      + (d1 != 0) on row 1; then the sixteen luma blocks' coefficient 0 (build_dcblock) through vp8_short_walsh4x4_c, with its
+ *      + (a1 != 0) and its += (x < 0) before (x + 3) >> 3, into block 24.  A luma block's own coefficient 0 stays what the DCT made
+ *      it -- the reference does not clear it --, so the quantiser quantises it with the y1dc factors, and it counts in that block's
+ *      eob: an entropy coder skips position 0 of the luma blocks of a macroblock that has a Y2 block, as every macroblock here has.
+ *   4. QUANTISATION of the 25 blocks, sixteen steps in zigzag order (0 1 4 8 5 2 3 6 9 12 13 10 7 11 14 15), position 0 with the dc
+ *      factors, the others with the ac factors of the block's table (Y1 for blocks 0..15, UV for 16..23, Y2 for 24), x = |z|:
+ *        regular:  zbin = zbin + zrun_zbin_boost[run] + extra;  y = x >= zbin ? (((x + round) * quant >> 16) + x + round) >> quant_shift : 0;
+ *                  run = y ? 0 : run + 1 (the number of steps since the last non-zero level, 0 at the start);
+ *        fast:     y = ((x + round) * quant_fast) >> 16;
+ *      qcoeff = z < 0 ? -y : y, dqcoeff = (int16)(qcoeff * dequant), eob = 1 + the last step whose y is not 0, else 0.
+ *   5. RECONSTRUCTION on the prediction of step 1.  vp8_inverse_transform_mby: vp8_short_inv_walsh4x4_c of block 24's dqcoeff where
+ *      eob[24] > 1, vp8_short_inv_walsh4x4_1_c ((dqcoeff[0] + 3) >> 3 sixteen times) otherwise, its outputs into position 0 of the
+ *      sixteen luma blocks; then eob_adjust -- a luma block whose eob is 0 but whose Walsh DC is not 0 is still transformed --; then
+ *      vp8_dequant_idct_add_y_block with the DC factor 1 and vp8_dequant_idct_add_uv_block: a block whose (adjusted) eob is above 1
+ *      is dequantised from its LEVELS ((int16)(qcoeff * dequant), position 0 of luma the Walsh DC itself) and goes through
+ *      vp8_short_idct4x4llm_c, any other adds ((int16)(position 0 * its factor) + 4) >> 3 to all sixteen pixels; clamped to 0..255.
+ *
+ * OUTPUTS, in the caller's device memory, each optional, at least one present; job i's at the pointer + i * its stride BYTES:
+ *   coef    [mb_rows][mb_cols][25][16] of int16, 800 bytes a macroblock, position 4 v + u inside a block (v the vertical frequency):
+ *           the reference's MACROBLOCKD.qcoeff[400] as it stands after step 4 -- Y 0..15, U 16..19, V 20..23, Y2 24.  p->stage
+ *           selects VP8HIP_COEF_LEVELS (qcoeff) or VP8HIP_COEF_DEQUANT (dqcoeff).  A record layout for readers that walk macroblocks,
+ *           not vp8hip_frames_coef_async's planes: block b, position 4 v + u here is that call's plane (Y: b < 16, U, V, Y2), block
+ *           (4 my + b / 4, 4 mx + b % 4) (chroma: (2 my + (b & 3) / 2, 2 mx + (b & 1))), raster position 4 v + u -- and the IR's
+ *           block (vp8_ir.h: column-major) is the transpose, entry 4 u + v.  Pointer and stride multiples of 16.
+ *           vp8hip_quant_coef_size(ctx) = 800 * mb_rows * mb_cols.
+ *   eob     [mb_rows][mb_cols][32] of uint8: the quantiser's eob of blocks 0..24 -- BEFORE eob_adjust --, entries 25..31 written as 0.
+ *           Pointer and stride multiples of 4.  vp8hip_quant_eob_size(ctx) = 32 * mb_rows * mb_cols.
+ *   stats   [popcount(p->planes)][mb_rows][mb_cols] of uint32 (pointer and stride multiples of 4), the planes in bit order:
+ *             VP8HIP_QUANT_ERRY    vp8_mbblock_error_c(mb, 1): the sum over luma blocks, positions 1..15, of (coeff - dqcoeff)^2;
+ *             VP8HIP_QUANT_ERRY2   vp8_block_error_c of block 24: all sixteen positions;
+ *             VP8HIP_QUANT_ERRUV   vp8_mbuverror_c: blocks 16..23, all sixteen positions;
+ *             VP8HIP_QUANT_EOBS    the sum of the 25 eobs;
+ *             VP8HIP_QUANT_RECSSE  the sum over the macroblock's 384 pixels of (source - reconstruction)^2: this library's own
+ *                                  figure, from which PSNR at the quantiser follows.
+ *           The three errors are not 0 for identical pictures: vp8_short_fdct4x4_c of a zero block leaves 1 at position 1 (its
+ *           rounding constant 14500 >> 12 = 3 in four rows, (12 + 7) >> 4), so ERRY is 16 and ERRUV 8 there, as in the reference.
+ *           vp8hip_quant_stats_size(ctx, p) = 4 * popcount * mb_rows * mb_cols, 0 for planes == 0 or unknown bits.  p->planes is not
+ *           read where stats is NULL, except for unknown bits.
+ *   rec     the reconstruction of step 5 as packed I420 at the DISPLAY size, vp8hip_i420_size(w, h) bytes:
+ *           vp8hip_frames_tfilter_async's dst layout.
+ * Only what an output needs is computed: a call without rec and without VP8HIP_QUANT_RECSSE makes no inverse transform.
+ *
+ * The call is its neighbours: enqueued on the context's stream -- a later writer of a frame buffer runs behind it, an earlier
+ * vp8hip_decode is seen --; nothing is converted, no raster pool is made and no device memory is added (the tables travel in the
+ * arguments of the launches; a call of many jobs, or of many different qindex values, is cut into launches where those are full);
+ * no frame buffer is written; only bytes inside an output's own [pointer + i * stride, + size) are written; no atomics: the same
+ * bits in every run.  It returns -2 with nothing enqueued for n < 1; an fb or ref_fb out of range (ref_fb < 0 included); a qindex
+ * outside 0..127 (p->qindex where job_qindex is NULL, else any of its n); a delta outside -15..15; an unknown quantizer, filter or
+ * stage; a zero-bin term outside +-1048576; plane bits other than the five; stats with planes == 0; all four outputs NULL; a stride
+ * below the size; a pointer or stride not aligned (mv: 2, coef: 16, eob: 4, stats: 4); an output or mv that is not device memory of
+ * the context's device or that cannot hold n jobs; outputs that overlap each other or mv.
+ *
+ * vp8hip_quant_factors(qindex, delta, out): host only, no context, no GPU.  What the reference's vp8cx_init_quantizer computes with
+ * sf.improved_quant on, for one qindex (0..127) and the five deltas (-15..15 each, the order above; NULL: all 0), for each of Y1, Y2
+ * and UV: the dc and the ac value of quant, quant_shift, quant_fast, zbin, round and dequant, and the sixteen zrun_zbin_boost
+ * values.  With d the dequant value -- vp8_dc_quant, vp8_dc2quant, vp8_dc_uv_quant, vp8_ac_yquant, vp8_ac2quant, vp8_ac_uv_quant:
+ * vp8hip_dequant_factors' six --, l = floor(log2 d): quant = (int16)(1 + (1 << (16 + l)) / d - (1 << 16)), quant_shift = l,
+ * quant_fast = (1 << 16) / d, zbin = ((qindex < 48 ? 84 : 80) * d + 64) >> 7, round = (48 * d) >> 7, and zrun_zbin_boost[i] =
+ * (d * {0, 0, 8, 10, 12, 14, 16, 20, 24, 28, 32, 36, 40, 44, 44, 44}[i]) >> 7 with d the dc value at i == 0 and the ac value
+ * elsewhere.  The call's plan uses it; a consumer of LEVELS that wants to requantise calls it too.  -2 for a NULL out or a value out
+ * of range. */
+#define VP8HIP_QUANT_REGULAR 0
+#define VP8HIP_QUANT_FAST    1
+#define VP8HIP_QUANT_ERRY    1   /* bit order = plane order */
+#define VP8HIP_QUANT_ERRY2   2
+#define VP8HIP_QUANT_ERRUV   4
+#define VP8HIP_QUANT_EOBS    8
+#define VP8HIP_QUANT_RECSSE  16
+typedef struct vp8hip_quant_table {        /* [0] Y1, [1] Y2, [2] UV; [][0] dc, [][1] ac */
+    int16_t quant[3][2], quant_shift[3][2], quant_fast[3][2], zbin[3][2], round[3][2], dequant[3][2];
+    int16_t zrun_zbin_boost[3][16];
+} vp8hip_quant_table;
+typedef struct vp8hip_quant {
+    int qindex;                /* 0..127; not read where job_qindex is given */
+    int delta[5];              /* y1dc, y2dc, y2ac, uvdc, uvac: -15..15 */
+    int quantizer;             /* VP8HIP_QUANT_REGULAR / _FAST */
+    int filter;                /* VP8HIP_TFILTER_SIXTAP / _BILINEAR */
+    int stage;                 /* of coef: VP8HIP_COEF_LEVELS / _DEQUANT */
+    int zbin_over_quant, zbin_mode_boost, act_zbin_adj;   /* -1048576..1048576 each; the regular quantiser's */
+    unsigned planes;           /* VP8HIP_QUANT_* bits of stats; may be 0 where stats is NULL */
+    const uint8_t *job_qindex; /* host memory, n bytes, or NULL: p->qindex for every job */
+} vp8hip_quant;
+int  vp8hip_quant_factors(int qindex, const int delta[5], vp8hip_quant_table *out);
+size_t vp8hip_quant_coef_size(const vp8hip_ctx *ctx);
+size_t vp8hip_quant_eob_size(const vp8hip_ctx *ctx);
+size_t vp8hip_quant_stats_size(const vp8hip_ctx *ctx, const vp8hip_quant *p);
+int  vp8hip_frames_quant_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int n, const vp8hip_quant *p, const void *mv, size_t mv_stride,
+                               void *coef, size_t coef_stride, void *eob, size_t eob_stride, void *stats, size_t stats_stride, void *rec,
+                               size_t rec_stride);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

@@ -594,6 +594,35 @@ def tfilter_sizes(w, h):
     return size, 2 * size
 
 
+QUANT_QUANTIZERS = {"regular": 0, "fast": 1}                  # VP8HIP_QUANT_REGULAR, _FAST
+QUANT_PLANES = {"erry": 1, "erry2": 2, "erruv": 4, "eobs": 8, "recsse": 16}      # VP8HIP_QUANT_*: bit order = plane order
+QUANT_ZBIN_MAX = 1 << 20                                      # the largest |zbin_over_quant|, |zbin_mode_boost|, |act_zbin_adj|
+
+
+def quant_sizes(w, h, planes=()):
+    """(bytes of one job's coef records, of its eobs, of its stats, of its reconstruction) of Vp8Hip.frames_quant at the display
+    size w x h: int16 [mb_rows, mb_cols, 25, 16], uint8 [mb_rows, mb_cols, 32], uint32 [P, mb_rows, mb_cols] (0 for no plane or an
+    unknown one) and packed I420 (vp8hip_i420_size); all 0 for a size outside 1..16383"""
+    if not (1 <= int(w) <= 16383 and 1 <= int(h) <= 16383):
+        return 0, 0, 0, 0
+    cells = ((int(w) + 15) // 16) * ((int(h) + 15) // 16)
+    mask = _plane_mask(planes, QUANT_PLANES, True)
+    return 800 * cells, 32 * cells, 0 if not mask else 4 * bin(mask).count("1") * cells, i420_size(int(w), int(h))
+
+
+def quant_factors(qindex, deltas=(0, 0, 0, 0, 0)):
+    """what the reference's vp8cx_init_quantizer computes with improved_quant for one qindex (vp8hip_quant_factors; on the host, no
+    GPU): a dict of int16 arrays [3, 2] -- Y1, Y2, UV by dc, ac -- "quant", "quant_shift", "quant_fast", "zbin", "round", "dequant",
+    and "zrun_zbin_boost" [3, 16].  deltas: y1dc, y2dc, y2ac, uvdc, uvac, each -15..15"""
+    d = [int(v) for v in deltas]
+    if len(d) != 5:
+        raise ValueError("quant_factors: five deltas (y1dc, y2dc, y2ac, uvdc, uvac)")
+    t = QuantTable()
+    if load_hip().vp8hip_quant_factors(int(qindex), (c_int * 5)(*d), ctypes.byref(t)):
+        raise ValueError(f"quant_factors: qindex {qindex} (0..127), deltas {deltas!r} (-15..15)")
+    return {name: np.ctypeslib.as_array(getattr(t, name)).copy() for name, _ in QuantTable._fields_}
+
+
 def ssim_mean(scores):
     """the scores [n, P, 2] of Vp8Hip.frames_ssim (a torch tensor or an array) -> float64 [n, P]: total / 2^32 / count, what
     vp8_ssim2 returns to within 2^-33 + N * 2^-52; NaN where the count is 0 (the reference's 0 / 0)"""
@@ -799,6 +828,16 @@ class TfilterJob(ctypes.Structure):         # vp8hip_tfilter_job, include/vp8hip
     _fields_ = [("fb", ctypes.c_int32), ("first", ctypes.c_int32), ("count", ctypes.c_int32)]
 
 
+class QuantTable(ctypes.Structure):         # vp8hip_quant_table, include/vp8hip.h
+    _fields_ = [(name, ctypes.c_int16 * 2 * 3) for name in ("quant", "quant_shift", "quant_fast", "zbin", "round", "dequant")] + \
+               [("zrun_zbin_boost", ctypes.c_int16 * 16 * 3)]
+
+
+class QuantParams(ctypes.Structure):        # vp8hip_quant, include/vp8hip.h
+    _fields_ = [("qindex", c_int), ("delta", c_int * 5), ("quantizer", c_int), ("filter", c_int), ("stage", c_int), ("zbin_over_quant", c_int),
+                ("zbin_mode_boost", c_int), ("act_zbin_adj", c_int), ("planes", ctypes.c_uint), ("job_qindex", ctypes.POINTER(ctypes.c_uint8))]
+
+
 class VisParams(ctypes.Structure):         # vp8hip_vis, include/vp8hip.h
     _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
                 ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
@@ -919,6 +958,14 @@ def load_hip():
         L.vp8hip_tfilter_count_size.restype = c_size_t
         L.vp8hip_frames_tfilter_async.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.POINTER(TfilterParams), c_void_p, c_size_t,
                                                   c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+        L.vp8hip_quant_factors.argtypes = [c_int, c_void_p, c_void_p]
+        for name in ("vp8hip_quant_coef_size", "vp8hip_quant_eob_size"):
+            getattr(L, name).argtypes = [c_void_p]
+            getattr(L, name).restype = c_size_t
+        L.vp8hip_quant_stats_size.argtypes = [c_void_p, ctypes.POINTER(QuantParams)]
+        L.vp8hip_quant_stats_size.restype = c_size_t
+        L.vp8hip_frames_quant_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(QuantParams), c_void_p, c_size_t, c_void_p, c_size_t,
+                                                c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1552,7 +1599,7 @@ class Vp8Hip:
     @staticmethod
     def _pair_jobs(who, jobs, planes, table, none_ok=False, ref_optional=False):
         """-> (the HistJob array, how many jobs, the plane mask) of a call over picture pairs (frames_hist, frames_ssim, frames_motion, frames_subpel,
-        frames_tfilter);
+        frames_tfilter, frames_quant);
         ValueError, in this order, for a job that is no (fb, ref_fb) -- ref_optional: or a bare frame buffer, and ref_fb may be
         None --, for an unknown plane or -- unless none_ok -- no plane, for no job and for a negative frame buffer"""
         items = []
@@ -1807,6 +1854,76 @@ class Vp8Hip:
                                                                                                          *ins, dp, ds, cp, cs),
                               "vp8hip_frames_tfilter_async", ok, "with stride(1) == 1")
         return tuple(made) if counted else made[0]
+
+    def frames_quant(self, jobs, mv=None, qindex=40, deltas=(0, 0, 0, 0, 0), quantizer="regular", filter="sixtap", stage="levels",
+                     zbin=(0, 0, 0), planes=(), want=("coef", "eob"), out_coef=None, out_eob=None, out_stats=None, out_rec=None):
+        """The reference's inter 16x16 encode of picture pairs on the context's device (vp8hip_frames_quant_async): per macroblock
+        of fb the prediction from ref_fb at the vector, the residual, the forward DCT and Walsh transform, the quantiser and --
+        where asked -- the reconstruction, bit for bit with vp8_encode_inter16x16, vp8_inverse_transform_mby and
+        vp8_dequant_idct_add_uv_block.  `jobs`: a list of (fb, ref_fb), fb the source, ref_fb the reference; any order, repeats
+        allowed, fb == ref_fb legal.  `mv`: frames_subpel's (or frames_motion's) torch.int16 tensor [n, 2, mb_rows, mb_cols] as it
+        stands, None: (0, 0).  `qindex`: 0..127 for every job, or a sequence of n, one a job.  `deltas`: y1dc, y2dc, y2ac, uvdc,
+        uvac, each -15..15 (the reference's rule that y2dc is 4 - Q below Q 4 is the caller's to apply).  quantizer: "regular" or
+        "fast"; filter: "sixtap" or "bilinear"; stage: "levels" or "dequant", what coef holds; zbin: (zbin_over_quant,
+        zbin_mode_boost, act_zbin_adj), the regular quantiser's.  Returns a dict of what `want` names or an out_* tensor is given
+        for: "coef" a torch.int16 tensor [n, mb_rows, mb_cols, 25, 16] (blocks Y 0..15, U 16..19, V 20..23, Y2 24; position
+        4 v + u), "eob" torch.uint8 [n, mb_rows, mb_cols, 32] (entries 25..31 are 0), "stats" torch.int32
+        [n, P, mb_rows, mb_cols] holding uint32 bits, the planes of `planes` ("erry", "erry2", "erruv", "eobs", "recsse", or the
+        mask) in bit order -- asked for by naming planes --, "rec" torch.uint8 [n, i420_size(width, height)], frames_tfilter's
+        layout.  Without "rec" and "recsse" no inverse transform is made.  Each frame buffer is read in the form it has; nothing
+        is converted or allocated.  out_*: tensors of those shapes and types, each job dense, stride(0) free (a multiple of 16
+        bytes for coef, 4 for eob).  Stream ordering, the `import torch` first rule and the remark on record_stream: as
+        frames_scaled."""
+        who = "frames_quant"
+        arr, n, mask = self._pair_jobs(who, jobs, planes, QUANT_PLANES, none_ok=True)
+        want = {want} if isinstance(want, str) else set(want)
+        if want - {"coef", "eob", "stats", "rec"}:
+            raise ValueError(f"{who}: want {sorted(want)!r} (of coef, eob, stats, rec)")
+        given = {"coef": out_coef, "eob": out_eob, "stats": out_stats, "rec": out_rec}
+        want |= {k for k, t in given.items() if t is not None}
+        if mask:
+            want.add("stats")
+        if "stats" in want and not mask:
+            raise ValueError(f"{who}: stats without planes")
+        if not want:
+            raise ValueError(f"{who}: no output asked for")
+        jq = None
+        if isinstance(qindex, (int, np.integer)):
+            qs = [int(qindex)]
+        else:
+            qs = [int(q) for q in qindex]
+            if len(qs) != n:
+                raise ValueError(f"{who}: {len(qs)} qindex values for {n} jobs")
+            jq = (ctypes.c_uint8 * n)(*[q & 255 for q in qs])
+        d = [int(v) for v in deltas]
+        z = [int(v) for v in zbin]
+        if any(not 0 <= q <= 127 for q in qs) or len(d) != 5 or any(not -15 <= v <= 15 for v in d):
+            raise ValueError(f"{who}: qindex {qindex!r} (0..127), deltas {deltas!r} (five of -15..15)")
+        if len(z) != 3 or any(abs(v) > QUANT_ZBIN_MAX for v in z):
+            raise ValueError(f"{who}: zbin {zbin!r} (zbin_over_quant, zbin_mode_boost, act_zbin_adj, each within +-{QUANT_ZBIN_MAX})")
+        if quantizer not in QUANT_QUANTIZERS or filter not in TFILTER_FILTERS or stage not in COEF_STAGES:
+            raise ValueError(f"{who}: quantizer {quantizer!r} ({', '.join(QUANT_QUANTIZERS)}), filter {filter!r} ({', '.join(TFILTER_FILTERS)}), "
+                             f"stage {stage!r} ({', '.join(COEF_STAGES)})")
+        p = QuantParams(qs[0], (c_int * 5)(*d), QUANT_QUANTIZERS[quantizer], TFILTER_FILTERS[filter], COEF_STAGES[stage], z[0], z[1], z[2], mask or 0, jq)
+        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
+        mptr, mstride = None, 0
+        if mv is not None:
+            torch, dev = self._torch_device(who)
+            if not self._dense(mv, torch.int16, (n, 2, rows, cols), dev):
+                raise ValueError(f"{who}: mv must be an int16 tensor {[n, 2, rows, cols]}, each job dense, on {dev}")
+            mptr, mstride = c_void_p(mv.data_ptr()), mv.stride(0) * 2
+        shapes = {"coef": ("int16", (n, rows, cols, 25, 16)), "eob": ("uint8", (n, rows, cols, 32)),
+                  "stats": ("int32", (n, bin(mask or 0).count("1"), rows, cols)),
+                  "rec": ("uint8", (n, int(self.L.vp8hip_i420_size(self.width, self.height))))}
+        names = [k for k in ("coef", "eob", "stats", "rec") if k in want]
+        outs = [("out_" + k, given[k], shapes[k][0], shapes[k][1]) for k in names]
+
+        def call(*args):
+            a = dict(zip(names, zip(args[0::2], args[1::2])))
+            flat = [v for k in ("coef", "eob", "stats", "rec") for v in a.get(k, (None, 0))]
+            return self.L.vp8hip_frames_quant_async(self.h, arr, n, ctypes.byref(p), mptr, mstride, *flat)
+        made = self._to_torch(who, outs, call, "vp8hip_frames_quant_async")
+        return dict(zip(names, made))
 
     def ssim_share(self, n, planes=("y", "u", "v")):
         """how many workgroups share each job of a frames_ssim call of n jobs over `planes` (vp8hip_ssim_share): 1 -- a workgroup

@@ -372,6 +372,31 @@ struct TfilterLaunch : FramePlanes {
     TfilterJob j[TFILTER_MAX_JOBS];
     int ref[TFILTER_MAX_REFS];    // the sources: frame buffer << 2 | form
 };
+// One launch of vp8hip_frames_quant_async (vp8_quant.hip), as the host's plan (vp8hip_quant.hip) left it.  A workgroup owns one
+// macroblock of one job.  A job names one of the launch's tables: what vp8hip_quant_factors gave for the job's qindex, as it stands,
+// then the three zero-bin extras; jobs of one qindex share a table, so a launch takes jobs until either array is full
+#define QUANT_MAX_JOBS 160        // jobs per launch (kernel arguments: 12 bytes each)
+#define QUANT_MAX_TABLES 8        // distinct qindex values per launch (176 bytes each)
+#define QUANT_THREADS TFILTER_THREADS    // the prediction is vp8_mc_pred.hip.h's: the same lanes own the same pixels
+#define QUANT_TABLE_SHORTS 88     // 84 of vp8hip_quant_table, 3 extras (Y1, Y2, UV), 1 unused
+#define QUANT_ERRY 1              // VP8HIP_QUANT_*
+#define QUANT_ERRY2 2
+#define QUANT_ERRUV 4
+#define QUANT_EOBS 8
+#define QUANT_RECSSE 16
+struct QuantJob {
+    int fb, ref;                  // the source and the reference picture: frame buffer << 2 | form, as of the call
+    int table;                    // its table in QuantLaunch::t
+};
+struct QuantLaunch : FramePlanes {
+    int filter;                   // 0: six-tap, 1: bilinear
+    int fast;                     // 0: the regular quantiser, 1: the fast one
+    int levels;                   // coef holds 1: qcoeff, 0: dqcoeff
+    unsigned planes;              // QUANT_* bits of the stats; 0: none
+    int mv, coef, eob, rec;       // 1: vectors are read / coefficients, eobs, reconstructions are written
+    short t[QUANT_MAX_TABLES][QUANT_TABLE_SHORTS];
+    QuantJob j[QUANT_MAX_JOBS];
+};
 // the five launches' layout in the kernels' arguments: the base takes 36 bytes and the first member lies right behind it (offsetof
 // past a base of plain ints is what the warning calls conditionally supported: it is supported here)
 #pragma clang diagnostic push
@@ -381,6 +406,7 @@ static_assert(sizeof(SubpelLaunch) == 2112 && sizeof(SubpelTablePiece) == 3592, 
 static_assert(offsetof(HistFrameLaunch, S) == 36 && offsetof(SsimLaunch, S) == 36 && offsetof(MotionLaunch, d) == 36, "");
 static_assert(offsetof(SubpelLaunch, precision) == 36, "");
 static_assert(sizeof(TfilterLaunch) == 3524 && offsetof(TfilterLaunch, strength) == 36, "");
+static_assert(sizeof(QuantLaunch) == 3396 && offsetof(QuantLaunch, filter) == 36 && offsetof(QuantLaunch, t) == 68, "");
 #pragma clang diagnostic pop
 
 #define WAVE 64
