@@ -150,9 +150,11 @@ ZIGZAG_RASTER = [0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15]
 ZIGZAG_COLMAJOR = [(z % 4) * 4 + z // 4 for z in ZIGZAG_RASTER]
 
 
-def synth_ir(width, height, seed, inter=False, version=0, filter_type=0, dense=0.3, big=False, segmented=True):
+def synth_ir(width, height, seed, inter=False, version=0, filter_type=0, dense=0.3, big=False, segmented=True, inter_share=0.8):
     """One frame of random IR.  Coefficients and eobs are mutually consistent the way the feeder
-    produces them (eob = last coded zig-zag position + 1; Y blocks of an MB with a Y2 block start at 1)."""
+    produces them (eob = last coded zig-zag position + 1; Y blocks of an MB with a Y2 block start at 1).
+    inter_share: of an inter frame's macroblocks, the share that is inter (1.0: not one intra macroblock, 0.0: all intra); the
+    draw that decides is made either way, and 0.8 gives the IR every seed has always given."""
     P = load_package()
     rng = np.random.default_rng(seed)
     cols, rows = (width + 15) // 16, (height + 15) // 16
@@ -182,7 +184,7 @@ def synth_ir(width, height, seed, inter=False, version=0, filter_type=0, dense=0
     zz = np.array(ZIGZAG_COLMAJOR)
     for i in range(n):
         r, c = divmod(i, cols)
-        is_inter = inter and rng.random() < 0.8
+        is_inter = inter and rng.random() < inter_share
         if is_inter:
             y_mode = int(rng.choice([5, 6, 7, 8, 9]))
             mbs[i, 2] = int(rng.integers(1, 4))
