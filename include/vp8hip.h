@@ -1278,6 +1278,129 @@ size_t vp8hip_quant_stats_size(const vp8hip_ctx *ctx, const vp8hip_quant *p);
 int  vp8hip_frames_quant_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int n, const vp8hip_quant *p, const void *mv, size_t mv_stride,
                                void *coef, size_t coef_stride, void *eob, size_t eob_stride, void *stats, size_t stats_stride, void *rec,
                                size_t rec_stride);
+/* COMPRESSED INTER FRAMES from quantised levels and vectors: the entropy coder behind vp8hip_frames_quant_async.
+ * vp8hip_frames_pack_async takes that call's mv and coef tensors as they stand and writes, per job, one complete compressed VP8
+ * inter frame (RFC 6386) into the caller's device memory: the 3-byte frame tag, the first partition, the partition size table, 1 to
+ * 8 token partitions.  Nothing but the frame header's few fields goes through the host; it reads no frame buffer and no IR slot;
+ * jobs are simply 0 .. n - 1.  Key frames and intra macroblocks, SPLITMV, segmentation and loop-filter deltas, probability updates
+ * or adaptation (only the counts are handed out), the trellis, rate control, containers and chaining rec back in as the next
+ * reference are not part of it.
+ *
+ * THE YARDSTICK for every byte is the stream writer of the test suite (tests/vp8_writer.py, write_inter_frame), written from RFC
+ * 6386 and arbitrated by the real reference decoder.  A partition is flushed as its BoolEncoder.finish does: the bits of the byte in
+ * the making, then three more bytes of `bottom`, four bytes in all.  The reference's vp8_stop_encode pads differently -- 32 times
+ * put(0, 128) -- and decodes alike.
+ *
+ * INPUTS, device memory.  mv: job i's [2][mb_rows][mb_cols] of int16 at mv + i * mv_stride BYTES (multiples of 2), channel 0 = x,
+ * 1 = y, in 1/8 pel -- vp8hip_frames_subpel_async's units --, NULL: (0, 0) everywhere.  coef: job i's LEVELS records
+ * [mb_rows][mb_cols][25][16] of int16 at coef + i * coef_stride (multiples of 16), position 4 v + u, blocks Y 0..15, U 16..19,
+ * V 20..23, Y2 24: vp8hip_frames_quant_async's layout with p->stage VP8HIP_COEF_LEVELS.  Position 0 of luma blocks 0..15 is NOT
+ * coded and is not read: every macroblock here has a Y2 block, and frames_quant leaves the y1dc-quantised value there.  There is no
+ * eob input: a block's end is the last non-zero zigzag step (0 1 4 8 5 2 3 6 9 12 13 10 7 11 14 15), from step 1 for luma and from
+ * step 0 otherwise, so an inconsistent eob cannot make a wrong stream.  Any int16 is data, never an address.
+ *
+ * PARAMETERS (vp8hip_pack).  version 0..3, show_frame 0..1, filter_type 0..1, filter_level 0..63, sharpness 0..7; qindex 0..127
+ * for every job, or job_qindex, a HOST pointer to n bytes copied at the call, as in vp8hip_quant; delta[5] = y1dc, y2dc, y2ac, uvdc,
+ * uvac, each -15..15; ref_frame 1..3 (LAST, GOLDEN, ALTREF), that of every macroblock; refresh_last, refresh_golden, refresh_alt,
+ * sign_bias_golden, sign_bias_alt 0..1; copy_buffer_to_gf, copy_buffer_to_arf 0..2 (coded only where the refresh flag is 0);
+ * log2_parts 0..3; prob_skip_false, prob_intra, prob_last, prob_gf 1..255 (0 is refused).  Fixed, as in the writer: segmentation
+ * off, mode_ref_lf_delta_enabled 0, refresh_entropy_probs 1, mb_no_coeff_skip 1, no coefficient, mode or vector probability update:
+ * the frame is coded with the default tables.
+ *
+ * THE FIRST PARTITION.  The header, in write_inter_frame's order: segmentation_enabled (0), filter_type, filter_level (6 bits),
+ * sharpness (3), mode_ref_lf_delta_enabled (0), log2_parts (2), qindex (7), the five deltas (a 0 flag, or 1, four magnitude bits and
+ * the sign), refresh_golden, refresh_alt, copy_buffer_to_gf (2, if !refresh_golden), copy_buffer_to_arf (2, if !refresh_alt),
+ * sign_bias_golden, sign_bias_alt, refresh_entropy_probs (1), refresh_last, 1056 "no update" flags at vp8_coef_update_probs,
+ * mb_no_coeff_skip (1), prob_skip_false, prob_intra, prob_last, prob_gf (8 each), the two intra probability update flags (0), 38 "no
+ * update" flags at vp8_mv_update_probs.  Then per macroblock in raster order:
+ *   1. the skip flag at prob_skip_false: 1 exactly where the reference's mb_is_skippable(x, 1) says so -- no coded level in any of the
+ *      25 blocks (luma position 0 not counting);
+ *   2. 1 at prob_intra (inter), then ref_frame: 0 at prob_last for LAST, else 1 and ref_frame - 2 at prob_gf;
+ *   3. the mode.  near[] and cnt[] are RFC 6386 18.3's (vp8_find_near_mvs) over the above, the left and the above-left macroblock,
+ *      weights 2, 2, 1: a neighbour outside the picture counts as intra (skipped); one inside has the GIVEN vector; a non-zero vector
+ *      that differs from near[k] opens near[++k] (the above one always does); cnt[k] or, for a zero vector, cnt[0] takes the weight.
+ *      All neighbours share ref_frame, so no sign bias applies.  p[i] = vp8_mode_contexts[cnt[i]][i].  In this order:
+ *        ZEROMV     if the vector is (0, 0): 0 at p[0].  Otherwise 1 at p[0]; then cnt[1] += 1 if cnt[3] and near[k] == near[1]; cnt[3]
+ *                   = 0 (the SPLITMV count: always 0 here); near[1] and near[2] with their counts swap if cnt[2] > cnt[1];
+ *        NEARESTMV  if the vector equals near[1] clamped: 0 at p[1].  Otherwise 1 at p[1];
+ *        NEARMV     if it equals near[2] clamped: 0 at p[2].  Otherwise 1 at p[2];
+ *        NEWMV      0 at p[3]; best = (cnt[1] >= cnt[0] ? near[1] : near[0]) clamped; then (v - best) / 2 per component, row first,
+ *                   through vp8_default_mv_context as RFC 6386 section 17 codes a component (short form below 8, else the long
+ *                   form: bits 0, 1, 2, then 9 .. 4, then bit 3 if the magnitude is above 15; the sign if it is not 0).
+ *      "clamped": the row to [-(16 my << 3) - 128, (16 (mb_rows - 1 - my) << 3) + 128], the column likewise with mx and mb_cols:
+ *      the 16-pixel margin.  A decoder derives the same four modes and the given vectors back.
+ *
+ * TOKENS.  A macroblock of row r goes into partition r % (1 << log2_parts); a skipped one codes nothing.  Order: Y2 (block 24, type
+ * 1), the sixteen luma blocks from position 1 (type 0), four U, four V (type 2).  The context of a block is above + left "had a
+ * coded level", across macroblocks, 0 outside the picture and for skipped macroblocks.  Per block from its first step: "not end of
+ * block" (unless the step before coded a zero), the token tree of RFC 6386 13.2 with vp8_default_coef_probs[type][band][context]
+ * -- the context of the next step is 0, 1 or 2 for a level of 0, +-1, more --, DCT_CAT1..6 with their extra bits (categories begin
+ * at 5, 7, 11, 19, 35, 67), the sign at 128; "end of block" after the block's end unless that is step 15.
+ *
+ * OUTPUTS, device memory.  dst: job i's frame at dst + i * dst_stride; at most `cap` bytes are ever written there, cap <=
+ * dst_stride, dst, cap and dst_stride multiples of 16.  info: job i's 16 uint32 at info + 64 i (a multiple of 4):
+ *   [0] status   [1] frame bytes   [2] first partition bytes   [3..10] token partition bytes (0 for partitions the frame does not
+ *   have)   [11] skipped macroblocks   [12..15] ZEROMV, NEARESTMV, NEARMV, NEWMV macroblocks
+ * -- the counts are what a later call needs to choose prob_skip_false and to adapt probabilities; that choice is the caller's.
+ * Status bits:
+ *   VP8HIP_PACK_OVERFLOW    the frame does not fit cap, or its first partition exceeds the tag's 19 bits (or a token partition the
+ *                           size table's 24);
+ *   VP8HIP_PACK_BAD_VECTOR  an odd component, or a NEWMV difference outside +-1023 coded units (the writer would clip it silently);
+ *   VP8HIP_PACK_BAD_LEVEL   a coded |level| above 2114, the end of DCT_CAT6;
+ *   VP8HIP_PACK_CLAMPS      informational: some NEWMV vector lies beyond mb_to_edge - (19 << 3) or + (18 << 3), where the decoder's
+ *                           clamp_mv_to_umv_border would move it.  The frame is valid, but does not decode to frames_quant's rec,
+ *                           which never clamps.
+ * With any of the first three: info[1] = 0, the bytes inside [dst, dst + cap) are unspecified, no byte outside is touched and the
+ * other jobs are unaffected.  With OVERFLOW alone info[2..10] are the sizes the partitions would have had (a first partition is
+ * counted on even where it no longer fits), so 3 + [2] + 3 (parts - 1) + the sum of [3..10] is the cap that suffices.
+ *
+ * vp8hip_pack_bound(ctx, log2_parts): a cap that always suffices, a multiple of 16; 0 for a context without a size or log2_parts
+ * outside 0..3.  A put shortens the coder's range from 128..255 to at least 1, so it is followed by at most 7 renormalisation
+ * shifts: 7 bits.  A macroblock is at most 32 puts of the first partition (skip, inter, two for the reference, four for the mode, two
+ * components of twelve) and 25 blocks of 16 tokens of 19 puts (7 of the tree, 11 extra bits, the sign) and an end-of-block: 28 and
+ * 6672 bytes.  The bound is 3 + (VP8HIP_PACK_HEAD_MAX + 8 + 28 MBs) + 3 (parts - 1) + 6672 MBs + 4 parts, rounded up: loose -- real
+ * frames are a hundredth of it --, so a caller that knows its content passes a smaller cap and watches OVERFLOW.
+ *
+ * vp8hip_pack_header(p, qindex, out): host only, no context, no GPU.  The header fields above through a C bool encoder up to where
+ * the per-macroblock data begin: out->bytes[0 .. nbytes) are the bytes BoolEncoder has written by then and bottom, range, bit_count
+ * its state; cache, pending and settled the same in the form the device coder continues from (bytes[settled] = cache is the last
+ * byte that is not 0xFF -- a later carry lands there --, `pending` bytes of 0xFF follow it; cache -1: nbytes is 0).  The plan calls
+ * it per distinct qindex of a call and hands state and bytes to the device: the mirror of vp8_parser_export_entropy.  -2 for a NULL
+ * or a value out of range (p->job_qindex and p->qindex are not read: the qindex is the argument).
+ *
+ * The call is its neighbours: enqueued on the context's stream; the same bits in every run (integer atomics only).  Scratch -- 32
+ * bytes a macroblock of plan records and the regions the partitions are coded into before their sizes are known, min(cap, bound of
+ * the partition) each -- is the context's, the buffer vp8hip_frames_rgb_async keeps (vp8hip_rgb_scratch_bytes,
+ * vp8hip_release_staging); a call is cut into groups of jobs so that it stays under 2 GB (one job at least) -- with the default cap
+ * at a large size that is few jobs a group, another reason to pass a realistic cap.  It returns -2 with nothing enqueued for n < 1;
+ * a parameter out of range; a NULL coef, dst or info; cap < 16, cap > dst_stride, a stride below the size (mv: 4 MBs, coef: 800
+ * MBs); a pointer, cap or stride not aligned (mv 2, coef 16, dst 16, info 4); memory that is not device memory of the context's
+ * device or cannot hold n jobs; dst or info overlapping each other, mv or coef. */
+#define VP8HIP_PACK_OVERFLOW   1
+#define VP8HIP_PACK_BAD_VECTOR 2
+#define VP8HIP_PACK_BAD_LEVEL  4
+#define VP8HIP_PACK_CLAMPS     8
+#define VP8HIP_PACK_HEAD_MAX   64
+typedef struct vp8hip_pack {
+    int version, show_frame, filter_type, filter_level, sharpness;
+    int qindex;                /* 0..127; not read where job_qindex is given */
+    int delta[5];              /* y1dc, y2dc, y2ac, uvdc, uvac: -15..15 */
+    int ref_frame;             /* 1 LAST, 2 GOLDEN, 3 ALTREF */
+    int refresh_last, refresh_golden, refresh_alt, copy_buffer_to_gf, copy_buffer_to_arf, sign_bias_golden, sign_bias_alt;
+    int log2_parts;            /* 0..3 */
+    int prob_skip_false, prob_intra, prob_last, prob_gf;   /* 1..255 */
+    const uint8_t *job_qindex; /* host memory, n bytes, or NULL: qindex for every job */
+} vp8hip_pack;
+typedef struct vp8hip_pack_head {
+    uint32_t bottom, range, bit_count, nbytes;
+    int32_t cache;
+    uint32_t pending, settled, reserved;
+    uint8_t bytes[VP8HIP_PACK_HEAD_MAX];
+} vp8hip_pack_head;
+size_t vp8hip_pack_bound(const vp8hip_ctx *ctx, int log2_parts);
+int  vp8hip_pack_header(const vp8hip_pack *p, int qindex, vp8hip_pack_head *out);
+int  vp8hip_frames_pack_async(vp8hip_ctx *ctx, int n, const vp8hip_pack *p, const void *mv, size_t mv_stride, const void *coef,
+                              size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

@@ -623,6 +623,71 @@ def quant_factors(qindex, deltas=(0, 0, 0, 0, 0)):
     return {name: np.ctypeslib.as_array(getattr(t, name)).copy() for name, _ in QuantTable._fields_}
 
 
+PACK_OVERFLOW, PACK_BAD_VECTOR, PACK_BAD_LEVEL, PACK_CLAMPS = 1, 2, 4, 8      # VP8HIP_PACK_*: the status bits of Vp8Hip.frames_pack
+# what Vp8Hip.frames_pack and pack_header take beside the levels, the vectors and the quantiser, with their defaults
+PACK_DEFAULTS = dict(version=0, show_frame=1, filter_type=0, filter_level=0, sharpness=0, ref_frame=1, refresh_last=1, refresh_golden=0, refresh_alt=0,
+                     copy_buffer_to_gf=0, copy_buffer_to_arf=0, sign_bias_golden=0, sign_bias_alt=0, log2_parts=0, prob_skip_false=200, prob_intra=150,
+                     prob_last=140, prob_gf=100)
+
+
+def _pack_params(who, qindex, deltas, fields, n=None):
+    """-> (PackParams, the array job_qindex points to -- to be kept alive -- or None); ValueError for an unknown field or a wrong count"""
+    unknown = set(fields) - set(PACK_DEFAULTS)
+    if unknown:
+        raise ValueError(f"{who}: unknown parameters {sorted(unknown)!r} (of {', '.join(PACK_DEFAULTS)})")
+    d = [int(v) for v in deltas]
+    if len(d) != 5:
+        raise ValueError(f"{who}: five deltas (y1dc, y2dc, y2ac, uvdc, uvac)")
+    p = PackParams()
+    for name, v in {**PACK_DEFAULTS, **fields}.items():
+        setattr(p, name, int(v))
+    p.delta = (c_int * 5)(*d)
+    jq = None
+    if isinstance(qindex, (int, np.integer)):
+        p.qindex = int(qindex)
+    else:
+        qs = [int(q) for q in qindex]
+        if n is None or len(qs) != n:
+            raise ValueError(f"{who}: {len(qs)} qindex values for {n} jobs")
+        if any(not 0 <= q <= 127 for q in qs):
+            raise ValueError(f"{who}: qindex {qindex!r} (0..127)")
+        jq = (ctypes.c_uint8 * n)(*qs)
+        p.qindex, p.job_qindex = qs[0], jq
+    return p, jq
+
+
+def pack_bound(w, h, log2_parts=0):
+    """a `cap` that always suffices for a frame of Vp8Hip.frames_pack at the display size w x h: what vp8hip_pack_bound gives for a
+    context of that size (include/vp8hip.h derives it: 7 bits a put, 32 puts a macroblock in the first partition, 7625 in the
+    tokens); 0 for a size outside 1..16383 or log2_parts outside 0..3"""
+    if not (1 <= int(w) <= 16383 and 1 <= int(h) <= 16383 and 0 <= int(log2_parts) <= 3):
+        return 0
+    cells, parts = ((int(w) + 15) // 16) * ((int(h) + 15) // 16), 1 << int(log2_parts)
+    return (3 + (64 + 8 + 28 * cells) + 3 * (parts - 1) + 6672 * cells + 4 * parts + 15) // 16 * 16
+
+
+def pack_header(qindex=40, deltas=(0, 0, 0, 0, 0), **fields):
+    """the frame header of Vp8Hip.frames_pack's frames through the library's C bool encoder, up to where the per-macroblock data
+    begin (vp8hip_pack_header; on the host, no GPU): a dict of "bytes" -- what the coder has written by then --, "bottom", "range",
+    "bit_count" -- its state -- and "cache", "pending", "settled", the same in the form the device continues from.  fields:
+    PACK_DEFAULTS' names"""
+    p, _ = _pack_params("pack_header", 0, deltas, fields)
+    h = PackHead()
+    if load_hip().vp8hip_pack_header(ctypes.byref(p), int(qindex), ctypes.byref(h)):
+        raise ValueError(f"pack_header: qindex {qindex} (0..127), deltas {deltas!r} (-15..15) or {fields!r} out of range")
+    out = {name: int(getattr(h, name)) for name in ("bottom", "range", "bit_count", "cache", "pending", "settled")}
+    out["bytes"] = bytes(h.bytes[:h.nbytes])
+    return out
+
+
+def pack_frames(data, info):
+    """(data, info) of Vp8Hip.frames_pack (torch tensors or arrays) -> a list of each job's compressed frame as bytes, None where the
+    job's status has PACK_OVERFLOW, PACK_BAD_VECTOR or PACK_BAD_LEVEL"""
+    d = np.asarray(data.cpu() if hasattr(data, "cpu") else data)
+    i = np.asarray(info.cpu() if hasattr(info, "cpu") else info)
+    return [None if int(s[0]) & 7 else d[k, :int(s[1])].tobytes() for k, s in enumerate(i)]
+
+
 def ssim_mean(scores):
     """the scores [n, P, 2] of Vp8Hip.frames_ssim (a torch tensor or an array) -> float64 [n, P]: total / 2^32 / count, what
     vp8_ssim2 returns to within 2^-33 + N * 2^-52; NaN where the count is 0 (the reference's 0 / 0)"""
@@ -838,6 +903,19 @@ class QuantParams(ctypes.Structure):        # vp8hip_quant, include/vp8hip.h
                 ("zbin_mode_boost", c_int), ("act_zbin_adj", c_int), ("planes", ctypes.c_uint), ("job_qindex", ctypes.POINTER(ctypes.c_uint8))]
 
 
+class PackParams(ctypes.Structure):         # vp8hip_pack, include/vp8hip.h
+    _fields_ = [(name, c_int) for name in ("version", "show_frame", "filter_type", "filter_level", "sharpness", "qindex")] + [("delta", c_int * 5)] + \
+               [(name, c_int) for name in ("ref_frame", "refresh_last", "refresh_golden", "refresh_alt", "copy_buffer_to_gf", "copy_buffer_to_arf",
+                                           "sign_bias_golden", "sign_bias_alt", "log2_parts", "prob_skip_false", "prob_intra", "prob_last", "prob_gf")] + \
+               [("job_qindex", ctypes.POINTER(ctypes.c_uint8))]
+
+
+class PackHead(ctypes.Structure):           # vp8hip_pack_head, include/vp8hip.h
+    _fields_ = [("bottom", ctypes.c_uint32), ("range", ctypes.c_uint32), ("bit_count", ctypes.c_uint32), ("nbytes", ctypes.c_uint32),
+                ("cache", ctypes.c_int32), ("pending", ctypes.c_uint32), ("settled", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("bytes", ctypes.c_uint8 * 64)]
+
+
 class VisParams(ctypes.Structure):         # vp8hip_vis, include/vp8hip.h
     _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
                 ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
@@ -966,6 +1044,11 @@ def load_hip():
         L.vp8hip_quant_stats_size.restype = c_size_t
         L.vp8hip_frames_quant_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(QuantParams), c_void_p, c_size_t, c_void_p, c_size_t,
                                                 c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+        L.vp8hip_pack_bound.argtypes = [c_void_p, c_int]
+        L.vp8hip_pack_bound.restype = c_size_t
+        L.vp8hip_pack_header.argtypes = [ctypes.POINTER(PackParams), c_int, ctypes.POINTER(PackHead)]
+        L.vp8hip_frames_pack_async.argtypes = [c_void_p, c_int, ctypes.POINTER(PackParams), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+                                               c_size_t, c_void_p]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -1924,6 +2007,54 @@ class Vp8Hip:
             return self.L.vp8hip_frames_quant_async(self.h, arr, n, ctypes.byref(p), mptr, mstride, *flat)
         made = self._to_torch(who, outs, call, "vp8hip_frames_quant_async")
         return dict(zip(names, made))
+
+    def pack_bound(self, log2_parts=0):
+        """a `cap` that always suffices for a frame of frames_pack at the context's size (vp8hip_pack_bound): a multiple of 16, and
+        loose -- real frames are a hundredth of it"""
+        size = int(self.L.vp8hip_pack_bound(self.h, int(log2_parts)))
+        if not size:
+            raise ValueError(f"pack_bound: log2_parts {log2_parts} (0..3) of a configured context")
+        return size
+
+    def frames_pack(self, mv, coef, qindex=40, deltas=(0, 0, 0, 0, 0), cap=None, out_data=None, out_info=None, **fields):
+        """Compressed VP8 inter frames from frames_quant's levels and vectors on the context's device (vp8hip_frames_pack_async;
+        include/vp8hip.h has the definition): job i's frame -- tag, first partition, size table, 1 << log2_parts token partitions
+        -- from mv[i] and coef[i], byte for byte what the test suite's stream writer writes for the same content.  `mv`:
+        frames_subpel's torch.int16 tensor [n, 2, mb_rows, mb_cols] as it stands, None: (0, 0); `coef`: frames_quant's "levels"
+        tensor [n, mb_rows, mb_cols, 25, 16] (torch.int16, stride(0) a multiple of 16 bytes).  `qindex`: 0..127, or a sequence of
+        n; `deltas` as frames_quant's; fields: PACK_DEFAULTS' names (ref_frame 1..3, log2_parts 0..3, the probabilities 1..255
+        ...).  `cap`: the most bytes a frame may take, a multiple of 16 (default: out_data's second dimension where that is given, else
+        pack_bound(log2_parts), which at large sizes
+        makes the call's scratch large: pass what the content needs and watch PACK_OVERFLOW).  Returns (data, info): torch.uint8
+        [n, cap] and torch.int32 [n, 16] -- [0] the status (PACK_* bits), [1] the frame's bytes (0 where the status forbids),
+        [2] the first partition's, [3..10] the token partitions', [11] skipped macroblocks, [12..15] ZEROMV, NEARESTMV, NEARMV,
+        NEWMV macroblocks; pack_frames gives the frames as bytes.  out_data: a uint8 tensor [n, cap], pointer and stride(0)
+        multiples of 16; out_info: int32 [n, 16], contiguous.  Stream ordering, the `import torch` first rule and the remark on
+        record_stream: as frames_scaled."""
+        who = "frames_pack"
+        torch, dev = self._torch_device(who)
+        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
+        if not hasattr(coef, "shape") or len(coef.shape) != 5 or not self._dense(coef, torch.int16, (coef.shape[0], rows, cols, 25, 16), dev) or not coef.shape[0]:
+            raise ValueError(f"{who}: coef must be an int16 tensor {['n', rows, cols, 25, 16]}, each job dense, on {dev}")
+        n = int(coef.shape[0])
+        p, jq = _pack_params(who, qindex, deltas, fields, n)
+        mptr, mstride = None, 0
+        if mv is not None:
+            if not self._dense(mv, torch.int16, (n, 2, rows, cols), dev):
+                raise ValueError(f"{who}: mv must be an int16 tensor {[n, 2, rows, cols]}, each job dense, on {dev}")
+            mptr, mstride = c_void_p(mv.data_ptr()), mv.stride(0) * 2
+        if cap is None:
+            cap = int(out_data.shape[1]) if out_data is not None and len(out_data.shape) == 2 else int(self.L.vp8hip_pack_bound(self.h, p.log2_parts))
+        cap = int(cap)
+        if cap < 16 or cap % 16:
+            raise ValueError(f"{who}: cap {cap} (a multiple of 16; log2_parts 0..3)")
+        if out_info is not None and not (self._dense(out_info, torch.int32, (n, 16), dev) and out_info.is_contiguous()):
+            raise ValueError(f"{who}: out_info must be a contiguous int32 tensor {[n, 16]} on {dev}")
+        outs = [("out_data", out_data, "uint8", (n, cap)), ("out_info", out_info, "int32", (n, 16))]
+        made = self._to_torch(who, outs, lambda dp, ds, ip, istride: self.L.vp8hip_frames_pack_async(
+            self.h, n, ctypes.byref(p), mptr, mstride, c_void_p(coef.data_ptr()), coef.stride(0) * 2, dp, ds, cap, ip), "vp8hip_frames_pack_async")
+        del jq
+        return made[0], made[1]
 
     def ssim_share(self, n, planes=("y", "u", "v")):
         """how many workgroups share each job of a frames_ssim call of n jobs over `planes` (vp8hip_ssim_share): 1 -- a workgroup

@@ -1,0 +1,204 @@
+// vp8hip_frames_pack_async, vp8hip_pack_bound and vp8hip_pack_header (include/vp8hip.h): compressed VP8 inter frames from
+// frames_quant's levels and vectors, in the caller's device memory.  The checks and the plan are made here, once per call; the
+// kernels are in vp8_pack.hip.  The frame header is coded on the host, once per distinct qindex, and travels with its coder state
+// in the arguments of the launches (PackLaunch), so a call of many jobs is cut where those are full -- and where the scratch, the
+// buffer the RGB call keeps, would pass PACK_SCRATCH_MAX.
+#include "vp8hip_ctx.hip.h"
+#include "vp8_pack.hip.h"
+
+extern "C" __global__ void vp8_pack_plan_kernel(const uint8_t *mv, size_t mv_stride, const uint8_t *coef, size_t coef_stride, uint8_t *scratch, PackLaunch L);
+extern "C" __global__ void vp8_pack_first_kernel(uint8_t *scratch, int jobs, PackLaunch L);
+extern "C" __global__ void vp8_pack_tokens_kernel(const uint8_t *coef, size_t coef_stride, uint8_t *scratch, int jobs, PackLaunch L);
+extern "C" __global__ void vp8_pack_assemble_kernel(const uint8_t *scratch, uint8_t *dst, size_t dst_stride, uint32_t *info, PackLaunch L);
+
+#define PACK_SCRATCH_MAX ((size_t)2 << 30)      // the scratch of a launch group: at most this much (one job at least)
+#define PACK_PART_LIMIT (((size_t)1 << 24) - 16) // the size table has 24 bits for a token partition
+
+static_assert(sizeof(vp8hip_pack_head) == sizeof(PackHead) && offsetof(vp8hip_pack_head, bytes) == offsetof(PackHead, bytes) &&
+              VP8HIP_PACK_HEAD_MAX == PACK_HEAD_BYTES, "");
+static_assert(sizeof(PackLaunch) <= 3072, "the launch's arguments");
+
+// RFC 6386 section 7.3 as tests/vp8_writer.py's BoolEncoder states it: a carry walks back through the bytes written
+struct HostBool {
+    uint8_t *out;
+    size_t n, cap;
+    uint32_t range = 255, bottom = 0;
+    int bit_count = 24;
+    bool over = false;
+    void carry()
+    {
+        size_t i = n;
+        while (i > 0 && out[i - 1] == 255) out[--i] = 0;
+        if (i > 0) out[i - 1]++;
+    }
+    void put(int bit, int prob)
+    {
+        const uint32_t split = 1 + (((range - 1) * (uint32_t)prob) >> 8);
+        if (bit) { bottom += split; range -= split; } else range = split;
+        while (range < 128) {
+            range <<= 1;
+            if (bottom & (1u << 31)) carry();
+            bottom <<= 1;
+            if (!--bit_count) {
+                if (n < cap) out[n++] = (uint8_t)(bottom >> 24); else over = true;
+                bottom &= (1u << 24) - 1;
+                bit_count = 8;
+            }
+        }
+    }
+    void literal(int value, int bits) { for (int i = bits - 1; i >= 0; i--) put((value >> i) & 1, 128); }
+};
+
+static bool in(int v, int lo, int hi) { return v >= lo && v <= hi; }
+
+// what the call refuses on p alone (the qindex aside)
+static bool pack_params_ok(const vp8hip_pack *p)
+{
+    if (!p) return false;
+    for (int k = 0; k < 5; k++)
+        if (!in(p->delta[k], -15, 15)) return false;
+    for (int f : {p->show_frame, p->filter_type, p->refresh_last, p->refresh_golden, p->refresh_alt, p->sign_bias_golden, p->sign_bias_alt})
+        if (!in(f, 0, 1)) return false;
+    for (int pr : {p->prob_skip_false, p->prob_intra, p->prob_last, p->prob_gf})
+        if (!in(pr, 1, 255)) return false;
+    return in(p->version, 0, 3) && in(p->filter_level, 0, 63) && in(p->sharpness, 0, 7) && in(p->ref_frame, 1, 3) &&
+           in(p->copy_buffer_to_gf, 0, 2) && in(p->copy_buffer_to_arf, 0, 2) && in(p->log2_parts, 0, 3);
+}
+
+extern "C" int vp8hip_pack_header(const vp8hip_pack *p, int qindex, vp8hip_pack_head *out)
+{
+    if (!out || !pack_params_ok(p) || !in(qindex, 0, 127)) return -2;
+    memset(out, 0, sizeof *out);
+    HostBool e;
+    e.out = out->bytes; e.n = 0; e.cap = sizeof out->bytes;
+    e.literal(0, 1);                                         // segmentation_enabled
+    e.literal(p->filter_type, 1);
+    e.literal(p->filter_level, 6);
+    e.literal(p->sharpness, 3);
+    e.literal(0, 1);                                         // mode_ref_lf_delta_enabled
+    e.literal(p->log2_parts, 2);
+    e.literal(qindex, 7);
+    for (int k = 0; k < 5; k++) {
+        const int d = p->delta[k];
+        e.put(d != 0, 128);
+        if (d) { e.literal(d < 0 ? -d : d, 4); e.put(d < 0, 128); }
+    }
+    e.literal(p->refresh_golden, 1);
+    e.literal(p->refresh_alt, 1);
+    if (!p->refresh_golden) e.literal(p->copy_buffer_to_gf, 2);
+    if (!p->refresh_alt) e.literal(p->copy_buffer_to_arf, 2);
+    e.literal(p->sign_bias_golden, 1);
+    e.literal(p->sign_bias_alt, 1);
+    e.literal(1, 1);                                         // refresh_entropy_probs
+    e.literal(p->refresh_last, 1);
+    for (int i = 0; i < 1056; i++) e.put(0, pack_tables::vp8t_coef_update_probs[i]);
+    e.literal(1, 1);                                         // mb_no_coeff_skip
+    e.literal(p->prob_skip_false, 8);
+    e.literal(p->prob_intra, 8);
+    e.literal(p->prob_last, 8);
+    e.literal(p->prob_gf, 8);
+    e.literal(0, 2);                                         // the intra 16x16 and chroma probabilities stay
+    for (int i = 0; i < 38; i++) e.put(0, pack_tables::vp8t_mv_update_probs[i]);
+    if (e.over) return -1;
+    out->bottom = e.bottom; out->range = e.range; out->bit_count = (uint32_t)e.bit_count; out->nbytes = (uint32_t)e.n;
+    size_t i = e.n;
+    while (i > 0 && out->bytes[i - 1] == 255) i--;
+    out->cache = i ? out->bytes[i - 1] : -1;
+    out->settled = i ? (uint32_t)(i - 1) : 0;
+    out->pending = (uint32_t)(e.n - i);
+    return 0;
+}
+
+static size_t pack_first_bound(size_t nmb) { return PACK_HEAD_BYTES + 4 + PACK_MB_FIRST_BYTES * nmb + PACK_FLUSH_BYTES; }
+
+extern "C" size_t vp8hip_pack_bound(const vp8hip_ctx *c, int log2_parts)
+{
+    if (!c || !c->width || log2_parts < 0 || log2_parts > 3) return 0;
+    const size_t nmb = (size_t)c->dg.mb_cols * c->dg.mb_rows, parts = (size_t)1 << log2_parts;
+    return align_up(3 + pack_first_bound(nmb) + 3 * (parts - 1) + PACK_MB_TOKEN_BYTES * nmb + PACK_FLUSH_BYTES * parts, 16);
+}
+
+extern "C" int vp8hip_frames_pack_async(vp8hip_ctx *c, int n, const vp8hip_pack *p, const void *mv, size_t mv_stride, const void *coef,
+                                        size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info)
+{
+    const char *who = "vp8hip_frames_pack_async";
+    if (!c || n < 1 || !p || !coef || !dst || !info || !c->width) return fail(c, -2, "%s: bad arguments", who);
+    if (!pack_params_ok(p))
+        return fail(c, -2, "%s: version %d (0..3), flags %d %d %d %d %d %d %d (0, 1), filter level %d (0..63), sharpness %d (0..7), deltas %d %d %d %d %d "
+                    "(-15..15), ref_frame %d (1..3), buffer copies %d %d (0..2), log2_parts %d (0..3), probabilities %d %d %d %d (1..255)", who,
+                    p->version, p->show_frame, p->filter_type, p->refresh_last, p->refresh_golden, p->refresh_alt, p->sign_bias_golden,
+                    p->sign_bias_alt, p->filter_level, p->sharpness, p->delta[0], p->delta[1], p->delta[2], p->delta[3], p->delta[4], p->ref_frame,
+                    p->copy_buffer_to_gf, p->copy_buffer_to_arf, p->log2_parts, p->prob_skip_false, p->prob_intra, p->prob_last, p->prob_gf);
+    if (!p->job_qindex && (p->qindex < 0 || p->qindex > 127)) return fail(c, -2, "%s: qindex %d (0..127)", who, p->qindex);
+    if (p->job_qindex)
+        for (int i = 0; i < n; i++)
+            if (p->job_qindex[i] > 127) return fail(c, -2, "%s: job_qindex[%d] = %d (0..127)", who, i, p->job_qindex[i]);
+    if (cap < 16 || cap % 16 || cap > dst_stride) return fail(c, -2, "%s: cap %zu (a multiple of 16, 16 .. the stride %zu)", who, cap, dst_stride);
+    const size_t nmb = (size_t)c->dg.mb_cols * c->dg.mb_rows;
+    const struct { const void *p; size_t stride, size, align; const char *name; } t[4] = {
+        {dst, dst_stride, cap, 16, "dst"}, {info, 64, 64, 4, "info"}, {mv, mv_stride, 4 * nmb, 2, "mv"}, {coef, coef_stride, 800 * nmb, 16, "coef"}};
+    for (const auto &a : t)
+        if (a.p)
+            if (int rc = vp8hip_check_named_dst(c, who, a.name, a.p, a.stride, a.size, a.align, n)) return rc;
+    for (int a = 0; a < 2; a++)                              // the outputs against each other and against the inputs
+        for (int b = a + 1; b < 4; b++)
+            if (t[b].p && vp8hip_spans_overlap(t[a].p, t[a].stride, n, t[b].p, t[b].stride, n))
+                return fail(c, -2, "%s: %s and %s overlap", who, t[a].name, t[b].name);
+    HIPCHK(c, hipSetDevice(c->device));
+
+    PackLaunch L;
+    memset(&L, 0, sizeof(L));
+    const int parts = 1 << p->log2_parts;
+    L.mb_cols = c->dg.mb_cols; L.mb_rows = c->dg.mb_rows;
+    L.log2_parts = p->log2_parts; L.has_mv = mv != nullptr;
+    L.ref_frame = p->ref_frame;
+    L.prob_skip = p->prob_skip_false; L.prob_intra = p->prob_intra; L.prob_last = p->prob_last; L.prob_gf = p->prob_gf;
+    L.version = p->version; L.show_frame = p->show_frame;
+    // no frame is longer than the bound, no first partition than its own, no token partition than that of the most rows one has
+    const size_t bound = vp8hip_pack_bound(c, p->log2_parts), frame_limit = 3 + PACK_FIRST_LIMIT + 24 + 8 * PACK_PART_LIMIT;
+    const size_t eff = cap < bound ? cap : bound;
+    const size_t part_rows = ((size_t)c->dg.mb_rows + parts - 1) / parts;
+    const size_t part_bound = PACK_MB_TOKEN_BYTES * part_rows * c->dg.mb_cols + PACK_FLUSH_BYTES;
+    auto least = [](size_t a, size_t b, size_t d) { a = a < b ? a : b; return a < d ? a : d; };
+    L.cap = (uint32_t)(eff < frame_limit ? eff : frame_limit);
+    L.first_cap = (uint32_t)align_up(least(pack_first_bound(nmb), eff, PACK_FIRST_LIMIT), 16);
+    L.part_cap = (uint32_t)align_up(least(part_bound, eff, PACK_PART_LIMIT), 16);
+    L.job_bytes = PACK_RECORD_BYTES * nmb + L.first_cap + (size_t)parts * L.part_cap;
+    size_t chunk = n < PACK_MAX_JOBS ? n : PACK_MAX_JOBS;
+    const size_t fit = PACK_SCRATCH_MAX / (L.job_bytes + 4 * PACK_CTR_DWORDS);
+    if (chunk > fit) chunk = fit < 1 ? 1 : fit;
+    L.jobs_off = align_up(chunk * 4 * PACK_CTR_DWORDS, 256);
+    const size_t need = L.jobs_off + chunk * L.job_bytes;
+    // (launches in flight read the scratch: hipFree waits for them)
+    if (c->d_rgb.grow(need) != hipSuccess) return fail(c, -1, "%s: no device memory for %zu bytes of scratch", who, need);
+    uint8_t *scratch = c->d_rgb;
+
+    for (int i0 = 0; i0 < n;) {
+        int m = 0, heads = 0, qof[PACK_MAX_HEADS];
+        for (; i0 + m < n && m < (int)chunk; m++) {
+            const int q = p->job_qindex ? p->job_qindex[i0 + m] : p->qindex;
+            int k = 0;
+            while (k < heads && qof[k] != q) k++;
+            if (k == heads) {
+                if (heads == PACK_MAX_HEADS) break;
+                qof[heads] = q;
+                vp8hip_pack_head h;
+                if (vp8hip_pack_header(p, q, &h)) return fail(c, -1, "%s: the frame header does not fit %d bytes", who, VP8HIP_PACK_HEAD_MAX);
+                memcpy(&L.heads[heads++], &h, sizeof h);
+            }
+            L.head_of[m] = (uint8_t)k;
+        }
+        auto at = [i0](const void *ptr, size_t stride) { return ptr ? (uint8_t *)ptr + stride * (size_t)i0 : nullptr; };
+        HIPCHK(c, hipMemsetAsync(scratch, 0, (size_t)m * 4 * PACK_CTR_DWORDS, c->stream));
+        hipLaunchKernelGGL(vp8_pack_plan_kernel, dim3((unsigned)((nmb + 7) / 8), (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)at(mv, mv_stride),
+                           mv_stride, (const uint8_t *)at(coef, coef_stride), coef_stride, scratch, L);
+        hipLaunchKernelGGL(vp8_pack_first_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, c->stream, scratch, m, L);
+        hipLaunchKernelGGL(vp8_pack_tokens_kernel, dim3((unsigned)((m * parts + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t *)at(coef, coef_stride),
+                           coef_stride, scratch, m, L);
+        hipLaunchKernelGGL(vp8_pack_assemble_kernel, dim3((unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)scratch, at(dst, dst_stride), dst_stride,
+                           (uint32_t *)at(info, 64), L);
+        HIPCHK(c, hipGetLastError());
+        i0 += m;
+    }
+    return 0;
+}
