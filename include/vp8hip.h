@@ -1282,9 +1282,10 @@ int  vp8hip_frames_quant_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int
  * vp8hip_frames_pack_async takes that call's mv and coef tensors as they stand and writes, per job, one complete compressed VP8
  * inter frame (RFC 6386) into the caller's device memory: the 3-byte frame tag, the first partition, the partition size table, 1 to
  * 8 token partitions.  Nothing but the frame header's few fields goes through the host; it reads no frame buffer and no IR slot;
- * jobs are simply 0 .. n - 1.  Key frames and intra macroblocks, SPLITMV, segmentation and loop-filter deltas, probability updates
- * or adaptation (only the counts are handed out), the trellis, rate control, containers and chaining rec back in as the next
- * reference are not part of it.
+ * jobs are simply 0 .. n - 1.  Key frames and intra macroblocks, SPLITMV, segmentation and loop-filter deltas, the trellis, rate
+ * control, containers and chaining rec back in as the next reference are not part of it.  This call codes every frame with the
+ * default probability tables; probability updates and adaptation to the frame's own counts are
+ * vp8hip_frames_pack_adapt_async's, below.
  *
  * THE YARDSTICK for every byte is the stream writer of the test suite (tests/vp8_writer.py, write_inter_frame), written from RFC
  * 6386 and arbitrated by the real reference decoder.  A partition is flushed as its BoolEncoder.finish does: the bits of the byte in
@@ -1341,7 +1342,7 @@ int  vp8hip_frames_quant_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int
  * dst_stride, dst, cap and dst_stride multiples of 16.  info: job i's 16 uint32 at info + 64 i (a multiple of 4):
  *   [0] status   [1] frame bytes   [2] first partition bytes   [3..10] token partition bytes (0 for partitions the frame does not
  *   have)   [11] skipped macroblocks   [12..15] ZEROMV, NEARESTMV, NEARMV, NEWMV macroblocks
- * -- the counts are what a later call needs to choose prob_skip_false and to adapt probabilities; that choice is the caller's.
+ * -- the counts are what a later call needs to choose prob_skip_false; vp8hip_frames_pack_adapt_async makes that choice itself.
  * Status bits:
  *   VP8HIP_PACK_OVERFLOW    the frame does not fit cap, or its first partition exceeds the tag's 19 bits (or a token partition the
  *                           size table's 24);
@@ -1401,6 +1402,91 @@ size_t vp8hip_pack_bound(const vp8hip_ctx *ctx, int log2_parts);
 int  vp8hip_pack_header(const vp8hip_pack *p, int qindex, vp8hip_pack_head *out);
 int  vp8hip_frames_pack_async(vp8hip_ctx *ctx, int n, const vp8hip_pack *p, const void *mv, size_t mv_stride, const void *coef,
                               size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info);
+/* COMPRESSED INTER FRAMES WITH ADAPTED PROBABILITIES.  vp8hip_frames_pack_adapt_async is vp8hip_frames_pack_async -- the same
+ * inputs, macroblock modes, token order, partitions, flush and statuses -- except that each frame carries probabilities fitted to
+ * its own counts by the reference encoder's rules (vp8_update_coef_probs, vp8_write_mvprobs, the skip and reference counts),
+ * coded into its header wherever an update pays for itself, and is coded with them.  Counting, the choice and the header's
+ * probability section all happen on the device; vp8hip_frames_pack_async and its bytes are unchanged.
+ *
+ * vp8hip_pack_probs is a job's probability set, 1104 bytes: coef[4][8][3][11] (block type, band, context, tree node: RFC 6386
+ * 13.4), mvc[2][19] (row, column: is_short, sign, short[7] -- vp8_small_mvtree's nodes --, bits[10]: RFC 6386 17.2) and 10
+ * reserved bytes, written as 0 and never read.  vp8hip_pack_probs_default(out) fills the defaults (vp8_default_coef_probs,
+ * vp8_default_mv_context) on the host; NULL does nothing.
+ *
+ * vp8hip_pack_adapt: flags, any of VP8HIP_ADAPT_COEF, _MV, _SKIP, _REF; refresh_entropy_probs 0..1, the header bit; probs_in,
+ * DEVICE memory, job i's BASELINE set at probs_in + i * probs_in_stride (pointer and stride multiples of 16; a stride of 0: one set
+ * for all jobs), or NULL: the defaults.  The baseline is what a decoder holds when the frame arrives.
+ *
+ * 1. COUNTS.  Over the macroblocks that are not skipped, the reference's coef_counts[type][band][ctx][token] (tokenize.c): every
+ *    coded step of every block adds 1 at the block's type (luma 0 from step 1, Y2 1, chroma 2; type 3 stays zero), the step's band,
+ *    the context the token coder would use (above + left for the block's first step, then 0, 1 or 2 for a level of 0, +-1, more)
+ *    and its token: 0 for a zero, 1..4 for +-1..4, 5..10 for DCT_CAT1..6; the end of block adds 1 at token 11, with band and
+ *    context of the step behind the block's end, unless the block ends at step 15.  A block without a coded level is one end of
+ *    block at its first step.  Per component (row, then column) of every NEWMV macroblock, skipped or not, the coded difference
+ *    d = (v - best) / 2 is reduced as write_component_probs does, x = |d|: is_short_ct[x >= 8]; sign_ct[d < 0] if x; for x < 8
+ *    short_ct[x]; else bit_ct[k][(x >> k) & 1] for all ten k -- bit 3 too, though it is not always coded.
+ * 2. THE CHOICE, in unsigned 32-bit integers as the reference's.  cost(c0, c1, p) = (c0 * C[p] + c1 * C[255 - p]) >> 8 with C =
+ *    vp8_prob_cost (csrc/host/vp8_enc_tables.c).
+ *    COEF: per context the branch counts of its 12 token counts down vp8_coef_tree -- node 0 (end of block | any other), 1 (zero |
+ *    rest), 2 (one | rest), 3 (2..4 | categories), 4 (2 | 3, 4), 5 (3 | 4), 6 (CAT1, 2 | CAT3..6), 7 (CAT1 | CAT2), 8 (CAT3, 4 |
+ *    CAT5, 6), 9 (CAT3 | CAT4), 10 (CAT5 | CAT6); the end-of-block branch thus includes tokens that follow a zero, as the
+ *    reference's does.  newp = (c0 * 256 + (tot >> 1)) / tot with tot = c0 + c1, 0 becomes 1, above 255 becomes 255; tot 0: 128.  s
+ *    = cost(c0, c1, oldp) - cost(c0, c1, newp) - (8 + ((C[255 - upd] - C[upd]) >> 8)) with oldp the baseline and upd
+ *    vp8_coef_update_probs' entry; the probability is updated iff s > 0 (the reference's path without error resilience).
+ *    MV: per component c0, c1 of probability 0 = is_short_ct, 1 = sign_ct, 2..8 the branches of short_ct down vp8_small_mvtree
+ *    ((0..3 | 4..7), (0, 1 | 2, 3), (0 | 1), (2 | 3), (4, 5 | 6, 7), (4 | 5), (6 | 7)), 9 + k = bit_ct[k].  newp = ((c0 * 255) /
+ *    tot) & 254, 0 becomes 1; with tot 0 it is the DEFAULT context's value, not the baseline's, as in the reference.  It is updated
+ *    iff cost(c0, c1, oldp) - cost(c0, c1, newp) > 6 + ((C[255 - upd] - C[upd] + 128) >> 8), upd from vp8_mv_update_probs.
+ *    SKIP: prob_skip_false = (macroblocks not skipped) * 256 / macroblocks, clipped to 1..255.
+ *    REF: vp8_convert_rfct_to_prob for a frame whose macroblocks are all inter on p->ref_frame: prob_intra 1; prob_last 255 for
+ *    LAST, else 1; prob_gf 128 for LAST, 255 for GOLDEN, 1 for ALTREF.
+ *    Without its flag a part keeps the baseline -- p's values for skip and the reference probabilities -- and codes no update.
+ *    The EFFECTIVE set is the baseline with this frame's updates applied.
+ * 3. THE FRAME.  The header as vp8hip_frames_pack_async's with refresh_entropy_probs as given; each of the 1056 coefficient flags
+ *    is 1 where the probability is updated and then followed by the new value in 8 bits; the four header probabilities are the
+ *    chosen ones; each of the 38 vector flags likewise, followed by newp >> 1 in 7 bits (a decoder doubles it and turns 0 into 1:
+ *    newp again).  Macroblocks and tokens are coded with the effective set and the chosen prob_skip_false.
+ *
+ * OUTPUTS.  dst, dst_stride, cap: as vp8hip_frames_pack_async's.  info: job i's 32 uint32 at info + 128 i: [0..15] as that call's;
+ * [16] coefficient probabilities updated; [17] vector probabilities updated; [18] the prob_skip_false coded; [19] the sum of the
+ * positive s modulo 2^32, the reference's estimate of the saving in bits; [20..31] 0.  counts: NULL, or job i's 1216 uint32 at counts + 4864 i
+ * (a multiple of 4): the 1152 token counts [4][8][3][12], then per component (row, column) 32 branch counts: is_short_ct[2],
+ * sign_ct[2], short_ct[8], bit_ct[10][2] -- for callers with a rule of their own.  probs_out: NULL, or job i's effective set at
+ * probs_out + 1104 i (a multiple of 16): where refresh_entropy_probs is 1, the next frame's probs_in.  A job whose status has
+ * BAD_VECTOR or BAD_LEVEL counts nothing: its counts are 0, its probs_out the baseline, info[16..19] 0.  With OVERFLOW alone all of
+ * them are as defined.
+ *
+ * vp8hip_pack_adapt_bound(ctx, log2_parts): vp8hip_pack_bound plus the worst case of the probability section, derived the same
+ * way: 1056 flags with 8 literal bits, 35 literal bits, 38 flags with 7 literal bits are 9843 puts of at most 7 bits, 8613 bytes,
+ * rounded to 8624.  vp8hip_pack_header_prefix(p, qindex, refresh_entropy_probs, out): host only; the header through refresh_last,
+ * where the probability section begins, in vp8hip_pack_head's form; -2 as vp8hip_pack_header, or for refresh_entropy_probs
+ * outside 0..1.
+ *
+ * Stream, determinism (integer atomics only), scratch and its groups under 2 GB, and what is refused: as vp8hip_frames_pack_async,
+ * with 8320 more bytes of scratch a job; also -2 for a NULL a, flags outside 0..15, refresh_entropy_probs outside 0..1, probs_in,
+ * counts or probs_out that are misaligned, not device memory or too small for n jobs, a probs_in_stride between 1 and 1103, or
+ * info, counts, probs_out or dst overlapping each other or an input. */
+#define VP8HIP_ADAPT_COEF 1
+#define VP8HIP_ADAPT_MV   2
+#define VP8HIP_ADAPT_SKIP 4
+#define VP8HIP_ADAPT_REF  8
+typedef struct vp8hip_pack_probs {
+    uint8_t coef[4][8][3][11];
+    uint8_t mvc[2][19];
+    uint8_t reserved[10];
+} vp8hip_pack_probs;
+typedef struct vp8hip_pack_adapt {
+    int flags;                 /* VP8HIP_ADAPT_* */
+    int refresh_entropy_probs; /* 0..1 */
+    const void *probs_in;      /* device memory, or NULL: the defaults */
+    size_t probs_in_stride;    /* 0: one set for all jobs */
+} vp8hip_pack_adapt;
+void vp8hip_pack_probs_default(vp8hip_pack_probs *out);
+size_t vp8hip_pack_adapt_bound(const vp8hip_ctx *ctx, int log2_parts);
+int  vp8hip_pack_header_prefix(const vp8hip_pack *p, int qindex, int refresh_entropy_probs, vp8hip_pack_head *out);
+int  vp8hip_frames_pack_adapt_async(vp8hip_ctx *ctx, int n, const vp8hip_pack *p, const vp8hip_pack_adapt *a, const void *mv, size_t mv_stride,
+                                    const void *coef, size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info, void *counts,
+                                    void *probs_out);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

@@ -680,6 +680,40 @@ def pack_header(qindex=40, deltas=(0, 0, 0, 0, 0), **fields):
     return out
 
 
+ADAPT_COEF, ADAPT_MV, ADAPT_SKIP, ADAPT_REF = 1, 2, 4, 8     # VP8HIP_ADAPT_*: what Vp8Hip.frames_pack_adapt fits to the frame's counts
+ADAPT_ALL = 15
+PACK_PROBS_BYTES = 1104                                       # sizeof(vp8hip_pack_probs): coef [4][8][3][11], mvc [2][19], 10 reserved
+PACK_COUNTS = 1216                                            # a job's counts: token counts [4][8][3][12], then 2 x 32 vector branch counts
+
+
+def pack_probs_default():
+    """the default probability set of Vp8Hip.frames_pack_adapt (vp8hip_pack_probs_default; on the host): uint8 [1104] --
+    vp8_default_coef_probs [4][8][3][11], vp8_default_mv_context [2][19], 10 reserved bytes of 0"""
+    out = np.zeros(PACK_PROBS_BYTES, np.uint8)
+    load_hip().vp8hip_pack_probs_default(c_void_p(out.ctypes.data))
+    return out
+
+
+def pack_adapt_bound(w, h, log2_parts=0):
+    """a `cap` that always suffices for a frame of Vp8Hip.frames_pack_adapt at the display size w x h (vp8hip_pack_adapt_bound):
+    pack_bound plus 8624 bytes, the worst case of the header's probability section; 0 where pack_bound is 0"""
+    b = pack_bound(w, h, log2_parts)
+    return b + 8624 if b else 0
+
+
+def pack_header_prefix(qindex=40, deltas=(0, 0, 0, 0, 0), refresh_entropy_probs=1, **fields):
+    """the frame header of Vp8Hip.frames_pack_adapt's frames through refresh_last, where the probability section begins
+    (vp8hip_pack_header_prefix; on the host, no GPU): a dict as pack_header's"""
+    p, _ = _pack_params("pack_header_prefix", 0, deltas, fields)
+    h = PackHead()
+    if load_hip().vp8hip_pack_header_prefix(ctypes.byref(p), int(qindex), int(refresh_entropy_probs), ctypes.byref(h)):
+        raise ValueError(f"pack_header_prefix: qindex {qindex} (0..127), deltas {deltas!r} (-15..15), refresh_entropy_probs "
+                         f"{refresh_entropy_probs} (0, 1) or {fields!r} out of range")
+    out = {name: int(getattr(h, name)) for name in ("bottom", "range", "bit_count", "cache", "pending", "settled")}
+    out["bytes"] = bytes(h.bytes[:h.nbytes])
+    return out
+
+
 def pack_frames(data, info):
     """(data, info) of Vp8Hip.frames_pack (torch tensors or arrays) -> a list of each job's compressed frame as bytes, None where the
     job's status has PACK_OVERFLOW, PACK_BAD_VECTOR or PACK_BAD_LEVEL"""
@@ -916,6 +950,10 @@ class PackHead(ctypes.Structure):           # vp8hip_pack_head, include/vp8hip.h
                 ("bytes", ctypes.c_uint8 * 64)]
 
 
+class PackAdapt(ctypes.Structure):          # vp8hip_pack_adapt, include/vp8hip.h
+    _fields_ = [("flags", c_int), ("refresh_entropy_probs", c_int), ("probs_in", c_void_p), ("probs_in_stride", c_size_t)]
+
+
 class VisParams(ctypes.Structure):         # vp8hip_vis, include/vp8hip.h
     _fields_ = [("flags", ctypes.c_uint), ("ref_frame_mask", c_int), ("mb_modes_mask", c_int), ("b_modes_mask", c_int),
                 ("mv_mask", c_int), ("frame_info", ctypes.c_char_p), ("rate_info", ctypes.c_char_p)]
@@ -1049,6 +1087,13 @@ def load_hip():
         L.vp8hip_pack_header.argtypes = [ctypes.POINTER(PackParams), c_int, ctypes.POINTER(PackHead)]
         L.vp8hip_frames_pack_async.argtypes = [c_void_p, c_int, ctypes.POINTER(PackParams), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
                                                c_size_t, c_void_p]
+        L.vp8hip_pack_adapt_bound.argtypes = [c_void_p, c_int]
+        L.vp8hip_pack_adapt_bound.restype = c_size_t
+        L.vp8hip_pack_probs_default.argtypes = [c_void_p]
+        L.vp8hip_pack_probs_default.restype = None
+        L.vp8hip_pack_header_prefix.argtypes = [ctypes.POINTER(PackParams), c_int, c_int, ctypes.POINTER(PackHead)]
+        L.vp8hip_frames_pack_adapt_async.argtypes = [c_void_p, c_int, ctypes.POINTER(PackParams), ctypes.POINTER(PackAdapt), c_void_p, c_size_t, c_void_p,
+                                                     c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -2055,6 +2100,68 @@ class Vp8Hip:
             self.h, n, ctypes.byref(p), mptr, mstride, c_void_p(coef.data_ptr()), coef.stride(0) * 2, dp, ds, cap, ip), "vp8hip_frames_pack_async")
         del jq
         return made[0], made[1]
+
+    def pack_adapt_bound(self, log2_parts=0):
+        """a `cap` that always suffices for a frame of frames_pack_adapt at the context's size (vp8hip_pack_adapt_bound)"""
+        size = int(self.L.vp8hip_pack_adapt_bound(self.h, int(log2_parts)))
+        if not size:
+            raise ValueError(f"pack_adapt_bound: log2_parts {log2_parts} (0..3) of a configured context")
+        return size
+
+    def frames_pack_adapt(self, mv, coef, qindex=40, deltas=(0, 0, 0, 0, 0), cap=None, flags=ADAPT_ALL, refresh_entropy_probs=1, probs_in=None,
+                          counts=False, probs=False, out_data=None, out_info=None, out_counts=None, out_probs=None, **fields):
+        """frames_pack with probabilities fitted to each frame's own counts by the reference encoder's rules and coded into its
+        header where an update pays for itself (vp8hip_frames_pack_adapt_async; include/vp8hip.h has the definition).  mv, coef,
+        qindex, deltas, cap (default: pack_adapt_bound), out_data and the fields: as frames_pack.  `flags`: ADAPT_COEF | ADAPT_MV |
+        ADAPT_SKIP | ADAPT_REF, what is fitted; the rest keeps the baseline (for skip and the reference probabilities: the
+        fields' values) and codes no update.  `refresh_entropy_probs`: the header bit.  `probs_in`: the baseline set(s), a
+        torch.uint8 tensor [1104] (one for all jobs) or [n, 1104] (stride(0) and pointer multiples of 16) on the device, None:
+        the defaults (pack_probs_default).  Returns (data, info, counts, probs): torch.uint8 [n, cap]; torch.int32 [n, 32] --
+        [0..15] as frames_pack's, [16] coefficient probabilities updated, [17] vector probabilities updated, [18] the
+        prob_skip_false coded, [19] the estimated saving in bits, the rest 0 --; with `counts` (or out_counts, int32 [n, 1216],
+        contiguous) the token counts [4][8][3][12] and 2 x 32 vector branch counts, else None; with `probs` (or out_probs, uint8
+        [n, 1104], contiguous, 16-byte aligned) the effective sets -- the next frame's probs_in where refresh_entropy_probs is 1
+        --, else None."""
+        who = "frames_pack_adapt"
+        torch, dev = self._torch_device(who)
+        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
+        if not hasattr(coef, "shape") or len(coef.shape) != 5 or not self._dense(coef, torch.int16, (coef.shape[0], rows, cols, 25, 16), dev) or not coef.shape[0]:
+            raise ValueError(f"{who}: coef must be an int16 tensor {['n', rows, cols, 25, 16]}, each job dense, on {dev}")
+        n = int(coef.shape[0])
+        p, jq = _pack_params(who, qindex, deltas, fields, n)
+        mptr, mstride = None, 0
+        if mv is not None:
+            if not self._dense(mv, torch.int16, (n, 2, rows, cols), dev):
+                raise ValueError(f"{who}: mv must be an int16 tensor {[n, 2, rows, cols]}, each job dense, on {dev}")
+            mptr, mstride = c_void_p(mv.data_ptr()), mv.stride(0) * 2
+        a = PackAdapt(int(flags), int(refresh_entropy_probs), None, 0)
+        if probs_in is not None:
+            one = hasattr(probs_in, "shape") and len(probs_in.shape) == 1
+            shape = (PACK_PROBS_BYTES,) if one else (n, PACK_PROBS_BYTES)
+            if not hasattr(probs_in, "shape") or tuple(probs_in.shape) != shape or probs_in.dtype != torch.uint8 or probs_in.device != dev or probs_in.stride(-1) != 1:
+                raise ValueError(f"{who}: probs_in must be a uint8 tensor [{PACK_PROBS_BYTES}] or {[n, PACK_PROBS_BYTES]}, each set dense, on {dev}")
+            a.probs_in, a.probs_in_stride = probs_in.data_ptr(), 0 if one else probs_in.stride(0)
+        if cap is None:
+            cap = int(out_data.shape[1]) if out_data is not None and len(out_data.shape) == 2 else int(self.L.vp8hip_pack_adapt_bound(self.h, p.log2_parts))
+        cap = int(cap)
+        if cap < 16 or cap % 16:
+            raise ValueError(f"{who}: cap {cap} (a multiple of 16; log2_parts 0..3)")
+        outs = [("out_data", out_data, "uint8", (n, cap)), ("out_info", out_info, "int32", (n, 32))]
+        if counts or out_counts is not None:
+            outs.append(("out_counts", out_counts, "int32", (n, PACK_COUNTS)))
+        if probs or out_probs is not None:
+            outs.append(("out_probs", out_probs, "uint8", (n, PACK_PROBS_BYTES)))
+        for arg, t, _, _ in outs[1:]:
+            if t is not None and not t.is_contiguous():
+                raise ValueError(f"{who}: {arg} must be contiguous")
+
+        def call(dp, ds, ip, istride, *rest):
+            opt = dict(zip([o[0] for o in outs[2:]], rest[0::2]))
+            return self.L.vp8hip_frames_pack_adapt_async(self.h, n, ctypes.byref(p), ctypes.byref(a), mptr, mstride, c_void_p(coef.data_ptr()),
+                                                         coef.stride(0) * 2, dp, ds, cap, ip, opt.get("out_counts"), opt.get("out_probs"))
+        made = dict(zip([o[0] for o in outs], self._to_torch(who, outs, call, "vp8hip_frames_pack_adapt_async")))
+        del jq
+        return made["out_data"], made["out_info"], made.get("out_counts"), made.get("out_probs")
 
     def ssim_share(self, n, planes=("y", "u", "v")):
         """how many workgroups share each job of a frames_ssim call of n jobs over `planes` (vp8hip_ssim_share): 1 -- a workgroup

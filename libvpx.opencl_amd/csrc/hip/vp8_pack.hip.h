@@ -59,6 +59,45 @@ struct PackLaunch {
     uint8_t head_of[PACK_MAX_JOBS];
 };
 
+// vp8hip_frames_pack_adapt_async adds, behind the last job's area (adapt_off, a multiple of 256), PACK_ADAPT_JOB_BYTES a job:
+//   PACK_ADAPT_COUNTS  1216 uint32: the token counts [4][8][3][12], then per vector component (row, column) 32 branch counts:
+//                      is_short_ct[2], sign_ct[2], short_ct[8], bit_ct[10][2] (the count kernel adds to them; zeroed before it)
+//   PACK_ADAPT_EFF     the effective probability set, vp8hip_pack_probs' 1104 bytes
+//   PACK_ADAPT_FLAG    1104 bytes: 1 where the frame codes an update of that probability
+//   PACK_ADAPT_ROWS    the effective coefficient table as the token coder's LDS holds it: 96 rows of 12 bytes
+//   PACK_ADAPT_HDR     8 uint32: info[16..19], then prob_intra, prob_last, prob_gf as coded ([2] is prob_skip_false)
+// and, at info_off, the 16 uint32 a job that the assemble kernel writes (the call's info has 32).
+#define PACK_PROBS_BYTES 1104           // sizeof(vp8hip_pack_probs)
+#define PACK_ADAPT_COUNT_DWORDS 1216
+#define PACK_ADAPT_COUNTS 0
+#define PACK_ADAPT_EFF 4864
+#define PACK_ADAPT_FLAG (PACK_ADAPT_EFF + PACK_PROBS_BYTES)
+#define PACK_ADAPT_ROWS (PACK_ADAPT_FLAG + PACK_PROBS_BYTES)
+#define PACK_ADAPT_HDR (PACK_ADAPT_ROWS + 1152)
+#define PACK_ADAPT_JOB_BYTES (PACK_ADAPT_HDR + 32)
+#define PACK_ADAPT_HDR_SKIP 2
+#define PACK_ADAPT_HDR_INTRA 4
+#define PACK_ADAPT_HDR_LAST 5
+#define PACK_ADAPT_HDR_GF 6
+// The update section behind the host's header prefix: 1056 flags with 8 literal bits each, 35 literal bits (mb_no_coeff_skip, the
+// four header probabilities, the two intra update flags), 38 flags with 7 literal bits each: 9843 puts of at most 7 bits, 8613
+// bytes, rounded up to a multiple of 16
+#define PACK_ADAPT_UPDATE_BYTES 8624
+
+#define PACK_ADAPT_COEF 1
+#define PACK_ADAPT_MV 2
+#define PACK_ADAPT_SKIP 4
+#define PACK_ADAPT_REF 8
+
+struct PackAdapt {
+    size_t adapt_off, info_off;
+    const uint8_t *probs_in;            // NULL: the defaults
+    size_t probs_in_stride;
+    uint32_t *info, *counts;            // the call's (32 and 1216 uint32 a job); counts may be NULL
+    uint8_t *probs_out;                 // 1104 bytes a job, or NULL
+    int flags;
+};
+
 // The record of a macroblock, eight dwords: [0] bits 0..24 "block b has a coded level" (b as in frames_quant's coef: Y 0..15, U, V,
 // Y2 24; none set: the macroblock is skipped), bits 25..26 the mode (0 ZEROMV, 1 NEARESTMV, 2 NEARMV, 3 NEWMV); [1..5] the blocks'
 // ends -- 1 + the last coded zigzag step, 0 for none --, five bits each, six to a dword; [6] the four mode probabilities the

@@ -1,6 +1,7 @@
-// vp8hip_frames_pack_async, vp8hip_pack_bound and vp8hip_pack_header (include/vp8hip.h): compressed VP8 inter frames from
-// frames_quant's levels and vectors, in the caller's device memory.  The checks and the plan are made here, once per call; the
-// kernels are in vp8_pack.hip.  The frame header is coded on the host, once per distinct qindex, and travels with its coder state
+// vp8hip_frames_pack_async, vp8hip_pack_bound and vp8hip_pack_header, and vp8hip_frames_pack_adapt_async with its bound, header
+// prefix and default set (include/vp8hip.h): compressed VP8 inter frames from frames_quant's levels and vectors, in the caller's
+// device memory.  The checks and the plan are made here, once per call, by one function for both calls; the kernels are in
+// vp8_pack.hip and vp8_pack_adapt.hip.  The frame header is coded on the host, once per distinct qindex, and travels with its coder state
 // in the arguments of the launches (PackLaunch), so a call of many jobs is cut where those are full -- and where the scratch, the
 // buffer the RGB call keeps, would pass PACK_SCRATCH_MAX.
 #include "vp8hip_ctx.hip.h"
@@ -10,13 +11,22 @@ extern "C" __global__ void vp8_pack_plan_kernel(const uint8_t *mv, size_t mv_str
 extern "C" __global__ void vp8_pack_first_kernel(uint8_t *scratch, int jobs, PackLaunch L);
 extern "C" __global__ void vp8_pack_tokens_kernel(const uint8_t *coef, size_t coef_stride, uint8_t *scratch, int jobs, PackLaunch L);
 extern "C" __global__ void vp8_pack_assemble_kernel(const uint8_t *scratch, uint8_t *dst, size_t dst_stride, uint32_t *info, PackLaunch L);
+// vp8_pack_adapt.hip
+extern "C" __global__ void vp8_pack_count_kernel(const uint8_t *coef, size_t coef_stride, uint8_t *scratch, PackLaunch L, PackAdapt A);
+extern "C" __global__ void vp8_pack_choose_kernel(uint8_t *scratch, PackLaunch L, PackAdapt A);
+extern "C" __global__ void vp8_pack_first_adapt_kernel(uint8_t *scratch, int jobs, PackLaunch L, PackAdapt A);
+extern "C" __global__ void vp8_pack_tokens_adapt_kernel(const uint8_t *coef, size_t coef_stride, uint8_t *scratch, int jobs, PackLaunch L, PackAdapt A);
+extern "C" __global__ void vp8_pack_adapt_info_kernel(const uint8_t *scratch, int jobs, PackAdapt A);
 
 #define PACK_SCRATCH_MAX ((size_t)2 << 30)      // the scratch of a launch group: at most this much (one job at least)
 #define PACK_PART_LIMIT (((size_t)1 << 24) - 16) // the size table has 24 bits for a token partition
 
 static_assert(sizeof(vp8hip_pack_head) == sizeof(PackHead) && offsetof(vp8hip_pack_head, bytes) == offsetof(PackHead, bytes) &&
               VP8HIP_PACK_HEAD_MAX == PACK_HEAD_BYTES, "");
-static_assert(sizeof(PackLaunch) <= 3072, "the launch's arguments");
+static_assert(sizeof(PackLaunch) + sizeof(PackAdapt) <= 3072, "the launch's arguments");
+static_assert(sizeof(vp8hip_pack_probs) == PACK_PROBS_BYTES && offsetof(vp8hip_pack_probs, mvc) == 1056, "");
+static_assert(VP8HIP_ADAPT_COEF == PACK_ADAPT_COEF && VP8HIP_ADAPT_MV == PACK_ADAPT_MV && VP8HIP_ADAPT_SKIP == PACK_ADAPT_SKIP &&
+              VP8HIP_ADAPT_REF == PACK_ADAPT_REF, "");
 
 // RFC 6386 section 7.3 as tests/vp8_writer.py's BoolEncoder states it: a carry walks back through the bytes written
 struct HostBool {
@@ -65,9 +75,11 @@ static bool pack_params_ok(const vp8hip_pack *p)
            in(p->copy_buffer_to_gf, 0, 2) && in(p->copy_buffer_to_arf, 0, 2) && in(p->log2_parts, 0, 3);
 }
 
-extern "C" int vp8hip_pack_header(const vp8hip_pack *p, int qindex, vp8hip_pack_head *out)
+// the header through refresh_last (prefix: vp8hip_pack_header_prefix) or to where the per-macroblock data begin, with no update
+// (vp8hip_pack_header), and the coder's state there
+static int pack_header_to(const vp8hip_pack *p, int qindex, int refresh_entropy_probs, bool prefix, vp8hip_pack_head *out)
 {
-    if (!out || !pack_params_ok(p) || !in(qindex, 0, 127)) return -2;
+    if (!out || !pack_params_ok(p) || !in(qindex, 0, 127) || !in(refresh_entropy_probs, 0, 1)) return -2;
     memset(out, 0, sizeof *out);
     HostBool e;
     e.out = out->bytes; e.n = 0; e.cap = sizeof out->bytes;
@@ -89,16 +101,18 @@ extern "C" int vp8hip_pack_header(const vp8hip_pack *p, int qindex, vp8hip_pack_
     if (!p->refresh_alt) e.literal(p->copy_buffer_to_arf, 2);
     e.literal(p->sign_bias_golden, 1);
     e.literal(p->sign_bias_alt, 1);
-    e.literal(1, 1);                                         // refresh_entropy_probs
+    e.literal(refresh_entropy_probs, 1);
     e.literal(p->refresh_last, 1);
-    for (int i = 0; i < 1056; i++) e.put(0, pack_tables::vp8t_coef_update_probs[i]);
-    e.literal(1, 1);                                         // mb_no_coeff_skip
-    e.literal(p->prob_skip_false, 8);
-    e.literal(p->prob_intra, 8);
-    e.literal(p->prob_last, 8);
-    e.literal(p->prob_gf, 8);
-    e.literal(0, 2);                                         // the intra 16x16 and chroma probabilities stay
-    for (int i = 0; i < 38; i++) e.put(0, pack_tables::vp8t_mv_update_probs[i]);
+    if (!prefix) {
+        for (int i = 0; i < 1056; i++) e.put(0, pack_tables::vp8t_coef_update_probs[i]);
+        e.literal(1, 1);                                     // mb_no_coeff_skip
+        e.literal(p->prob_skip_false, 8);
+        e.literal(p->prob_intra, 8);
+        e.literal(p->prob_last, 8);
+        e.literal(p->prob_gf, 8);
+        e.literal(0, 2);                                     // the intra 16x16 and chroma probabilities stay
+        for (int i = 0; i < 38; i++) e.put(0, pack_tables::vp8t_mv_update_probs[i]);
+    }
     if (e.over) return -1;
     out->bottom = e.bottom; out->range = e.range; out->bit_count = (uint32_t)e.bit_count; out->nbytes = (uint32_t)e.n;
     size_t i = e.n;
@@ -109,19 +123,40 @@ extern "C" int vp8hip_pack_header(const vp8hip_pack *p, int qindex, vp8hip_pack_
     return 0;
 }
 
-static size_t pack_first_bound(size_t nmb) { return PACK_HEAD_BYTES + 4 + PACK_MB_FIRST_BYTES * nmb + PACK_FLUSH_BYTES; }
+extern "C" int vp8hip_pack_header(const vp8hip_pack *p, int qindex, vp8hip_pack_head *out) { return pack_header_to(p, qindex, 1, false, out); }
 
-extern "C" size_t vp8hip_pack_bound(const vp8hip_ctx *c, int log2_parts)
+extern "C" int vp8hip_pack_header_prefix(const vp8hip_pack *p, int qindex, int refresh_entropy_probs, vp8hip_pack_head *out)
+{
+    return pack_header_to(p, qindex, refresh_entropy_probs, true, out);
+}
+
+extern "C" void vp8hip_pack_probs_default(vp8hip_pack_probs *out)
+{
+    if (!out) return;
+    memset(out, 0, sizeof *out);
+    memcpy(out->coef, pack_tables::vp8t_default_coef_probs, sizeof out->coef);
+    memcpy(out->mvc, pack_tables::vp8t_default_mv_context, sizeof out->mvc);
+}
+
+// `update`: the bytes of the probability section where the device codes it (PACK_ADAPT_UPDATE_BYTES), else 0
+static size_t pack_first_bound(size_t nmb, size_t update) { return PACK_HEAD_BYTES + 4 + update + PACK_MB_FIRST_BYTES * nmb + PACK_FLUSH_BYTES; }
+
+static size_t pack_bound(const vp8hip_ctx *c, int log2_parts, size_t update)
 {
     if (!c || !c->width || log2_parts < 0 || log2_parts > 3) return 0;
     const size_t nmb = (size_t)c->dg.mb_cols * c->dg.mb_rows, parts = (size_t)1 << log2_parts;
-    return align_up(3 + pack_first_bound(nmb) + 3 * (parts - 1) + PACK_MB_TOKEN_BYTES * nmb + PACK_FLUSH_BYTES * parts, 16);
+    return align_up(3 + pack_first_bound(nmb, update) + 3 * (parts - 1) + PACK_MB_TOKEN_BYTES * nmb + PACK_FLUSH_BYTES * parts, 16);
 }
 
-extern "C" int vp8hip_frames_pack_async(vp8hip_ctx *c, int n, const vp8hip_pack *p, const void *mv, size_t mv_stride, const void *coef,
-                                        size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info)
+extern "C" size_t vp8hip_pack_bound(const vp8hip_ctx *c, int log2_parts) { return pack_bound(c, log2_parts, 0); }
+extern "C" size_t vp8hip_pack_adapt_bound(const vp8hip_ctx *c, int log2_parts) { return pack_bound(c, log2_parts, PACK_ADAPT_UPDATE_BYTES); }
+
+// The plan of both calls.  a == NULL: vp8hip_frames_pack_async -- the four kernels of vp8_pack.hip, info 16 uint32 a job.  Else
+// vp8hip_frames_pack_adapt_async: count and choose behind the plan kernel, the coders' ADAPT variants, and the assemble kernel's
+// 16 uint32 go to the scratch, from where the info kernel makes the call's 32.
+static int pack_frames(vp8hip_ctx *c, const char *who, int n, const vp8hip_pack *p, const vp8hip_pack_adapt *a, const void *mv, size_t mv_stride,
+                       const void *coef, size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info, void *counts, void *probs_out)
 {
-    const char *who = "vp8hip_frames_pack_async";
     if (!c || n < 1 || !p || !coef || !dst || !info || !c->width) return fail(c, -2, "%s: bad arguments", who);
     if (!pack_params_ok(p))
         return fail(c, -2, "%s: version %d (0..3), flags %d %d %d %d %d %d %d (0, 1), filter level %d (0..63), sharpness %d (0..7), deltas %d %d %d %d %d "
@@ -134,16 +169,24 @@ extern "C" int vp8hip_frames_pack_async(vp8hip_ctx *c, int n, const vp8hip_pack 
         for (int i = 0; i < n; i++)
             if (p->job_qindex[i] > 127) return fail(c, -2, "%s: job_qindex[%d] = %d (0..127)", who, i, p->job_qindex[i]);
     if (cap < 16 || cap % 16 || cap > dst_stride) return fail(c, -2, "%s: cap %zu (a multiple of 16, 16 .. the stride %zu)", who, cap, dst_stride);
-    const size_t nmb = (size_t)c->dg.mb_cols * c->dg.mb_rows;
-    const struct { const void *p; size_t stride, size, align; const char *name; } t[4] = {
-        {dst, dst_stride, cap, 16, "dst"}, {info, 64, 64, 4, "info"}, {mv, mv_stride, 4 * nmb, 2, "mv"}, {coef, coef_stride, 800 * nmb, 16, "coef"}};
-    for (const auto &a : t)
-        if (a.p)
-            if (int rc = vp8hip_check_named_dst(c, who, a.name, a.p, a.stride, a.size, a.align, n)) return rc;
-    for (int a = 0; a < 2; a++)                              // the outputs against each other and against the inputs
-        for (int b = a + 1; b < 4; b++)
-            if (t[b].p && vp8hip_spans_overlap(t[a].p, t[a].stride, n, t[b].p, t[b].stride, n))
-                return fail(c, -2, "%s: %s and %s overlap", who, t[a].name, t[b].name);
+    if (a && (!in(a->flags, 0, 15) || !in(a->refresh_entropy_probs, 0, 1)))
+        return fail(c, -2, "%s: flags %d (VP8HIP_ADAPT_* bits), refresh_entropy_probs %d (0, 1)", who, a->flags, a->refresh_entropy_probs);
+    const size_t nmb = (size_t)c->dg.mb_cols * c->dg.mb_rows, info_bytes = a ? 128 : 64;
+    const void *probs_in = a ? a->probs_in : nullptr;
+    const bool one_set = a && !a->probs_in_stride;           // stride 0: one baseline for all jobs
+    // the outputs first, then the inputs
+    const struct { const void *p; size_t stride, size, align; int n; const char *name; } t[7] = {
+        {dst, dst_stride, cap, 16, n, "dst"}, {info, info_bytes, info_bytes, 4, n, "info"},
+        {counts, 4 * PACK_ADAPT_COUNT_DWORDS, 4 * PACK_ADAPT_COUNT_DWORDS, 4, n, "counts"}, {probs_out, PACK_PROBS_BYTES, PACK_PROBS_BYTES, 16, n, "probs_out"},
+        {mv, mv_stride, 4 * nmb, 2, n, "mv"}, {coef, coef_stride, 800 * nmb, 16, n, "coef"},
+        {probs_in, one_set ? PACK_PROBS_BYTES : a ? a->probs_in_stride : 0, PACK_PROBS_BYTES, 16, one_set ? 1 : n, "probs_in"}};
+    for (const auto &s : t)
+        if (s.p)
+            if (int rc = vp8hip_check_named_dst(c, who, s.name, s.p, s.stride, s.size, s.align, s.n)) return rc;
+    for (int i = 0; i < 4; i++)                              // the outputs against each other and against the inputs
+        for (int j = i + 1; j < 7; j++)
+            if (t[i].p && t[j].p && vp8hip_spans_overlap(t[i].p, t[i].stride, t[i].n, t[j].p, t[j].stride, t[j].n))
+                return fail(c, -2, "%s: %s and %s overlap", who, t[i].name, t[j].name);
     HIPCHK(c, hipSetDevice(c->device));
 
     PackLaunch L;
@@ -154,21 +197,34 @@ extern "C" int vp8hip_frames_pack_async(vp8hip_ctx *c, int n, const vp8hip_pack 
     L.ref_frame = p->ref_frame;
     L.prob_skip = p->prob_skip_false; L.prob_intra = p->prob_intra; L.prob_last = p->prob_last; L.prob_gf = p->prob_gf;
     L.version = p->version; L.show_frame = p->show_frame;
+    if (a && (a->flags & VP8HIP_ADAPT_REF)) {
+        // vp8_convert_rfct_to_prob of a frame whose macroblocks are all inter on ref_frame: 0 * 255 / n = 0 becomes 1; LAST or GOLDEN
+        // n * 255 / n = 255; prob_gf of a frame without GOLDEN and ALTREF macroblocks 128
+        L.prob_intra = 1;
+        L.prob_last = p->ref_frame == 1 ? 255 : 1;
+        L.prob_gf = p->ref_frame == 1 ? 128 : p->ref_frame == 2 ? 255 : 1;
+    }
     // no frame is longer than the bound, no first partition than its own, no token partition than that of the most rows one has
-    const size_t bound = vp8hip_pack_bound(c, p->log2_parts), frame_limit = 3 + PACK_FIRST_LIMIT + 24 + 8 * PACK_PART_LIMIT;
+    const size_t update = a ? PACK_ADAPT_UPDATE_BYTES : 0;
+    const size_t bound = pack_bound(c, p->log2_parts, update), frame_limit = 3 + PACK_FIRST_LIMIT + 24 + 8 * PACK_PART_LIMIT;
     const size_t eff = cap < bound ? cap : bound;
     const size_t part_rows = ((size_t)c->dg.mb_rows + parts - 1) / parts;
     const size_t part_bound = PACK_MB_TOKEN_BYTES * part_rows * c->dg.mb_cols + PACK_FLUSH_BYTES;
     auto least = [](size_t a, size_t b, size_t d) { a = a < b ? a : b; return a < d ? a : d; };
     L.cap = (uint32_t)(eff < frame_limit ? eff : frame_limit);
-    L.first_cap = (uint32_t)align_up(least(pack_first_bound(nmb), eff, PACK_FIRST_LIMIT), 16);
+    L.first_cap = (uint32_t)align_up(least(pack_first_bound(nmb, update), eff, PACK_FIRST_LIMIT), 16);
     L.part_cap = (uint32_t)align_up(least(part_bound, eff, PACK_PART_LIMIT), 16);
     L.job_bytes = PACK_RECORD_BYTES * nmb + L.first_cap + (size_t)parts * L.part_cap;
+    const size_t adapt_job = a ? PACK_ADAPT_JOB_BYTES + 64 : 0;  // (the adapt area and the assemble kernel's info)
     size_t chunk = n < PACK_MAX_JOBS ? n : PACK_MAX_JOBS;
-    const size_t fit = PACK_SCRATCH_MAX / (L.job_bytes + 4 * PACK_CTR_DWORDS);
+    const size_t fit = (PACK_SCRATCH_MAX - (a ? 512 : 0)) / (L.job_bytes + 4 * PACK_CTR_DWORDS + adapt_job);     // (512: the two roundings to 256)
     if (chunk > fit) chunk = fit < 1 ? 1 : fit;
     L.jobs_off = align_up(chunk * 4 * PACK_CTR_DWORDS, 256);
-    const size_t need = L.jobs_off + chunk * L.job_bytes;
+    PackAdapt A;
+    memset(&A, 0, sizeof(A));
+    A.adapt_off = align_up(L.jobs_off + chunk * L.job_bytes, 256);
+    A.info_off = A.adapt_off + chunk * PACK_ADAPT_JOB_BYTES;
+    const size_t need = a ? A.info_off + chunk * 64 : L.jobs_off + chunk * L.job_bytes;
     // (launches in flight read the scratch: hipFree waits for them)
     if (c->d_rgb.grow(need) != hipSuccess) return fail(c, -1, "%s: no device memory for %zu bytes of scratch", who, need);
     uint8_t *scratch = c->d_rgb;
@@ -183,22 +239,56 @@ extern "C" int vp8hip_frames_pack_async(vp8hip_ctx *c, int n, const vp8hip_pack 
                 if (heads == PACK_MAX_HEADS) break;
                 qof[heads] = q;
                 vp8hip_pack_head h;
-                if (vp8hip_pack_header(p, q, &h)) return fail(c, -1, "%s: the frame header does not fit %d bytes", who, VP8HIP_PACK_HEAD_MAX);
+                if (pack_header_to(p, q, a ? a->refresh_entropy_probs : 1, a != nullptr, &h))
+                    return fail(c, -1, "%s: the frame header does not fit %d bytes", who, VP8HIP_PACK_HEAD_MAX);
                 memcpy(&L.heads[heads++], &h, sizeof h);
             }
             L.head_of[m] = (uint8_t)k;
         }
         auto at = [i0](const void *ptr, size_t stride) { return ptr ? (uint8_t *)ptr + stride * (size_t)i0 : nullptr; };
+        const dim3 plan_grid((unsigned)((nmb + 7) / 8), (unsigned)m), first_grid((unsigned)((m + 63) / 64)), tokens_grid((unsigned)((m * parts + 63) / 64));
+        const uint8_t *mv_at = (const uint8_t *)at(mv, mv_stride), *coef_at = (const uint8_t *)at(coef, coef_stride);
         HIPCHK(c, hipMemsetAsync(scratch, 0, (size_t)m * 4 * PACK_CTR_DWORDS, c->stream));
-        hipLaunchKernelGGL(vp8_pack_plan_kernel, dim3((unsigned)((nmb + 7) / 8), (unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)at(mv, mv_stride),
-                           mv_stride, (const uint8_t *)at(coef, coef_stride), coef_stride, scratch, L);
-        hipLaunchKernelGGL(vp8_pack_first_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, c->stream, scratch, m, L);
-        hipLaunchKernelGGL(vp8_pack_tokens_kernel, dim3((unsigned)((m * parts + 63) / 64)), dim3(64), 0, c->stream, (const uint8_t *)at(coef, coef_stride),
-                           coef_stride, scratch, m, L);
-        hipLaunchKernelGGL(vp8_pack_assemble_kernel, dim3((unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)scratch, at(dst, dst_stride), dst_stride,
-                           (uint32_t *)at(info, 64), L);
+        hipLaunchKernelGGL(vp8_pack_plan_kernel, plan_grid, dim3(256), 0, c->stream, mv_at, mv_stride, coef_at, coef_stride, scratch, L);
+        if (!a) {
+            hipLaunchKernelGGL(vp8_pack_first_kernel, first_grid, dim3(64), 0, c->stream, scratch, m, L);
+            hipLaunchKernelGGL(vp8_pack_tokens_kernel, tokens_grid, dim3(64), 0, c->stream, coef_at, coef_stride, scratch, m, L);
+            hipLaunchKernelGGL(vp8_pack_assemble_kernel, dim3((unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)scratch, at(dst, dst_stride), dst_stride,
+                               (uint32_t *)at(info, 64), L);
+        } else {
+            A.probs_in = (const uint8_t *)at(a->probs_in, a->probs_in_stride);
+            A.probs_in_stride = a->probs_in_stride;
+            A.info = (uint32_t *)at(info, 128);
+            A.counts = (uint32_t *)at(counts, 4 * PACK_ADAPT_COUNT_DWORDS);
+            A.probs_out = at(probs_out, PACK_PROBS_BYTES);
+            A.flags = a->flags;
+            // (the counts of every job's adapt area: the count kernel adds to them)
+            HIPCHK(c, hipMemsetAsync(scratch + A.adapt_off, 0, (size_t)m * PACK_ADAPT_JOB_BYTES, c->stream));
+            hipLaunchKernelGGL(vp8_pack_count_kernel, plan_grid, dim3(256), 0, c->stream, coef_at, coef_stride, scratch, L, A);
+            hipLaunchKernelGGL(vp8_pack_choose_kernel, dim3((unsigned)m), dim3(256), 0, c->stream, scratch, L, A);
+            hipLaunchKernelGGL(vp8_pack_first_adapt_kernel, first_grid, dim3(64), 0, c->stream, scratch, m, L, A);
+            hipLaunchKernelGGL(vp8_pack_tokens_adapt_kernel, tokens_grid, dim3(64), 0, c->stream, coef_at, coef_stride, scratch, m, L, A);
+            hipLaunchKernelGGL(vp8_pack_assemble_kernel, dim3((unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)scratch, at(dst, dst_stride), dst_stride,
+                               (uint32_t *)(scratch + A.info_off), L);
+            hipLaunchKernelGGL(vp8_pack_adapt_info_kernel, dim3((unsigned)((m * 32 + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)scratch, m, A);
+        }
         HIPCHK(c, hipGetLastError());
         i0 += m;
     }
     return 0;
+}
+
+extern "C" int vp8hip_frames_pack_async(vp8hip_ctx *c, int n, const vp8hip_pack *p, const void *mv, size_t mv_stride, const void *coef,
+                                        size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info)
+{
+    return pack_frames(c, "vp8hip_frames_pack_async", n, p, nullptr, mv, mv_stride, coef, coef_stride, dst, dst_stride, cap, info, nullptr, nullptr);
+}
+
+extern "C" int vp8hip_frames_pack_adapt_async(vp8hip_ctx *c, int n, const vp8hip_pack *p, const vp8hip_pack_adapt *a, const void *mv, size_t mv_stride,
+                                              const void *coef, size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info, void *counts,
+                                              void *probs_out)
+{
+    const char *who = "vp8hip_frames_pack_adapt_async";
+    if (!a) return fail(c, -2, "%s: bad arguments", who);
+    return pack_frames(c, who, n, p, a, mv, mv_stride, coef, coef_stride, dst, dst_stride, cap, info, counts, probs_out);
 }

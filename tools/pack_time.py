@@ -22,6 +22,33 @@ from vp8_testlib import ivf_path, load_package  # noqa: E402
 import pack_reference as R  # noqa: E402
 
 
+def make_jobs(P, n):
+    """-> (ctx, jobs, mv, coef): n decoded frame buffers of kf_1920x1080, job i frame buffer i against i + 1, frames_subpel's vectors
+    of them and an empty levels tensor for frames_quant (tools/pack_adapt_time.py measures on the same jobs)"""
+    os.environ["VP8HIP_RECON"] = "simt"                 # the large launch's kernels: frames left as tiles
+    w, h, frames = P.read_ivf(ivf_path("kf_1920x1080"))
+    ctx = P.Vp8Hip(0)
+    ctx.configure(w, h, n, n)
+    parser = P.Parser()
+    for i, data in enumerate(frames[:n]):
+        ctx.sync()
+        hdr, _ = ctx.parse_into_slot_compact(parser, data, i)
+        parser.swap(hdr)
+    parser.close()
+    for i in range(len(frames), n):
+        ctx.ir_copy(i, i % len(frames))
+    ctx.decode([(i, i, None) for i in range(n)], P.STAGE_ALL)
+    ctx.sync()
+    rows, cols = ctx.g.aligned_h // 16, ctx.g.aligned_w // 16
+    jobs = [(i, (i + 1) % n) for i in range(n)]
+    whole = torch.empty((n, 2, rows, cols), dtype=torch.int16, device="cuda:0")
+    mv = torch.empty((n, 2, rows, cols), dtype=torch.int16, device="cuda:0")
+    coef = torch.empty((n, rows, cols, 25, 16), dtype=torch.int16, device="cuda:0")
+    ctx.frames_motion(jobs, 16, planes=(), out_mv=whole)
+    ctx.frames_subpel(jobs, start=whole, planes=(), out_mv=mv)
+    return ctx, jobs, mv, coef
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
@@ -48,29 +75,10 @@ def main():
     def mean(key):
         return sum(times[key]) / len(times[key])
 
-    os.environ["VP8HIP_RECON"] = "simt"                 # the large launch's kernels: frames left as tiles
-    w, h, frames = P.read_ivf(ivf_path("kf_1920x1080"))
-    ctx = P.Vp8Hip(0)
-    ctx.configure(w, h, n, n)
-    parser = P.Parser()
-    for i, data in enumerate(frames[:n]):
-        ctx.sync()
-        hdr, _ = ctx.parse_into_slot_compact(parser, data, i)
-        parser.swap(hdr)
-    parser.close()
-    for i in range(len(frames), n):
-        ctx.ir_copy(i, i % len(frames))
-    ctx.decode([(i, i, None) for i in range(n)], P.STAGE_ALL)
-    ctx.sync()
+    ctx, jobs, mv, coef = make_jobs(P, n)
     rows, cols = ctx.g.aligned_h // 16, ctx.g.aligned_w // 16
     say(f"kf_1920x1080 x {n} frame buffers, {rows * cols} macroblocks a picture; {reps} timed calls after 1; pack_bound {ctx.pack_bound(0)} / "
         f"{ctx.pack_bound(3)} bytes (1 / 8 partitions)")
-    jobs = [(i, (i + 1) % n) for i in range(n)]
-    whole = torch.empty((n, 2, rows, cols), dtype=torch.int16, device="cuda:0")
-    mv = torch.empty((n, 2, rows, cols), dtype=torch.int16, device="cuda:0")
-    coef = torch.empty((n, rows, cols, 25, 16), dtype=torch.int16, device="cuda:0")
-    ctx.frames_motion(jobs, 16, planes=(), out_mv=whole)
-    ctx.frames_subpel(jobs, start=whole, planes=(), out_mv=mv)
     summary = []
     for q in (10, 40):
         ctx.frames_quant(jobs, mv, q, want=(), out_coef=coef)
