@@ -1153,7 +1153,7 @@ int  vp8hip_frames_tfilter_async(vp8hip_ctx *ctx, const vp8hip_tfilter_job *jobs
  * quantise, then dequantise, inverse-transform and add: vp8_encode_inter16x16 (vp8/encoder/encodemb.c) followed by
  * vp8_inverse_transform_mby and vp8_dequant_idct_add_uv_block.  vp8hip_frames_quant_async makes them per macroblock of any picture
  * pair, bit for bit, and hands out the levels, the end-of-block positions, the error figures and the reconstruction: from pictures
- * to what an entropy coder, a requantiser or a rate-distortion estimate reads, without leaving the device.  SPLITMV, intra modes,
+ * to what an entropy coder, a requantiser or a rate-distortion estimate reads, without leaving the device.  SPLITMV, intra modes (vp8hip_frames_intra_async below),
  * the trellis (optimize_b), tokens and rate in bits, per-macroblock quantisers and the loop filter are not part of it.
  *
  * JOBS are vp8hip_hist_job (fb, ref_fb) exactly as for vp8hip_frames_subpel_async: fb is the SOURCE picture, ref_fb the REFERENCE it is
@@ -1278,6 +1278,109 @@ size_t vp8hip_quant_stats_size(const vp8hip_ctx *ctx, const vp8hip_quant *p);
 int  vp8hip_frames_quant_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int n, const vp8hip_quant *p, const void *mv, size_t mv_stride,
                                void *coef, size_t coef_stride, void *eob, size_t eob_stride, void *stats, size_t stats_stride, void *rec,
                                size_t rec_stride);
+/* INTRA MODES AND LEVELS of key-frame macroblocks: the intra counterpart of vp8hip_frames_quant_async.  What the reference does per
+ * macroblock of a key frame at real-time speed -- vp8_pick_intra_mode (vp8/encoder/pickinter.c) followed by the body of
+ * vp8cx_encode_intra_macro_block (vp8/encoder/encodeframe.c) -- for every macroblock of any picture in the context's frame buffers,
+ * bit for bit: the modes, the levels, the eobs, three figures of the decision and the reconstruction, in the caller's device
+ * memory.  With it a stream can begin, and a scene cut can be coded, without leaving the device; writing the key frame's bytes from
+ * these outputs is not part of it.  NOT part of it either: vp8_rd_pick_intra_mode, the trellis (`optimize` 0), activity masking,
+ * segmentation, a choice between intra and inter, the loop filter -- the reconstruction is the UNFILTERED one, the one intra
+ * prediction reads -- and rec into a frame buffer.
+ *
+ * JOBS.  fb[i], i < n: the SOURCE picture of job i, a frame-buffer index; any order, repeats allowed, either form.  It is read
+ * exactly as vp8hip_frames_quant_async reads its fb: the coded area A x B = 16 mb_cols x 16 mb_rows, S(F).
+ * QUANTISER.  p->q: vp8hip_quant as it stands -- qindex / job_qindex, delta[5], quantizer, stage, the three zero-bin terms, the same
+ * ranges and the same vp8hip_quant_factors; q.filter and q.planes are not read.
+ * MODE DECISION.  All arithmetic is in `int`; the ranges keep it inside 31 bits.  p->rdmult 0..1000, p->rddiv 1..100 (the reference's:
+ * vp8hip_intra_rd below), p->cost.mbmode_cost[5] (DC, V, H, TM, B_PRED) and p->cost.bmode_cost[above][left][mode], each 0..65535 (the
+ * reference's: vp8hip_intra_costs below).  RDCOST(rate, dist) = ((128 + rate * rdmult) >> 8) + rddiv * dist.  p->bmode_last, 0..9:
+ * the last sub-block mode tried.  The reference's picker tries B_DC_PRED .. B_HE_PRED only -- its loop bound, 3 --; 9 tries all
+ * ten: the one place the call goes beyond the reference, a loop bound over the decoder's own predictors.  p->flags:
+ * VP8HIP_INTRA_NO_BPRED leaves step 3 out.
+ *
+ * Per macroblock (r, c), in raster order's dependencies:
+ *   0. NEIGHBOURS are the reconstruction (step 5) of macroblocks of the same job already coded, never loop-filtered.  Outside the
+ *      picture the decoder's rules hold (vp8_setup_intra_recon, vp8_extend_mb_row): the row above the picture is 127 from column -1
+ *      through A + 3; the column left of it is 129, so the top-left pixel of (r > 0, 0) is 129 and of (0, c) 127; the above-right four
+ *      pixels of the last macroblock column in rows r > 0 are the last pixel of the line above, four times.  In B_PRED the
+ *      above-right of the right-hand block column is the macroblock's own above-right row for all four block rows
+ *      (vp8_intra_prediction_down_copy).
+ *   1. CHROMA MODE (pick_intra_mbuv_mode): the squared error over U and V together of the predictions DC ((sum + (1 << (shift - 1)))
+ *      >> shift, shift = 2 + up + left, 128 with neither), V (the row above), H (the left column), TM (clamp(L + A - TL)); the first
+ *      strict minimum in that order wins.
+ *   2. 16x16 LUMA MODE: for DC (shift = 3 + up + left), V, H, TM the decoder's prediction P; vp8_variance16x16_c against the source:
+ *      variance = sse - ((unsigned)(sum * sum) >> 8); rd = RDCOST(mbmode_cost[mode], variance); the first strict minimum wins: its rd
+ *      is error16x16, its sse best_sse.
+ *   3. B_PRED (pick_intra4x4mby_modes): cost = mbmode_cost[B_PRED], dist = 0; for block b = 0..15 in raster order: the contexts A and
+ *      L are the modes of the block above and of the block to the left -- inside the macroblock those just chosen, in a neighbour
+ *      macroblock its sub-block modes or those its 16x16 mode implies (DC: B_DC, V: B_VE, H: B_HE, TM: B_TM), outside the picture
+ *      B_DC --; for mode 0..bmode_last: vp8_intra4x4_predict, d = the 4x4 squared error, rd = RDCOST(bmode_cost[A][L][mode], d), the
+ *      first strict minimum wins; the block is encoded as vp8_encode_intra4x4block does -- residual, vp8_short_fdct4x4_c, the
+ *      quantiser over the Y1 factors on all sixteen positions (position 0 with the dc factors), vp8_short_idct4x4llm_c of dqcoeff
+ *      where eob > 1, else vp8_dc_only_idct_add of dqcoeff[0], onto the prediction --, and its reconstruction is the neighbour of the
+ *      blocks after it; cost += rate, dist += d; where dist > best_sse the macroblock breaks out and error4x4 is INT_MAX; after
+ *      the sixteenth block error4x4 = RDCOST(cost, dist).  With VP8HIP_INTRA_NO_BPRED error4x4 is INT_MAX.
+ *   4. B_PRED wins where error4x4 < error16x16.
+ *   5. ENCODE.  B_PRED: step 3's levels and reconstruction; there is no Y2 block: block 24 is zero and eob[24] is 0.  Otherwise
+ *      vp8_encode_intra16x16mby then vp8_inverse_transform_mby: vp8hip_frames_quant_async's steps 2-5 on the winner's prediction.
+ *      Chroma in both cases: vp8_encode_intra16x16mbuv then vp8_dequant_idct_add_uv_block on step 1's prediction.
+ *
+ * OUTPUTS, all in the caller's device memory, each optional (NULL), at least one; job i's lies at pointer + i * stride:
+ *   coef, eob, rec   vp8hip_frames_quant_async's layouts and size functions, unchanged.  For a B_PRED macroblock position 0 of the luma
+ *           blocks IS coded and block 24 is zero.
+ *   modes   [mb_rows][mb_cols][32] of uint8, vp8hip_intra_modes_size(ctx) = 32 * mb_rows * mb_cols; pointer and stride multiples of 4.
+ *           [0] the y mode in vp8_ir.h's numbering (0..4); [1] the uv mode; [2] 1 where nothing is left to code (mb_is_skippable: with
+ *           a Y2 block every luma eob < 2 and the nine others 0; B_PRED: all 24 zero); [3] 0; [4..19] the sixteen sub-block modes,
+ *           the implied ones for a 16x16 mode; [20..31] 0.
+ *   stats   uint32 planes [mb_rows][mb_cols], one per bit of p->planes in bit order; pointer and stride multiples of 4;
+ *           vp8hip_intra_stats_size(ctx, p) = 4 * popcount * mb_rows * mb_cols, 0 for planes == 0 or unknown bits:
+ *             VP8HIP_INTRA_RD16    error16x16;
+ *             VP8HIP_INTRA_RD4     error4x4, 0x7FFFFFFF where broken out or not tried;
+ *             VP8HIP_INTRA_RATE    what vp8_pick_intra_mode returns: the winner's rate;
+ *             VP8HIP_INTRA_EOBS    the sum of the 25 eobs;
+ *             VP8HIP_INTRA_RECSSE  the sum over the macroblock's 384 pixels of (source - reconstruction)^2.
+ *
+ * The call is its neighbours: enqueued on the context's stream; no device memory is added (tables and costs travel in the
+ * arguments of the launches; a call of many jobs, or of more than four different qindex values, is cut into launches); no frame
+ * buffer is written; only bytes inside an output's own range are written; no atomics: the same bits in every run.  It refuses no
+ * size the context accepts.  -2 with nothing enqueued for n < 1; an fb out of range; a qindex outside 0..127; a delta outside
+ * -15..15; an unknown quantizer or stage; a zero-bin term outside +-1048576; rdmult, rddiv, a cost or bmode_last out of range;
+ * unknown flags or plane bits; stats with planes == 0; all five outputs NULL; a stride below the size; a pointer or stride not
+ * aligned (coef: 16, eob, modes, stats: 4); an output that is not device memory of the context's device or cannot hold n jobs;
+ * outputs that overlap.
+ *
+ * vp8hip_intra_costs(out): host only, no context, no GPU.  The reference's key-frame mbmode_cost[KEY_FRAME][DC, V, H, TM, B_PRED] and
+ * bmode_costs[10][10][10] as vp8_init_mode_costs computes them: vp8_cost_tokens over vp8_kf_ymode_prob / vp8_kf_bmode_prob with
+ * vp8_prob_cost.  -2 for a NULL out.
+ * vp8hip_intra_rd(qindex, y1dc_delta, zbin_over_quant, &rdmult, &rddiv): host only.  vp8_initialize_rd_consts for one pass: Qvalue =
+ * vp8_dc_quant(qindex, y1dc_delta), capped at 160; rdmult = (int)(2.70 * q * q) in double; for zbin_over_quant > 0, modq =
+ * (int)(q * (1.0 + 0.0015625 * zbin_over_quant)) and rdmult = (int)(2.70 * modq * modq); above 1000, rddiv = 1 and rdmult /= 100,
+ * else rddiv = 100.  Not the two-pass term.  -2 for a NULL pointer, a qindex outside 0..127 or a delta outside -15..15. */
+#define VP8HIP_INTRA_NO_BPRED 1  /* flags */
+#define VP8HIP_INTRA_RD16    1   /* bit order = plane order */
+#define VP8HIP_INTRA_RD4     2
+#define VP8HIP_INTRA_RATE    4
+#define VP8HIP_INTRA_EOBS    8
+#define VP8HIP_INTRA_RECSSE  16
+typedef struct vp8hip_intra_cost {
+    int mbmode_cost[5];        /* DC, V, H, TM, B_PRED: 0..65535 */
+    int bmode_cost[10][10][10];/* [above][left][mode]: 0..65535 */
+} vp8hip_intra_cost;
+typedef struct vp8hip_intra {
+    vp8hip_quant q;            /* the quantiser; filter and planes are not read */
+    int rdmult, rddiv;         /* 0..1000, 1..100 */
+    int bmode_last;            /* 0..9; the reference's is 3 */
+    unsigned flags;            /* VP8HIP_INTRA_NO_BPRED */
+    unsigned planes;           /* VP8HIP_INTRA_* bits of stats; may be 0 where stats is NULL */
+    vp8hip_intra_cost cost;
+} vp8hip_intra;
+int  vp8hip_intra_costs(vp8hip_intra_cost *out);
+int  vp8hip_intra_rd(int qindex, int y1dc_delta, int zbin_over_quant, int *rdmult, int *rddiv);
+size_t vp8hip_intra_modes_size(const vp8hip_ctx *ctx);
+size_t vp8hip_intra_stats_size(const vp8hip_ctx *ctx, const vp8hip_intra *p);
+int  vp8hip_frames_intra_async(vp8hip_ctx *ctx, const int *fb, int n, const vp8hip_intra *p, void *coef, size_t coef_stride, void *eob,
+                               size_t eob_stride, void *stats, size_t stats_stride, void *rec, size_t rec_stride, void *modes,
+                               size_t modes_stride);
 /* COMPRESSED INTER FRAMES from quantised levels and vectors: the entropy coder behind vp8hip_frames_quant_async.
  * vp8hip_frames_pack_async takes that call's mv and coef tensors as they stand and writes, per job, one complete compressed VP8
  * inter frame (RFC 6386) into the caller's device memory: the 3-byte frame tag, the first partition, the partition size table, 1 to

@@ -624,6 +624,38 @@ def quant_factors(qindex, deltas=(0, 0, 0, 0, 0)):
 
 
 PACK_OVERFLOW, PACK_BAD_VECTOR, PACK_BAD_LEVEL, PACK_CLAMPS = 1, 2, 4, 8      # VP8HIP_PACK_*: the status bits of Vp8Hip.frames_pack
+INTRA_PLANES = {"rd16": 1, "rd4": 2, "rate": 4, "eobs": 8, "recsse": 16}        # VP8HIP_INTRA_*: bit order = plane order
+INTRA_NO_BPRED = 1                                            # VP8HIP_INTRA_NO_BPRED
+
+
+def intra_sizes(w, h, planes=()):
+    """(bytes of one job's coef records, of its eobs, of its stats, of its reconstruction, of its modes) of Vp8Hip.frames_intra at the
+    display size w x h: 800, 32, 4 * planes and 32 bytes a macroblock, and i420_size(w, h); (0, 0, 0, 0, 0) for a size outside
+    1..16383 or an unknown plane"""
+    mask = _plane_mask(planes, INTRA_PLANES, True)
+    if mask is None or not (1 <= w <= 16383 and 1 <= h <= 16383):
+        return 0, 0, 0, 0, 0
+    n = ((w + 15) // 16) * ((h + 15) // 16)
+    return 800 * n, 32 * n, 4 * bin(mask).count("1") * n, int(load_hip().vp8hip_i420_size(int(w), int(h))), 32 * n
+
+
+def intra_costs():
+    """the reference's key-frame mode costs (vp8hip_intra_costs; on the host, no GPU): (mbmode_cost int32 [5] -- DC, V, H, TM, B_PRED --,
+    bmode_cost int32 [10, 10, 10] -- above, left, mode), as vp8_init_mode_costs computes them"""
+    t = IntraCost()
+    if load_hip().vp8hip_intra_costs(ctypes.byref(t)):
+        raise ValueError("intra_costs: refused")
+    return np.ctypeslib.as_array(t.mbmode_cost).astype(np.int32), np.ctypeslib.as_array(t.bmode_cost).astype(np.int32).reshape(10, 10, 10)
+
+
+def intra_rd(qindex, y1dc_delta=0, zbin_over_quant=0):
+    """(rdmult, rddiv) of the reference's vp8_initialize_rd_consts for one pass (vp8hip_intra_rd; on the host, no GPU)"""
+    m, d = c_int(), c_int()
+    if load_hip().vp8hip_intra_rd(int(qindex), int(y1dc_delta), int(zbin_over_quant), ctypes.byref(m), ctypes.byref(d)):
+        raise ValueError(f"intra_rd: qindex {qindex} (0..127), y1dc_delta {y1dc_delta} (-15..15)")
+    return m.value, d.value
+
+
 # what Vp8Hip.frames_pack and pack_header take beside the levels, the vectors and the quantiser, with their defaults
 PACK_DEFAULTS = dict(version=0, show_frame=1, filter_type=0, filter_level=0, sharpness=0, ref_frame=1, refresh_last=1, refresh_golden=0, refresh_alt=0,
                      copy_buffer_to_gf=0, copy_buffer_to_arf=0, sign_bias_golden=0, sign_bias_alt=0, log2_parts=0, prob_skip_false=200, prob_intra=150,
@@ -937,6 +969,15 @@ class QuantParams(ctypes.Structure):        # vp8hip_quant, include/vp8hip.h
                 ("zbin_mode_boost", c_int), ("act_zbin_adj", c_int), ("planes", ctypes.c_uint), ("job_qindex", ctypes.POINTER(ctypes.c_uint8))]
 
 
+class IntraCost(ctypes.Structure):          # vp8hip_intra_cost, include/vp8hip.h
+    _fields_ = [("mbmode_cost", c_int * 5), ("bmode_cost", c_int * 10 * 10 * 10)]
+
+
+class IntraParams(ctypes.Structure):        # vp8hip_intra, include/vp8hip.h
+    _fields_ = [("q", QuantParams), ("rdmult", c_int), ("rddiv", c_int), ("bmode_last", c_int), ("flags", ctypes.c_uint), ("planes", ctypes.c_uint),
+                ("cost", IntraCost)]
+
+
 class PackParams(ctypes.Structure):         # vp8hip_pack, include/vp8hip.h
     _fields_ = [(name, c_int) for name in ("version", "show_frame", "filter_type", "filter_level", "sharpness", "qindex")] + [("delta", c_int * 5)] + \
                [(name, c_int) for name in ("ref_frame", "refresh_last", "refresh_golden", "refresh_alt", "copy_buffer_to_gf", "copy_buffer_to_arf",
@@ -1081,6 +1122,14 @@ def load_hip():
         L.vp8hip_quant_stats_size.argtypes = [c_void_p, ctypes.POINTER(QuantParams)]
         L.vp8hip_quant_stats_size.restype = c_size_t
         L.vp8hip_frames_quant_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(QuantParams), c_void_p, c_size_t, c_void_p, c_size_t,
+                                                c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
+        L.vp8hip_intra_costs.argtypes = [ctypes.POINTER(IntraCost)]
+        L.vp8hip_intra_rd.argtypes = [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+        L.vp8hip_intra_modes_size.argtypes = [c_void_p]
+        L.vp8hip_intra_modes_size.restype = c_size_t
+        L.vp8hip_intra_stats_size.argtypes = [c_void_p, ctypes.POINTER(IntraParams)]
+        L.vp8hip_intra_stats_size.restype = c_size_t
+        L.vp8hip_frames_intra_async.argtypes = [c_void_p, c_void_p, c_int, ctypes.POINTER(IntraParams), c_void_p, c_size_t, c_void_p, c_size_t,
                                                 c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t]
         L.vp8hip_pack_bound.argtypes = [c_void_p, c_int]
         L.vp8hip_pack_bound.restype = c_size_t
@@ -2051,6 +2100,92 @@ class Vp8Hip:
             flat = [v for k in ("coef", "eob", "stats", "rec") for v in a.get(k, (None, 0))]
             return self.L.vp8hip_frames_quant_async(self.h, arr, n, ctypes.byref(p), mptr, mstride, *flat)
         made = self._to_torch(who, outs, call, "vp8hip_frames_quant_async")
+        return dict(zip(names, made))
+
+    def frames_intra(self, fbs, qindex=40, deltas=(0, 0, 0, 0, 0), quantizer="regular", stage="levels", zbin=(0, 0, 0), rdmult=None, rddiv=None,
+                     mbmode_cost=None, bmode_cost=None, bmode_last=3, bpred=True, planes=(), want=("coef", "eob", "modes"), out_coef=None,
+                     out_eob=None, out_stats=None, out_rec=None, out_modes=None):
+        """The reference's intra mode decision and encode of key-frame macroblocks on the context's device
+        (vp8hip_frames_intra_async): per macroblock of each source picture vp8_pick_intra_mode -- the chroma mode, the 16x16 mode,
+        the B_PRED chain, the choice -- then the encode and the unfiltered reconstruction the neighbours predict from, bit for bit.
+        `fbs`: a list of frame buffers, the sources; any order, repeats allowed.  qindex, deltas, quantizer, stage, zbin: as
+        frames_quant.  rdmult (0..1000), rddiv (1..100): None for intra_rd(qindex, deltas[0], zbin[0]) -- one pair serves every job
+        of a call, so with a sequence of DIFFERENT qindex values both must be given --; mbmode_cost [5], bmode_cost [10, 10, 10], each 0..65535: None for intra_costs().  bmode_last:
+        the last sub-block mode tried, 0..9; the reference's is 3.  bpred=False leaves the B_PRED chain out.  Returns a dict of what
+        `want` names or an out_* tensor is given for: "coef", "eob", "rec" as frames_quant (a B_PRED macroblock codes position 0 of
+        its luma blocks and has a zero block 24), "modes" torch.uint8 [n, mb_rows, mb_cols, 32] ([0] y mode, [1] uv mode, [2]
+        skippable, [4..19] the sub-block modes), "stats" torch.int32 [n, P, mb_rows, mb_cols] holding uint32 bits, the planes of
+        `planes` ("rd16", "rd4", "rate", "eobs", "recsse", or the mask) in bit order.  out_*: as frames_quant (modes: stride(0) a
+        multiple of 4).  Stream ordering, the `import torch` first rule and the remark on record_stream: as frames_scaled."""
+        who = "frames_intra"
+        fbs = [int(f) for f in fbs]
+        n = len(fbs)
+        mask = _plane_mask(planes, INTRA_PLANES, True)
+        if mask is None:
+            raise ValueError(f"{who}: planes {planes!r} (of {', '.join(INTRA_PLANES)})")
+        if not n:
+            raise ValueError(f"{who}: no jobs")
+        if any(f < 0 for f in fbs):
+            raise ValueError(f"{who}: a negative frame buffer")
+        want = {want} if isinstance(want, str) else set(want)
+        if want - {"coef", "eob", "stats", "rec", "modes"}:
+            raise ValueError(f"{who}: want {sorted(want)!r} (of coef, eob, stats, rec, modes)")
+        given = {"coef": out_coef, "eob": out_eob, "stats": out_stats, "rec": out_rec, "modes": out_modes}
+        want |= {k for k, t in given.items() if t is not None}
+        if mask:
+            want.add("stats")
+        if "stats" in want and not mask:
+            raise ValueError(f"{who}: stats without planes")
+        if not want:
+            raise ValueError(f"{who}: no output asked for")
+        jq = None
+        if isinstance(qindex, (int, np.integer)):
+            qs = [int(qindex)]
+        else:
+            qs = [int(q) for q in qindex]
+            if len(qs) != n:
+                raise ValueError(f"{who}: {len(qs)} qindex values for {n} jobs")
+            jq = (ctypes.c_uint8 * n)(*[q & 255 for q in qs])
+        d = [int(v) for v in deltas]
+        z = [int(v) for v in zbin]
+        if any(not 0 <= q <= 127 for q in qs) or len(d) != 5 or any(not -15 <= v <= 15 for v in d):
+            raise ValueError(f"{who}: qindex {qindex!r} (0..127), deltas {deltas!r} (five of -15..15)")
+        if len(z) != 3 or any(abs(v) > QUANT_ZBIN_MAX for v in z):
+            raise ValueError(f"{who}: zbin {zbin!r} (zbin_over_quant, zbin_mode_boost, act_zbin_adj, each within +-{QUANT_ZBIN_MAX})")
+        if quantizer not in QUANT_QUANTIZERS or stage not in COEF_STAGES:
+            raise ValueError(f"{who}: quantizer {quantizer!r} ({', '.join(QUANT_QUANTIZERS)}), stage {stage!r} ({', '.join(COEF_STAGES)})")
+        if rdmult is None or rddiv is None:
+            if len(set(qs)) > 1:
+                raise ValueError(f"{who}: rdmult and rddiv must be given with different qindex values: one pair serves every job")
+            m0, d0 = intra_rd(qs[0], d[0], z[0])
+            rdmult, rddiv = (m0 if rdmult is None else rdmult), (d0 if rddiv is None else rddiv)
+        if mbmode_cost is None or bmode_cost is None:
+            mc, bc = intra_costs()
+            mbmode_cost, bmode_cost = (mc if mbmode_cost is None else mbmode_cost), (bc if bmode_cost is None else bmode_cost)
+        mc, bc = [int(v) for v in mbmode_cost], [int(v) for v in np.asarray(bmode_cost).ravel()]
+        if not (0 <= int(rdmult) <= 1000 and 1 <= int(rddiv) <= 100 and 0 <= int(bmode_last) <= 9 and len(mc) == 5 and len(bc) == 1000 and
+                all(0 <= v <= 65535 for v in mc + bc)):
+            raise ValueError(f"{who}: rdmult {rdmult} (0..1000), rddiv {rddiv} (1..100), bmode_last {bmode_last} (0..9), mbmode_cost [5] and "
+                             "bmode_cost [10, 10, 10] of 0..65535")
+        p = IntraParams()
+        p.q = QuantParams(qs[0], (c_int * 5)(*d), QUANT_QUANTIZERS[quantizer], 0, COEF_STAGES[stage], z[0], z[1], z[2], 0, jq)
+        p.rdmult, p.rddiv, p.bmode_last, p.flags, p.planes = int(rdmult), int(rddiv), int(bmode_last), 0 if bpred else INTRA_NO_BPRED, mask or 0
+        p.cost.mbmode_cost[:] = mc
+        ctypes.memmove(p.cost.bmode_cost, (c_int * 1000)(*bc), 4000)
+        arr = (c_int * n)(*fbs)
+        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
+        shapes = {"coef": ("int16", (n, rows, cols, 25, 16)), "eob": ("uint8", (n, rows, cols, 32)),
+                  "stats": ("int32", (n, bin(mask or 0).count("1"), rows, cols)),
+                  "rec": ("uint8", (n, int(self.L.vp8hip_i420_size(self.width, self.height)))), "modes": ("uint8", (n, rows, cols, 32))}
+        order = ("coef", "eob", "stats", "rec", "modes")
+        names = [k for k in order if k in want]
+        outs = [("out_" + k, given[k], shapes[k][0], shapes[k][1]) for k in names]
+
+        def call(*args):
+            a = dict(zip(names, zip(args[0::2], args[1::2])))
+            flat = [v for k in order for v in a.get(k, (None, 0))]
+            return self.L.vp8hip_frames_intra_async(self.h, arr, n, ctypes.byref(p), *flat)
+        made = self._to_torch(who, outs, call, "vp8hip_frames_intra_async")
         return dict(zip(names, made))
 
     def pack_bound(self, log2_parts=0):

@@ -397,6 +397,34 @@ struct QuantLaunch : FramePlanes {
     short t[QUANT_MAX_TABLES][QUANT_TABLE_SHORTS];
     QuantJob j[QUANT_MAX_JOBS];
 };
+// One launch of vp8hip_frames_intra_async (vp8_intra_enc.hip), as the host's plan (vp8hip_intra.hip) left it.  A WORKGROUP owns one
+// job and walks its macroblocks as a wavefront: step s holds the macroblocks (r, c) with c + 2 r == s, dealt to the workgroup's waves,
+// a workgroup barrier between steps.  Rows are walked in bands of INTRA_BAND; the tables are vp8hip_quant_staged_table's, one per
+// distinct qindex; the mode costs ride in the arguments, so a launch takes jobs until either array is full
+#define INTRA_MAX_JOBS 256        // jobs per launch (kernel arguments: 4 bytes each)
+#define INTRA_MAX_TABLES 4        // distinct qindex values per launch (176 bytes each)
+#define INTRA_WAVES 8             // waves a workgroup: macroblocks of a step coded at the same time
+#define INTRA_THREADS (64 * INTRA_WAVES)
+#define INTRA_BAND 68             // macroblock rows a band: 1080p is one band; LDS holds a ring of four bottom lines per row of a band
+#define INTRA_LINE_WORDS 9        // a macroblock's bottom line (or right column): Y 16, U 8, V 8 bytes, then its four sub-block modes
+#define INTRA_RD16 1              // VP8HIP_INTRA_*
+#define INTRA_RD4 2
+#define INTRA_RATE 4
+#define INTRA_EOBS 8
+#define INTRA_RECSSE 16
+struct IntraLaunch : FramePlanes {
+    int fast;                     // 0: the regular quantiser, 1: the fast one
+    int levels;                   // coef holds 1: qcoeff, 0: dqcoeff
+    unsigned planes;              // INTRA_* bits of the stats; 0: none
+    int coef, eob, rec, modes;    // 1: coefficients, eobs, reconstructions, modes are written
+    int rdmult, rddiv;            // RDCOST's two
+    int bmode_last;               // the last sub-block mode tried, 0..9
+    int no_bpred;                 // 1: step 3 is left out
+    unsigned short mbmode_cost[6];       // DC, V, H, TM, B_PRED; one unused
+    unsigned short bmode_cost[1000];     // [above][left][mode]
+    short t[INTRA_MAX_TABLES][QUANT_TABLE_SHORTS];
+    int j[INTRA_MAX_JOBS];        // the source: frame buffer << 2 | form, as of the call, and in bits 28..29 its table
+};
 // the five launches' layout in the kernels' arguments: the base takes 36 bytes and the first member lies right behind it (offsetof
 // past a base of plain ints is what the warning calls conditionally supported: it is supported here)
 #pragma clang diagnostic push

@@ -218,6 +218,11 @@ int vp8hip_check_pairs(vp8hip_ctx *c, const char *who, const vp8hip_hist_job *jo
 void vp8hip_frame_planes(const vp8hip_ctx *c, FramePlanes &L);
 int vp8hip_check_named_dst(vp8hip_ctx *c, const char *who, const char *name, const void *dst, size_t dst_stride, size_t size, size_t elem_size, int n);
 int vp8hip_check_slots(vp8hip_ctx *c, const char *who, const int *slots, int n);
+// vp8hip_quant.hip: what vp8hip_frames_quant_async and vp8hip_frames_intra_async share of a vp8hip_quant -- the check of its quantiser
+// part, and table k of a launch: vp8hip_quant_factors for qindex as it stands, then the three ZBIN_EXTRAs (QUANT_TABLE_SHORTS shorts)
+#define QUANT_ZBIN_MAX (1 << 20)
+bool vp8hip_quantiser_ok(const vp8hip_quant *p);
+void vp8hip_quant_staged_table(short *t, int qindex, const vp8hip_quant *p);
 bool vp8hip_out_grid(const vp8hip_ctx *c, int dst_w, int dst_h, int cells, int &gw, int &gh);
 int vp8hip_check_device_span(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, int n);
 int vp8hip_check_dst(vp8hip_ctx *c, const char *who, const void *dst, size_t dst_stride, size_t size, size_t elem_size, int n);

@@ -12,7 +12,6 @@ extern "C" __global__ void vp8_quant_frames_kernel(const uint8_t *raster, size_t
                                                    size_t stats_stride, uint8_t *rec, size_t rec_stride, QuantLaunch L);
 
 #define QUANT_PLANES (VP8HIP_QUANT_ERRY | VP8HIP_QUANT_ERRY2 | VP8HIP_QUANT_ERRUV | VP8HIP_QUANT_EOBS | VP8HIP_QUANT_RECSSE)
-#define QUANT_ZBIN_MAX (1 << 20)
 
 extern "C" int vp8hip_quant_factors(int qindex, const int delta[5], vp8hip_quant_table *out)
 {
@@ -46,17 +45,22 @@ extern "C" int vp8hip_quant_factors(int qindex, const int delta[5], vp8hip_quant
     return 0;
 }
 
-// what the call refuses on p alone (job_qindex aside)
-static bool quant_params_ok(const vp8hip_quant *p)
+// the quantiser part of p (vp8hip_intra.hip takes it too): deltas, zero-bin terms, quantizer and stage; job_qindex aside
+bool vp8hip_quantiser_ok(const vp8hip_quant *p)
 {
-    if (!p || (p->planes & ~(unsigned)QUANT_PLANES)) return false;
     for (int k = 0; k < 5; k++)
         if (p->delta[k] < -15 || p->delta[k] > 15) return false;
     for (int z : {p->zbin_over_quant, p->zbin_mode_boost, p->act_zbin_adj})
         if (z < -QUANT_ZBIN_MAX || z > QUANT_ZBIN_MAX) return false;
     return (p->quantizer == VP8HIP_QUANT_REGULAR || p->quantizer == VP8HIP_QUANT_FAST) &&
-           (p->filter == VP8HIP_TFILTER_SIXTAP || p->filter == VP8HIP_TFILTER_BILINEAR) &&
            (p->stage == VP8HIP_COEF_LEVELS || p->stage == VP8HIP_COEF_DEQUANT);
+}
+
+// what the call refuses on p alone (job_qindex aside)
+static bool quant_params_ok(const vp8hip_quant *p)
+{
+    if (!p || (p->planes & ~(unsigned)QUANT_PLANES)) return false;
+    return vp8hip_quantiser_ok(p) && (p->filter == VP8HIP_TFILTER_SIXTAP || p->filter == VP8HIP_TFILTER_BILINEAR);
 }
 
 extern "C" size_t vp8hip_quant_coef_size(const vp8hip_ctx *c) { return c && c->width ? (size_t)800 * c->dg.mb_cols * c->dg.mb_rows : 0; }
@@ -68,7 +72,7 @@ extern "C" size_t vp8hip_quant_stats_size(const vp8hip_ctx *c, const vp8hip_quan
 }
 
 // table k of the launch: vp8hip_quant_factors for qindex as it stands, then the three ZBIN_EXTRAs (Y1, Y2, UV) through the `(short)`
-static void quant_table(short *t, int qindex, const vp8hip_quant *p)
+void vp8hip_quant_staged_table(short *t, int qindex, const vp8hip_quant *p)
 {
     vp8hip_quant_table f;
     vp8hip_quant_factors(qindex, p->delta, &f);
@@ -131,7 +135,7 @@ extern "C" int vp8hip_frames_quant_async(vp8hip_ctx *c, const vp8hip_hist_job *j
             if (k == tables) {
                 if (tables == QUANT_MAX_TABLES) break;
                 qof[tables] = q;
-                quant_table(L.t[tables++], q, p);
+                vp8hip_quant_staged_table(L.t[tables++], q, p);
             }
             L.j[m] = QuantJob{vp8hip_frame_ref(c, jobs[i0 + m].fb), vp8hip_frame_ref(c, jobs[i0 + m].ref_fb), k};
         }
