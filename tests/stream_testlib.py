@@ -1,5 +1,7 @@
 """Streams written at test time from seeds (tests/vp8_writer.py), and what the tests around them share:
  * inter_sequence: a key frame and inter frames of one size (tests/test_writer_cpu.py);
+ * writer_reference_listing: what the REFERENCE decoder gave for a written stream, live or as recorded in
+   tests/golden/writer_ref_md5.json; EXTREME_CASES: the two streams at 16383x16 and 16x16383 that the CPU and the GPU tests share;
  * size_change_stream: sections of different sizes one after the other -- every section's key frame makes the decoder allocate
    again (vp8/decoder/decodframe.c:771-808 -> vp8_alloc_frame_buffers, alloccommon.c:59-152) -- with the three streams MAIN, MFQE
    and ALIGNED of tests/test_sizechange_cpu.py and tests/test_gpu_sizechange.py;
@@ -31,11 +33,12 @@ RECORD = os.environ.get("VP8_RECORD_REF_DIGESTS") == "1"
 
 # ---- inter frames: every inter mode, all three references with sign biases, split vectors, and the segment map's three lives
 # (coded, kept with new data, kept untouched) -- content the reference ENCODER never produces (it codes no map on inter frames)
-def inter_sequence(w, h, seed, plan, lp=0, dense=0.25, big=False, tweak=None):
+def inter_sequence(w, h, seed, plan, lp=0, dense=0.25, big=False, tweak=None, mv_reach=None):
     """A key frame and one inter frame per entry of plan ("keep": segmentation on, nothing coded; "data": new segment data, map
     kept; "map": new map, data kept; "both"; "off": segmentation off).  Returns the frames and, per frame, the IR the stream was
     written from as a decoder is to read it back: (hdr, mbs, coef, mvs, segment map known).  tweak(k, hdr), if given, may change
-    frame k's header just before it is written (it draws no random numbers: without it the streams are what they always were)."""
+    frame k's header just before it is written (it draws no random numbers: without it the streams are what they always were).
+    mv_reach: synth_ir's bound on the inter frames' vectors, for pictures too large to draw them over (None: as ever)."""
     rng = np.random.default_rng(seed)
     hdr, mbs, coef, mvs = synth_ir(w, h, seed, inter=False, dense=dense, big=big, segmented=True)
     hdr.num_token_partitions = 1 << lp
@@ -46,7 +49,8 @@ def inter_sequence(w, h, seed, plan, lp=0, dense=0.25, big=False, tweak=None):
     segq, seglf = list(hdr.segment_quant), list(hdr.segment_lf)
     known = True
     for i, step in enumerate(plan):
-        hdr, mbs, coef, mvs = synth_ir(w, h, seed * 100 + i + 1, inter=True, dense=dense, big=big, segmented=step != "off")
+        hdr, mbs, coef, mvs = synth_ir(w, h, seed * 100 + i + 1, inter=True, dense=dense, big=big, segmented=step != "off",
+                                       mv_reach=mv_reach)
         hdr.num_token_partitions = 1 << lp
         hdr.refresh_last = int(rng.integers(0, 4) > 0)
         hdr.refresh_golden, hdr.refresh_alt = int(rng.integers(0, 3) == 0), int(rng.integers(0, 3) == 0)
@@ -75,6 +79,66 @@ def inter_sequence(w, h, seed, plan, lp=0, dense=0.25, big=False, tweak=None):
         frames.append(data)
         expect.append((hdr, mbs2, coef, mvs2, known))
     return frames, expect
+
+
+# ---- the reference decoder's listings of streams of the writer (tests/test_writer_cpu.py and the GPU tests over the same streams)
+WRITER_LISTINGS = os.path.join(GOLDEN, "writer_ref_md5.json")
+
+
+def writer_reference_listing(key, ivf):
+    """The reference decoder's per-frame MD5s of the stream in `ivf`: printed by oracle/_ref/ref_md5 where it is built (and then
+    equal to the recorded listing), else the listing recorded from it for a stream with the same SHA-256."""
+    sha = hashlib.sha256(open(ivf, "rb").read()).hexdigest()
+    table = json.load(open(WRITER_LISTINGS)) if os.path.exists(WRITER_LISTINGS) else {}
+    live = None
+    if os.path.exists(REF_MD5):
+        out = str(ivf) + ".md5"
+        r = subprocess.run([REF_MD5, str(ivf), out], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        live = [l.split()[0] for l in open(out)]
+    if RECORD:
+        assert live is not None, "VP8_RECORD_REF_DIGESTS=1 needs the reference build (make -C oracle ref)"
+        table[key] = {"stream_sha256": sha, "md5": live}
+        with open(WRITER_LISTINGS, "w") as f:
+            json.dump(table, f, indent=1, sort_keys=True)
+            f.write("\n")
+    rec = table.get(key)
+    assert rec is not None, f"{key}: no reference listing recorded in {WRITER_LISTINGS}"
+    assert rec["stream_sha256"] == sha, f"{key}: the written stream is not the one the reference listing was recorded from"
+    if live is not None:
+        assert live == rec["md5"], key
+    return rec["md5"]
+
+
+# The ends of the size range vp8hip_configure accepts (16383 either way): a key frame and three inter frames, 1024 macroblocks in
+# one row under eight token partitions, and in one column.  Vectors no further than 2040 eighth-pel units: what the writer can
+# code as one difference.  width, height, seed, plan, log2 partitions, big coefficients, mv_reach
+EXTREME_CASES = [
+    (16383, 16, 27, ("keep", "both", "data"), 3, False, 2040),
+    (16, 16383, 26, ("keep", "map", "both"), 0, False, 2040),
+]
+_extreme = {}
+
+
+def extreme_sequence(case):
+    """-> (frames, expect) of inter_sequence for one of EXTREME_CASES; written once a process (a second or two each)"""
+    if case not in _extreme:
+        w, h, seed, plan, lp, big, reach = case
+        _extreme[case] = inter_sequence(w, h, seed, plan, lp, big=big, mv_reach=reach)
+    return _extreme[case]
+
+
+def extreme_key(case):
+    """the name the reference's listing of the stream is recorded under in tests/golden/writer_ref_md5.json"""
+    return "extreme_%dx%d_seed%d" % case[:3]
+
+
+def extreme_listing(case, directory):
+    """-> (frames, the reference decoder's per-frame MD5s) of one of EXTREME_CASES"""
+    frames, _ = extreme_sequence(case)
+    ivf = os.path.join(str(directory), extreme_key(case) + ".ivf")
+    write_ivf(ivf, case[0], case[1], frames)
+    return frames, writer_reference_listing(extreme_key(case), ivf)
 
 
 # ---- streams that change their size: sections of (width, height, seed, plan, log2 token partitions)

@@ -269,6 +269,18 @@ def test_written_inter_streams():
         assert _one_slot_stream(P, w, h, frames, gold, (w, h, seed, "pooled"), pooled=True) == len(plan)
 
 
+@pytest.mark.parametrize("which", [0, 1])
+def test_written_streams_at_the_ends_of_the_size_range(which, tmp_path):
+    """16383x16 under eight token partitions and 16x16383 (tests/stream_testlib.py: EXTREME_CASES), a key frame and three inter
+    frames each through ONE slot: the IR and the vectors the host feeder reads, and the frames of the reference decoder's listing
+    recorded for these stream bytes."""
+    from stream_testlib import EXTREME_CASES, extreme_key, extreme_listing
+    P = load_package()
+    case = EXTREME_CASES[which]
+    frames, gold = extreme_listing(case, tmp_path)
+    assert _one_slot_stream(P, case[0], case[1], frames, gold, extreme_key(case)) == len(case[3])
+
+
 @pytest.mark.parametrize("name", ["kf_odd_67x45", "kf_640x360", "kf_1920x1080", "kf_8part_1920x1080", "kf_3840x2160"])
 def test_block_pool(name):
     """vp8hip_configure_pooled: the slots' block streams out of one pool, a chunk (four macroblock rows' worst case) at a time.

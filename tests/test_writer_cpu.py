@@ -6,46 +6,13 @@
    (tests/golden/writer_ref_md5.json; VP8_RECORD_REF_DIGESTS=1 with the reference built rewrites it).  This pins feeder
    AND oracle on content no encoder would choose: every mode everywhere, all segment / delta features, 1..8 token
    partitions, coefficients up to +-2047, odd sizes."""
-import hashlib
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from stream_testlib import inter_sequence
-from vp8_testlib import GOLDEN, ROOT, load_package, oracle_decode, synth_ir
+from stream_testlib import (EXTREME_CASES, extreme_key, extreme_listing, extreme_sequence, inter_sequence,
+                            writer_reference_listing as reference_listing)
+from vp8_testlib import load_package, oracle_decode, synth_ir
 from vp8_writer import write_ivf, write_key_frame
-
-REF_MD5 = os.path.join(ROOT, "oracle", "_ref", "ref_md5")
-LISTINGS = os.path.join(GOLDEN, "writer_ref_md5.json")
-RECORD = os.environ.get("VP8_RECORD_REF_DIGESTS") == "1"
-
-
-def reference_listing(key, ivf):
-    """The reference decoder's per-frame MD5s of the stream in `ivf`: printed by oracle/_ref/ref_md5 where it is built (and then
-    equal to the recorded listing), else the listing recorded from it for a stream with the same SHA-256."""
-    sha = hashlib.sha256(open(ivf, "rb").read()).hexdigest()
-    table = json.load(open(LISTINGS)) if os.path.exists(LISTINGS) else {}
-    live = None
-    if os.path.exists(REF_MD5):
-        out = str(ivf) + ".md5"
-        r = subprocess.run([REF_MD5, str(ivf), out], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        live = [l.split()[0] for l in open(out)]
-    if RECORD:
-        assert live is not None, "VP8_RECORD_REF_DIGESTS=1 needs the reference build (make -C oracle ref)"
-        table[key] = {"stream_sha256": sha, "md5": live}
-        with open(LISTINGS, "w") as f:
-            json.dump(table, f, indent=1, sort_keys=True)
-            f.write("\n")
-    rec = table.get(key)
-    assert rec is not None, f"{key}: no reference listing recorded in {LISTINGS}"
-    assert rec["stream_sha256"] == sha, f"{key}: the written stream is not the one the reference listing was recorded from"
-    if live is not None:
-        assert live == rec["md5"], key
-    return rec["md5"]
 
 CASES = [  # width, height, seed, log2 partitions, filter_type, dense, big coefficients, segmented
     (16, 16, 1, 0, 0, 0.5, False, True), (48, 32, 2, 1, 1, 0.4, False, True), (176, 144, 3, 2, 0, 0.3, True, True),
@@ -165,6 +132,68 @@ def test_reference_decodes_written_inter_streams_like_the_oracle(pkg, case, tmp_
         if hdr.show_frame:
             mine.append(pkg.frame_md5(bufs[show], g, w, h))
     assert mine == ref
+
+
+@pytest.mark.parametrize("case", EXTREME_CASES, ids=extreme_key)
+def test_extreme_sizes_feeder_oracle_and_reference(pkg, case, tmp_path):
+    """At 16383x16 and 16x16383 the feeder reads back the IR the stream was written from, and the reference decoder's listing is
+    what feeder + oracle decode: the oracle had only been held to the reference at small sizes."""
+    w, h = case[:2]
+    frames, expect = extreme_sequence(case)
+    _, ref = extreme_listing(case, tmp_path)
+    got = _feed(pkg, frames)
+    assert len(got) == 4 and [x[0].frame_type for x in got] == [0, 1, 1, 1]
+    g = pkg.geom(w, h)
+    bufs = [np.zeros(g.frame_size, np.uint8) for _ in range(4)]
+    mine = []
+    for k, ((hdr, mbs, coef, mvs, known), (h2, m2, c2, v2, (new, lst, gld, alt), show)) in enumerate(zip(expect, got)):
+        assert (h2.width, h2.height, h2.mb_cols, h2.mb_rows) == (w, h, (w + 15) // 16, (h + 15) // 16), k
+        assert h2.num_token_partitions == 1 << case[4], k
+        assert np.array_equal(m2[:, 0], mbs[:, 0]) and np.array_equal(m2[:, 2], mbs[:, 2]), k
+        assert np.array_equal(m2[:, 3] & 3, mbs[:, 3] & 3), k
+        if known and hdr.segmentation_enabled:
+            assert np.array_equal(m2[:, 4], mbs[:, 4]), k
+        assert np.array_equal(v2, mvs), k
+        live = (mbs[:, 3] & 1) == 0
+        assert np.array_equal(m2[live, 8:33], mbs[live, 8:33]) and np.array_equal(c2[live], coef[live]), k
+        oracle_decode(h2, m2, c2, v2, bufs[new], (bufs[lst], bufs[gld], bufs[alt]))
+        if h2.show_frame:
+            mine.append(pkg.frame_md5(bufs[show], g, w, h))
+    inter = np.concatenate([e[1] for e in expect[1:]])
+    assert (inter[:, 2] != 0).any() and (inter[:, 2] == 0).any() and (inter[inter[:, 2] != 0, 0] == 9).any()
+    assert len(mine) >= 3 and mine == ref
+
+
+@pytest.mark.parametrize("w,h,seed", [(176, 144, 12), (130, 98, 13), (33, 200, 14)])
+def test_mv_reach_that_covers_the_picture_changes_nothing(w, h, seed):
+    """synth_ir's mv_reach draws no random number: a reach at or above the picture's own span (in eighth-pel units) gives the
+    arrays None gives, for seeds the suite uses."""
+    span = (max((w + 15) // 16, (h + 15) // 16) * 16) * 8
+    for reach in (span, span + 1, 1 << 20):
+        a = synth_ir(w, h, seed, inter=True, dense=0.25)
+        b = synth_ir(w, h, seed, inter=True, dense=0.25, mv_reach=reach)
+        assert bytes(a[0]) == bytes(b[0])
+        for x, y in zip(a[1:], b[1:]):
+            assert np.array_equal(x, y)
+    # ... and a reach below it does bound them (the generator would otherwise prove nothing at the large sizes)
+    c = synth_ir(w, h, seed, inter=True, dense=0.25, mv_reach=64)
+    assert np.abs(c[3]).max() <= 64 + 400 and not np.array_equal(c[3], a[3])
+
+
+def test_mv_reach_makes_the_widest_inter_frame():
+    """16383 pixels are 131064 eighth-pel units: without a reach the vectors leave int16 (synth_ir raises OverflowError).  With
+    4000 they fit, go both ways, and some are flagged for clamping."""
+    with pytest.raises(OverflowError):
+        synth_ir(16383, 16, 5, inter=True)
+    hdr, mbs, coef, mvs = synth_ir(16383, 16, 5, inter=True, mv_reach=4000)
+    assert mvs.dtype == np.int16 and mbs.shape[0] == 1024
+    inter = mbs[:, 2] != 0
+    assert inter.sum() > 700
+    assert np.abs(mvs.astype(np.int32)).max() <= 4000 + 400
+    cols = mvs[inter, :, 1]
+    assert (cols > 2000).any() and (cols < -2000).any()           # (far both ways: the reach is used, not just the sign)
+    assert (mvs[inter, :, 0] > 0).any() and (mvs[inter, :, 0] < 0).any()
+    assert (mbs[inter, 3] & 2).any() and not (mbs[~inter, 3] & 2).any()
 
 
 def fuzz_case(seed):

@@ -150,11 +150,15 @@ ZIGZAG_RASTER = [0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15]
 ZIGZAG_COLMAJOR = [(z % 4) * 4 + z // 4 for z in ZIGZAG_RASTER]
 
 
-def synth_ir(width, height, seed, inter=False, version=0, filter_type=0, dense=0.3, big=False, segmented=True, inter_share=0.8):
+def synth_ir(width, height, seed, inter=False, version=0, filter_type=0, dense=0.3, big=False, segmented=True, inter_share=0.8,
+             mv_reach=None):
     """One frame of random IR.  Coefficients and eobs are mutually consistent the way the feeder
     produces them (eob = last coded zig-zag position + 1; Y blocks of an MB with a Y2 block start at 1).
     inter_share: of an inter frame's macroblocks, the share that is inter (1.0: not one intra macroblock, 0.0: all intra); the
-    draw that decides is made either way, and 0.8 gives the IR every seed has always given."""
+    draw that decides is made either way, and 0.8 gives the IR every seed has always given.
+    mv_reach: vectors are drawn over the whole picture, which leaves int16 (eighth-pel units) beyond about 4095 pixels; given, no
+    component goes further than mv_reach units either way, plus the 400 units a vector flagged for clamping may go past the bounds.
+    It draws no random number: None, or a reach that covers the picture, gives the IR every seed has always given."""
     P = load_package()
     rng = np.random.default_rng(seed)
     cols, rows = (width + 15) // 16, (height + 15) // 16
@@ -203,6 +207,8 @@ def synth_ir(width, height, seed, inter=False, version=0, filter_type=0, dense=0
             clampflag = rng.random() < 0.3
             lim_l, lim_r = -(c * 16 + 16) * 8, ((cols - 1 - c) * 16 + 16) * 8
             lim_t, lim_b = -(r * 16 + 16) * 8, ((rows - 1 - r) * 16 + 16) * 8
+            if mv_reach is not None:
+                lim_l, lim_r, lim_t, lim_b = (max(-mv_reach, min(mv_reach, v)) for v in (lim_l, lim_r, lim_t, lim_b))
             if clampflag:
                 lim_l -= 400; lim_r += 400; lim_t -= 400; lim_b += 400
                 mbs[i, 3] |= 2
@@ -259,6 +265,35 @@ def random_frame(g, seed):
     rng = np.random.default_rng(seed)
     buf = rng.integers(0, 256, size=g.frame_size).astype(np.uint8)
     return buf
+
+
+# ------------------------------------------------------------------------------------------
+# picture sizes at which the decoder's launch plan changes (tests/test_gpu_geometry.py, tests/test_geometry_cpu.py)
+# ------------------------------------------------------------------------------------------
+# (width, height, waves per workgroup of the wave-per-row reconstruction): the last aligned width that still gets 12 waves, the
+# first past each threshold (10, 8, 6, 4, 2), the widest picture there is -- rows enough that the rule on rows halves nothing --
+# and 9104x80, which the automatic cross-CU plan spreads over two workgroups (five rows on two waves a workgroup).  The counts are
+# written out here: the table is the expectation, recon_waves_by_rule the derivation it is checked against.  3072 macroblocks at most.
+WIDE_SIZES = [(2304, 112, 12), (2320, 96, 10), (2992, 80, 8), (4016, 64, 6), (5712, 48, 4), (9104, 48, 2), (16383, 33, 2), (9104, 80, 2)]
+TALL_SIZES = [(16, 16383), (48, 4112), (33, 8200)]       # one column and 1024 rows; 257 rows; odd width and 513 rows
+RECON_LDS_LIMIT = 160 * 1024                              # the LDS of a CU
+
+
+def recon_lds_bytes(nw, aligned_w):
+    """What a workgroup of nw waves of the wave-per-row reconstruction needs in LDS: 1 KB of progress flags and gather table, and
+    per wave two working sets (2080 B) and two line slots -- the bottom pixel line of Y, U and V, 16 bytes of pad either side of each."""
+    return 1024 + nw * 2 * (2080 + (aligned_w + 32) + 2 * (aligned_w // 2 + 32))
+
+
+def recon_waves_by_rule(width, height):
+    """At most 12 waves a workgroup, two fewer while they do not fit in LDS, halved while half of them are a wave per macroblock row"""
+    aligned_w, rows = (width + 15) // 16 * 16, (height + 15) // 16
+    nw = 12
+    while nw > 2 and recon_lds_bytes(nw, aligned_w) > RECON_LDS_LIMIT:
+        nw -= 2
+    while nw > 2 and nw // 2 >= rows:
+        nw //= 2
+    return nw
 
 
 # ------------------------------------------------------------------------------------------
