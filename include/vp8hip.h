@@ -1283,7 +1283,7 @@ int  vp8hip_frames_quant_async(vp8hip_ctx *ctx, const vp8hip_hist_job *jobs, int
  * vp8cx_encode_intra_macro_block (vp8/encoder/encodeframe.c) -- for every macroblock of any picture in the context's frame buffers,
  * bit for bit: the modes, the levels, the eobs, three figures of the decision and the reconstruction, in the caller's device
  * memory.  With it a stream can begin, and a scene cut can be coded, without leaving the device; writing the key frame's bytes from
- * these outputs is not part of it.  NOT part of it either: vp8_rd_pick_intra_mode, the trellis (`optimize` 0), activity masking,
+ * these outputs is not part of it (it is vp8hip_frames_pack_key_async's, below).  NOT part of it either: vp8_rd_pick_intra_mode, the trellis (`optimize` 0), activity masking,
  * segmentation, a choice between intra and inter, the loop filter -- the reconstruction is the UNFILTERED one, the one intra
  * prediction reads -- and rec into a frame buffer.
  *
@@ -1590,6 +1590,90 @@ int  vp8hip_pack_header_prefix(const vp8hip_pack *p, int qindex, int refresh_ent
 int  vp8hip_frames_pack_adapt_async(vp8hip_ctx *ctx, int n, const vp8hip_pack *p, const vp8hip_pack_adapt *a, const void *mv, size_t mv_stride,
                                     const void *coef, size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info, void *counts,
                                     void *probs_out);
+/* COMPRESSED KEY FRAMES from intra modes and levels: the entropy coder behind vp8hip_frames_intra_async, the key-frame counterpart
+ * of vp8hip_frames_pack_async.  vp8hip_frames_pack_key_async takes that call's modes and coef tensors as they stand and writes, per
+ * job, one complete compressed VP8 key frame into the caller's device memory, so that with frames_motion, frames_subpel,
+ * frames_quant and frames_pack behind it every byte of a stream is made on the device.  It codes with the default probability
+ * tables; probability adaptation for key frames, segmentation, loop-filter deltas, scaling bits other than 0, mb_no_coeff_skip 0,
+ * rate control and a combined "encode a key frame" call are not part of it.
+ *
+ * THE YARDSTICK for every byte is tests/vp8_writer.py's write_key_frame for the same content with segmentation off,
+ * mode_ref_lf_delta_enabled 0, refresh_entropy_probs 1, mb_no_coeff_skip 1 and no coefficient probability update (the writer fixes
+ * show_frame to 1; here the tag carries the given bit), every partition flushed as BoolEncoder.finish does: exactly how
+ * vp8hip_frames_pack_async is tied to write_inter_frame.
+ *
+ * INPUTS, device memory, vp8hip_frames_intra_async's outputs.  modes: job i's [mb_rows][mb_cols][32] of uint8 at modes + i *
+ * modes_stride (multiples of 4; the stride at least 32 MBs): byte 0 the y mode (0..4: DC, V, H, TM, B_PRED), byte 1 the uv mode
+ * (0..3), bytes 4..19 the sixteen sub-block modes (0..9: B_DC, B_TM, B_VE, B_HE, B_LD, B_RD, B_VR, B_VL, B_HD, B_HU), which are
+ * read ONLY where the y mode is B_PRED: for a 16x16 mode the contexts its neighbours see are the implied ones (DC: B_DC, V: B_VE,
+ * H: B_HE, TM: B_TM), derived from byte 0.  Bytes 2, 3 and 20..31 are not read.  coef: the LEVELS records [mb_rows][mb_cols][25][16]
+ * of int16 as vp8hip_frames_pack_async takes them (multiples of 16).  There is no eob input: a block's end is its last non-zero
+ * zigzag step.  Any byte or int16 is data, never an address: a mode out of range is caught before it indexes a table.
+ *
+ * PER MACROBLOCK.  has_y2 = the y mode is not B_PRED.  With a Y2 block the macroblock is vp8hip_frames_pack_async's: position 0 of
+ * the sixteen luma blocks is not coded and not read, luma is block type 0 coded from step 1, Y2 type 1, chroma type 2.  Without:
+ * block 24 is not read and not coded, the sixteen luma blocks are type 3 and coded from step 0.  The macroblock is skipped exactly
+ * where no coded level is left -- in 25 blocks with a Y2 block, in 24 without; the flag is derived from the levels, never from
+ * modes[2], so an inconsistent input cannot make a wrong stream.
+ *
+ * THE FIRST PARTITION.  The header, in write_key_frame's order: color_space, clamping_type, segmentation_enabled (0), filter_type,
+ * filter_level (6 bits), sharpness (3), mode_ref_lf_delta_enabled (0), log2_parts (2), qindex (7), the five deltas (a 0 flag, or 1,
+ * four magnitude bits and the sign), refresh_entropy_probs (1), 1056 "no update" flags at vp8_coef_update_probs, mb_no_coeff_skip
+ * (1), prob_skip_false (8).  Then per macroblock in raster order: the skip flag at prob_skip_false; the y mode down
+ * vp8_kf_ymode_tree (B_PRED "0", DC "100", V "101", H "110", TM "111") at {145, 156, 163, 128}; for B_PRED the sixteen sub-block
+ * modes in raster order down vp8_bmode_tree at vp8_kf_bmode_prob[A][L], A and L the modes of the block above and to the left --
+ * inside the macroblock its own, in a neighbour macroblock that one's sub-block or implied modes, outside the picture B_DC --; the
+ * uv mode (DC "0", V "10", H "110", TM "111") at {142, 114, 183}.
+ *
+ * TOKENS.  Partition r % (1 << log2_parts); a skipped macroblock codes nothing.  Order: Y2 (where present), sixteen luma, four U,
+ * four V; the tokens of a block as vp8hip_frames_pack_async codes them with vp8_default_coef_probs.  The context of a luma or
+ * chroma block is above + left "had a coded level" across macroblocks, 0 outside the picture and for skipped macroblocks.  THE Y2
+ * CONTEXT is not the neighbouring macroblock's: a B_PRED macroblock, skipped or not, leaves it untouched, so the above (left) Y2
+ * context of a macroblock is that of the nearest macroblock above it in its column (left of it in its row) that has a Y2 block: 1
+ * if that one's Y2 block had a coded level, 0 if it had none, was skipped, or there is none (the reference decoder's
+ * vp8_reset_mb_tokens_context).
+ *
+ * THE FRAME.  The 3-byte tag -- bit 0 is 0, version (3 bits), show_frame, the first partition's size (19) --, 9d 01 2a, width and
+ * height as 14 bits each with scale 0 -- the context's DISPLAY size --, the first partition, the size table, the token partitions.
+ *
+ * PARAMETERS (vp8hip_pack_key).  version 0..3, show_frame, color_space, clamping_type, filter_type 0..1, filter_level 0..63,
+ * sharpness 0..7; qindex / job_qindex and delta[5] as vp8hip_pack's; log2_parts 0..3; prob_skip_false 1..255.
+ *
+ * OUTPUTS.  dst, dst_stride, cap: as vp8hip_frames_pack_async's.  info: job i's 16 uint32 at info + 64 i: [0] status, [1] frame
+ * bytes, [2] first partition bytes, [3..10] token partition bytes, [11] skipped macroblocks, [12] B_PRED macroblocks, [13..15] 0.
+ * Status: VP8HIP_PACK_OVERFLOW and VP8HIP_PACK_BAD_LEVEL as there -- luma position 0 of a B_PRED macroblock is a coded level, its
+ * block 24 is none --, and VP8HIP_PACK_BAD_MODE: a y mode above 4, a uv mode above 3, or a sub-block mode above 9 that is read.
+ * With any of the three: info[1] = 0, the bytes inside [dst, dst + cap) are unspecified, no byte outside is touched and the other
+ * jobs are unaffected.  With OVERFLOW alone info[2..10] are the sizes the partitions would have had, so 10 + [2] + 3 (parts - 1) +
+ * the sum of [3..10] is the cap that suffices.  With BAD_LEVEL or BAD_MODE [2..10] are unspecified; [11] and [12] are counted as
+ * defined, a y mode above 4 counting as a 16x16 mode (it has a Y2 block and is no B_PRED macroblock).
+ *
+ * vp8hip_pack_key_bound(ctx, log2_parts): a cap that always suffices, a multiple of 16, derived as vp8hip_pack_bound: 7 bits a put.
+ * The first partition of a macroblock is at most the skip flag, the B_PRED bit, sixteen sub-block modes at the longest path of
+ * vp8_bmode_tree (B_HD, B_HU: seven puts) and three puts for the uv mode: 117 puts, 819 bits, 103 bytes (a 16x16 macroblock has
+ * seven puts).  The tokens are 24 blocks from step 0 or 25 of which sixteen from step 1: within vp8hip_pack_bound's 6672 bytes.
+ * The bound is 10 + (VP8HIP_PACK_HEAD_MAX + 8 + 103 MBs) + 3 (parts - 1) + 6672 MBs + 4 parts, rounded up.
+ *
+ * vp8hip_pack_key_header(p, qindex, out): host only, the mirror of vp8hip_pack_header: the key frame's header fields through the C
+ * bool encoder up to where the per-macroblock data begin, in vp8hip_pack_head's form; -2 for a NULL or a value out of range.
+ *
+ * Stream, determinism, scratch (32 bytes a macroblock of records and the partitions' regions, in the buffer
+ * vp8hip_frames_rgb_async keeps), groups of at most 1024 jobs, eight headers and 2 GB: as vp8hip_frames_pack_async.  It returns -2
+ * with nothing enqueued for what that call refuses, `modes` treated as `coef` is: NULL, misaligned (4), a stride below 32 MBs, not
+ * device memory of the context's device, too small for n jobs, or overlapping dst or info. */
+#define VP8HIP_PACK_BAD_MODE 16
+typedef struct vp8hip_pack_key {
+    int version, show_frame, color_space, clamping_type, filter_type, filter_level, sharpness;
+    int qindex;                /* 0..127; not read where job_qindex is given */
+    int delta[5];              /* y1dc, y2dc, y2ac, uvdc, uvac: -15..15 */
+    int log2_parts;            /* 0..3 */
+    int prob_skip_false;       /* 1..255 */
+    const uint8_t *job_qindex; /* host memory, n bytes, or NULL: qindex for every job */
+} vp8hip_pack_key;
+size_t vp8hip_pack_key_bound(const vp8hip_ctx *ctx, int log2_parts);
+int  vp8hip_pack_key_header(const vp8hip_pack_key *p, int qindex, vp8hip_pack_head *out);
+int  vp8hip_frames_pack_key_async(vp8hip_ctx *ctx, int n, const vp8hip_pack_key *p, const void *modes, size_t modes_stride, const void *coef,
+                                  size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info);
 /* the HIP device the context runs on (a device of -1 at vp8hip_create resolved) */
 int  vp8hip_device(const vp8hip_ctx *ctx);
 /* A frame buffer has two forms on the device: the RASTER form (vp8ir_geom: the reference's YV12 layout, borders included), which

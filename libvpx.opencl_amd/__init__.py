@@ -624,6 +624,7 @@ def quant_factors(qindex, deltas=(0, 0, 0, 0, 0)):
 
 
 PACK_OVERFLOW, PACK_BAD_VECTOR, PACK_BAD_LEVEL, PACK_CLAMPS = 1, 2, 4, 8      # VP8HIP_PACK_*: the status bits of Vp8Hip.frames_pack
+PACK_BAD_MODE = 16                                            # VP8HIP_PACK_BAD_MODE: frames_pack_key's, beside OVERFLOW and BAD_LEVEL
 INTRA_PLANES = {"rd16": 1, "rd4": 2, "rate": 4, "eobs": 8, "recsse": 16}        # VP8HIP_INTRA_*: bit order = plane order
 INTRA_NO_BPRED = 1                                            # VP8HIP_INTRA_NO_BPRED
 
@@ -662,16 +663,18 @@ PACK_DEFAULTS = dict(version=0, show_frame=1, filter_type=0, filter_level=0, sha
                      prob_last=140, prob_gf=100)
 
 
-def _pack_params(who, qindex, deltas, fields, n=None):
-    """-> (PackParams, the array job_qindex points to -- to be kept alive -- or None); ValueError for an unknown field or a wrong count"""
-    unknown = set(fields) - set(PACK_DEFAULTS)
+def _pack_params(who, qindex, deltas, fields, n=None, key=False):
+    """-> (PackParams -- key: PackKeyParams --, the array job_qindex points to -- to be kept alive -- or None); ValueError for an
+    unknown field or a wrong count"""
+    defaults = PACK_KEY_DEFAULTS if key else PACK_DEFAULTS
+    unknown = set(fields) - set(defaults)
     if unknown:
-        raise ValueError(f"{who}: unknown parameters {sorted(unknown)!r} (of {', '.join(PACK_DEFAULTS)})")
+        raise ValueError(f"{who}: unknown parameters {sorted(unknown)!r} (of {', '.join(defaults)})")
     d = [int(v) for v in deltas]
     if len(d) != 5:
         raise ValueError(f"{who}: five deltas (y1dc, y2dc, y2ac, uvdc, uvac)")
-    p = PackParams()
-    for name, v in {**PACK_DEFAULTS, **fields}.items():
+    p = PackKeyParams() if key else PackParams()
+    for name, v in {**defaults, **fields}.items():
         setattr(p, name, int(v))
     p.delta = (c_int * 5)(*d)
     jq = None
@@ -747,11 +750,39 @@ def pack_header_prefix(qindex=40, deltas=(0, 0, 0, 0, 0), refresh_entropy_probs=
 
 
 def pack_frames(data, info):
-    """(data, info) of Vp8Hip.frames_pack (torch tensors or arrays) -> a list of each job's compressed frame as bytes, None where the
-    job's status has PACK_OVERFLOW, PACK_BAD_VECTOR or PACK_BAD_LEVEL"""
+    """(data, info) of Vp8Hip.frames_pack or frames_pack_key (torch tensors or arrays) -> a list of each job's compressed frame as
+    bytes, None where the job's status has PACK_OVERFLOW, PACK_BAD_VECTOR, PACK_BAD_LEVEL or PACK_BAD_MODE"""
     d = np.asarray(data.cpu() if hasattr(data, "cpu") else data)
     i = np.asarray(info.cpu() if hasattr(info, "cpu") else info)
-    return [None if int(s[0]) & 7 else d[k, :int(s[1])].tobytes() for k, s in enumerate(i)]
+    fatal = PACK_OVERFLOW | PACK_BAD_VECTOR | PACK_BAD_LEVEL | PACK_BAD_MODE
+    return [None if int(s[0]) & fatal else d[k, :int(s[1])].tobytes() for k, s in enumerate(i)]
+
+
+# what Vp8Hip.frames_pack_key and pack_key_header take beside the modes, the levels and the quantiser, with their defaults
+PACK_KEY_DEFAULTS = dict(version=0, show_frame=1, color_space=0, clamping_type=0, filter_type=0, filter_level=0, sharpness=0, log2_parts=0,
+                         prob_skip_false=200)
+
+
+def pack_key_bound(w, h, log2_parts=0):
+    """a `cap` that always suffices for a frame of Vp8Hip.frames_pack_key at the display size w x h: what vp8hip_pack_key_bound gives
+    for a context of that size (include/vp8hip.h derives it: 7 bits a put, 117 puts a macroblock in the first partition, 7625 in
+    the tokens, ten bytes of frame header); 0 for a size outside 1..16383 or log2_parts outside 0..3"""
+    if not (1 <= int(w) <= 16383 and 1 <= int(h) <= 16383 and 0 <= int(log2_parts) <= 3):
+        return 0
+    cells, parts = ((int(w) + 15) // 16) * ((int(h) + 15) // 16), 1 << int(log2_parts)
+    return (10 + (64 + 8 + 103 * cells) + 3 * (parts - 1) + 6672 * cells + 4 * parts + 15) // 16 * 16
+
+
+def pack_key_header(qindex=40, deltas=(0, 0, 0, 0, 0), **fields):
+    """the frame header of Vp8Hip.frames_pack_key's frames through the library's C bool encoder, up to where the per-macroblock
+    data begin (vp8hip_pack_key_header; on the host, no GPU): a dict as pack_header's.  fields: PACK_KEY_DEFAULTS' names"""
+    p, _ = _pack_params("pack_key_header", 0, deltas, fields, key=True)
+    h = PackHead()
+    if load_hip().vp8hip_pack_key_header(ctypes.byref(p), int(qindex), ctypes.byref(h)):
+        raise ValueError(f"pack_key_header: qindex {qindex} (0..127), deltas {deltas!r} (-15..15) or {fields!r} out of range")
+    out = {name: int(getattr(h, name)) for name in ("bottom", "range", "bit_count", "cache", "pending", "settled")}
+    out["bytes"] = bytes(h.bytes[:h.nbytes])
+    return out
 
 
 def ssim_mean(scores):
@@ -985,6 +1016,12 @@ class PackParams(ctypes.Structure):         # vp8hip_pack, include/vp8hip.h
                [("job_qindex", ctypes.POINTER(ctypes.c_uint8))]
 
 
+class PackKeyParams(ctypes.Structure):      # vp8hip_pack_key, include/vp8hip.h
+    _fields_ = [(name, c_int) for name in ("version", "show_frame", "color_space", "clamping_type", "filter_type", "filter_level", "sharpness",
+                                           "qindex")] + [("delta", c_int * 5), ("log2_parts", c_int), ("prob_skip_false", c_int),
+                                                         ("job_qindex", ctypes.POINTER(ctypes.c_uint8))]
+
+
 class PackHead(ctypes.Structure):           # vp8hip_pack_head, include/vp8hip.h
     _fields_ = [("bottom", ctypes.c_uint32), ("range", ctypes.c_uint32), ("bit_count", ctypes.c_uint32), ("nbytes", ctypes.c_uint32),
                 ("cache", ctypes.c_int32), ("pending", ctypes.c_uint32), ("settled", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
@@ -1143,6 +1180,11 @@ def load_hip():
         L.vp8hip_pack_header_prefix.argtypes = [ctypes.POINTER(PackParams), c_int, c_int, ctypes.POINTER(PackHead)]
         L.vp8hip_frames_pack_adapt_async.argtypes = [c_void_p, c_int, ctypes.POINTER(PackParams), ctypes.POINTER(PackAdapt), c_void_p, c_size_t, c_void_p,
                                                      c_size_t, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p]
+        L.vp8hip_pack_key_bound.argtypes = [c_void_p, c_int]
+        L.vp8hip_pack_key_bound.restype = c_size_t
+        L.vp8hip_pack_key_header.argtypes = [ctypes.POINTER(PackKeyParams), c_int, ctypes.POINTER(PackHead)]
+        L.vp8hip_frames_pack_key_async.argtypes = [c_void_p, c_int, ctypes.POINTER(PackKeyParams), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                                   c_size_t, c_size_t, c_void_p]
         # One HIP runtime per process: torch carries its own libamdhip64 (SONAME libamdhip64.so.7), which libvp8hip.so's
         # dependency resolves to only if torch was loaded first; otherwise torch maps a second runtime later, whose device
         # pointers this library's runtime does not know
@@ -2233,6 +2275,48 @@ class Vp8Hip:
         outs = [("out_data", out_data, "uint8", (n, cap)), ("out_info", out_info, "int32", (n, 16))]
         made = self._to_torch(who, outs, lambda dp, ds, ip, istride: self.L.vp8hip_frames_pack_async(
             self.h, n, ctypes.byref(p), mptr, mstride, c_void_p(coef.data_ptr()), coef.stride(0) * 2, dp, ds, cap, ip), "vp8hip_frames_pack_async")
+        del jq
+        return made[0], made[1]
+
+    def pack_key_bound(self, log2_parts=0):
+        """a `cap` that always suffices for a frame of frames_pack_key at the context's size (vp8hip_pack_key_bound)"""
+        size = int(self.L.vp8hip_pack_key_bound(self.h, int(log2_parts)))
+        if not size:
+            raise ValueError(f"pack_key_bound: log2_parts {log2_parts} (0..3) of a configured context")
+        return size
+
+    def frames_pack_key(self, modes, coef, qindex=40, deltas=(0, 0, 0, 0, 0), cap=None, out_data=None, out_info=None, **fields):
+        """Compressed VP8 key frames from frames_intra's modes and levels on the context's device (vp8hip_frames_pack_key_async;
+        include/vp8hip.h has the definition): job i's frame -- tag, start code and size, first partition, size table, 1 <<
+        log2_parts token partitions -- from modes[i] and coef[i], byte for byte what the test suite's stream writer writes for the
+        same content.  `modes`: frames_intra's "modes" tensor [n, mb_rows, mb_cols, 32] (torch.uint8, stride(0) a multiple of 4) --
+        [0] the y mode, [1] the uv mode, [4..19] the sub-block modes, read where the y mode is B_PRED; `coef`: its "coef" tensor of
+        levels [n, mb_rows, mb_cols, 25, 16] (torch.int16, stride(0) a multiple of 16 bytes).  qindex, deltas, cap (default:
+        out_data's second dimension, else pack_key_bound(log2_parts)), out_data, out_info: as frames_pack; fields:
+        PACK_KEY_DEFAULTS' names.  Returns (data, info): torch.uint8 [n, cap] and torch.int32 [n, 16] -- [0] the status
+        (PACK_OVERFLOW, PACK_BAD_LEVEL, PACK_BAD_MODE), [1] the frame's bytes (0 where the status forbids), [2] the first
+        partition's, [3..10] the token partitions', [11] skipped macroblocks, [12] B_PRED macroblocks; pack_frames gives the frames
+        as bytes.  Stream ordering, the `import torch` first rule and the remark on record_stream: as frames_scaled."""
+        who = "frames_pack_key"
+        torch, dev = self._torch_device(who)
+        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
+        if not hasattr(coef, "shape") or len(coef.shape) != 5 or not self._dense(coef, torch.int16, (coef.shape[0], rows, cols, 25, 16), dev) or not coef.shape[0]:
+            raise ValueError(f"{who}: coef must be an int16 tensor {['n', rows, cols, 25, 16]}, each job dense, on {dev}")
+        n = int(coef.shape[0])
+        if not hasattr(modes, "shape") or not self._dense(modes, torch.uint8, (n, rows, cols, 32), dev):
+            raise ValueError(f"{who}: modes must be a uint8 tensor {[n, rows, cols, 32]}, each job dense, on {dev}")
+        p, jq = _pack_params(who, qindex, deltas, fields, n, key=True)
+        if cap is None:
+            cap = int(out_data.shape[1]) if out_data is not None and len(out_data.shape) == 2 else int(self.L.vp8hip_pack_key_bound(self.h, p.log2_parts))
+        cap = int(cap)
+        if cap < 16 or cap % 16:
+            raise ValueError(f"{who}: cap {cap} (a multiple of 16; log2_parts 0..3)")
+        if out_info is not None and not (self._dense(out_info, torch.int32, (n, 16), dev) and out_info.is_contiguous()):
+            raise ValueError(f"{who}: out_info must be a contiguous int32 tensor {[n, 16]} on {dev}")
+        outs = [("out_data", out_data, "uint8", (n, cap)), ("out_info", out_info, "int32", (n, 16))]
+        made = self._to_torch(who, outs, lambda dp, ds, ip, istride: self.L.vp8hip_frames_pack_key_async(
+            self.h, n, ctypes.byref(p), c_void_p(modes.data_ptr()), modes.stride(0), c_void_p(coef.data_ptr()), coef.stride(0) * 2, dp, ds, cap, ip),
+            "vp8hip_frames_pack_key_async")
         del jq
         return made[0], made[1]
 

@@ -24,11 +24,18 @@ namespace pack_tables {
 #define PACK_MB_TOKEN_BYTES 6672
 #define PACK_FLUSH_BYTES 4              // BoolEncoder.finish
 #define PACK_FIRST_LIMIT (1u << 19)     // the frame tag has 19 bits for the first partition's size
+// A key frame (vp8hip_frames_pack_key_async; vp8_pack_key.hip has its record): ten bytes before the first partition -- the tag, the
+// start code, width and height.  First partition, per macroblock: the skip flag, the B_PRED bit of vp8_kf_ymode_tree, sixteen
+// sub-block modes at the longest path of vp8_bmode_tree, seven puts, and three puts for the uv mode: 117 puts, 819 bits (a 16x16
+// mode is seven puts in all).  The tokens are at most the inter frame's: 24 blocks from step 0, or 25 with sixteen of them from step 1.
+#define PACK_KEY_HEADER_BYTES 10
+#define PACK_KEY_MB_FIRST_BYTES 103
 
 #define PACK_OVERFLOW 1u
 #define PACK_BAD_VECTOR 2u
 #define PACK_BAD_LEVEL 4u
 #define PACK_CLAMPS 8u
+#define PACK_BAD_MODE 16u               // (key frames)
 #define PACK_MAX_LEVEL 2114             // DCT_CAT6: 67 + 2047
 
 // a job's counters: [0] status, [1] skipped macroblocks, [2..5] ZEROMV / NEARESTMV / NEARMV / NEWMV, [6] first partition bytes,
@@ -57,6 +64,14 @@ struct PackLaunch {
     size_t jobs_off, job_bytes;
     PackHead heads[PACK_MAX_HEADS];
     uint8_t head_of[PACK_MAX_JOBS];
+};
+
+// what the kernels of vp8hip_frames_pack_key_async take beside PackLaunch (of which has_mv, ref_frame and the three reference
+// probabilities are not read; counter [2] counts the B_PRED macroblocks)
+struct PackKey {
+    const uint8_t *modes;
+    size_t modes_stride;
+    int width, height;                  // the display size, 14 bits each in the frame
 };
 
 // vp8hip_frames_pack_adapt_async adds, behind the last job's area (adapt_off, a multiple of 256), PACK_ADAPT_JOB_BYTES a job:

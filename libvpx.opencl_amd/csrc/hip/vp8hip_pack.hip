@@ -3,7 +3,8 @@
 // device memory.  The checks and the plan are made here, once per call, by one function for both calls; the kernels are in
 // vp8_pack.hip and vp8_pack_adapt.hip.  The frame header is coded on the host, once per distinct qindex, and travels with its coder state
 // in the arguments of the launches (PackLaunch), so a call of many jobs is cut where those are full -- and where the scratch, the
-// buffer the RGB call keeps, would pass PACK_SCRATCH_MAX.
+// buffer the RGB call keeps, would pass PACK_SCRATCH_MAX.  vp8hip_frames_pack_key_async with its bound and header, the key frames
+// from frames_intra's modes and levels, is at the end: the same scratch, groups and headers, the kernels of vp8_pack_key.hip.
 #include "vp8hip_ctx.hip.h"
 #include "vp8_pack.hip.h"
 
@@ -17,6 +18,12 @@ extern "C" __global__ void vp8_pack_choose_kernel(uint8_t *scratch, PackLaunch L
 extern "C" __global__ void vp8_pack_first_adapt_kernel(uint8_t *scratch, int jobs, PackLaunch L, PackAdapt A);
 extern "C" __global__ void vp8_pack_tokens_adapt_kernel(const uint8_t *coef, size_t coef_stride, uint8_t *scratch, int jobs, PackLaunch L, PackAdapt A);
 extern "C" __global__ void vp8_pack_adapt_info_kernel(const uint8_t *scratch, int jobs, PackAdapt A);
+// vp8_pack_key.hip
+extern "C" __global__ void vp8_pack_key_plan_kernel(const uint8_t *coef, size_t coef_stride, uint8_t *scratch, PackLaunch L, PackKey K);
+extern "C" __global__ void vp8_pack_key_y2_kernel(uint8_t *scratch, int jobs, PackLaunch L);
+extern "C" __global__ void vp8_pack_key_first_kernel(uint8_t *scratch, int jobs, PackLaunch L);
+extern "C" __global__ void vp8_pack_key_tokens_kernel(const uint8_t *coef, size_t coef_stride, uint8_t *scratch, int jobs, PackLaunch L);
+extern "C" __global__ void vp8_pack_key_assemble_kernel(const uint8_t *scratch, uint8_t *dst, size_t dst_stride, uint32_t *info, PackLaunch L, PackKey K);
 
 #define PACK_SCRATCH_MAX ((size_t)2 << 30)      // the scratch of a launch group: at most this much (one job at least)
 #define PACK_PART_LIMIT (((size_t)1 << 24) - 16) // the size table has 24 bits for a token partition
@@ -27,6 +34,7 @@ static_assert(sizeof(PackLaunch) + sizeof(PackAdapt) <= 3072, "the launch's argu
 static_assert(sizeof(vp8hip_pack_probs) == PACK_PROBS_BYTES && offsetof(vp8hip_pack_probs, mvc) == 1056, "");
 static_assert(VP8HIP_ADAPT_COEF == PACK_ADAPT_COEF && VP8HIP_ADAPT_MV == PACK_ADAPT_MV && VP8HIP_ADAPT_SKIP == PACK_ADAPT_SKIP &&
               VP8HIP_ADAPT_REF == PACK_ADAPT_REF, "");
+static_assert(VP8HIP_PACK_BAD_MODE == PACK_BAD_MODE && sizeof(PackLaunch) + sizeof(PackKey) <= 3072, "");
 
 // RFC 6386 section 7.3 as tests/vp8_writer.py's BoolEncoder states it: a carry walks back through the bytes written
 struct HostBool {
@@ -291,4 +299,142 @@ extern "C" int vp8hip_frames_pack_adapt_async(vp8hip_ctx *c, int n, const vp8hip
     const char *who = "vp8hip_frames_pack_adapt_async";
     if (!a) return fail(c, -2, "%s: bad arguments", who);
     return pack_frames(c, who, n, p, a, mv, mv_stride, coef, coef_stride, dst, dst_stride, cap, info, counts, probs_out);
+}
+
+// ---- key frames: vp8hip_frames_pack_key_async, vp8hip_pack_key_bound, vp8hip_pack_key_header ----------------------------------------
+static bool pack_key_params_ok(const vp8hip_pack_key *p)
+{
+    if (!p) return false;
+    for (int k = 0; k < 5; k++)
+        if (!in(p->delta[k], -15, 15)) return false;
+    for (int f : {p->show_frame, p->color_space, p->clamping_type, p->filter_type})
+        if (!in(f, 0, 1)) return false;
+    return in(p->version, 0, 3) && in(p->filter_level, 0, 63) && in(p->sharpness, 0, 7) && in(p->log2_parts, 0, 3) && in(p->prob_skip_false, 1, 255);
+}
+
+extern "C" int vp8hip_pack_key_header(const vp8hip_pack_key *p, int qindex, vp8hip_pack_head *out)
+{
+    if (!out || !pack_key_params_ok(p) || !in(qindex, 0, 127)) return -2;
+    memset(out, 0, sizeof *out);
+    HostBool e;
+    e.out = out->bytes; e.n = 0; e.cap = sizeof out->bytes;
+    e.literal(p->color_space, 1);
+    e.literal(p->clamping_type, 1);
+    e.literal(0, 1);                                         // segmentation_enabled
+    e.literal(p->filter_type, 1);
+    e.literal(p->filter_level, 6);
+    e.literal(p->sharpness, 3);
+    e.literal(0, 1);                                         // mode_ref_lf_delta_enabled
+    e.literal(p->log2_parts, 2);
+    e.literal(qindex, 7);
+    for (int k = 0; k < 5; k++) {
+        const int d = p->delta[k];
+        e.put(d != 0, 128);
+        if (d) { e.literal(d < 0 ? -d : d, 4); e.put(d < 0, 128); }
+    }
+    e.literal(1, 1);                                         // refresh_entropy_probs
+    for (int i = 0; i < 1056; i++) e.put(0, pack_tables::vp8t_coef_update_probs[i]);
+    e.literal(1, 1);                                         // mb_no_coeff_skip
+    e.literal(p->prob_skip_false, 8);
+    if (e.over) return -1;
+    out->bottom = e.bottom; out->range = e.range; out->bit_count = (uint32_t)e.bit_count; out->nbytes = (uint32_t)e.n;
+    size_t i = e.n;
+    while (i > 0 && out->bytes[i - 1] == 255) i--;
+    out->cache = i ? out->bytes[i - 1] : -1;
+    out->settled = i ? (uint32_t)(i - 1) : 0;
+    out->pending = (uint32_t)(e.n - i);
+    return 0;
+}
+
+static size_t pack_key_first_bound(size_t nmb) { return PACK_HEAD_BYTES + 4 + PACK_KEY_MB_FIRST_BYTES * nmb + PACK_FLUSH_BYTES; }
+
+extern "C" size_t vp8hip_pack_key_bound(const vp8hip_ctx *c, int log2_parts)
+{
+    if (!c || !c->width || log2_parts < 0 || log2_parts > 3) return 0;
+    const size_t nmb = (size_t)c->dg.mb_cols * c->dg.mb_rows, parts = (size_t)1 << log2_parts;
+    return align_up(PACK_KEY_HEADER_BYTES + pack_key_first_bound(nmb) + 3 * (parts - 1) + PACK_MB_TOKEN_BYTES * nmb + PACK_FLUSH_BYTES * parts, 16);
+}
+
+// The plan is pack_frames' without the adapt part: the same scratch, groups and headers; the kernels are vp8_pack_key.hip's.
+extern "C" int vp8hip_frames_pack_key_async(vp8hip_ctx *c, int n, const vp8hip_pack_key *p, const void *modes, size_t modes_stride, const void *coef,
+                                            size_t coef_stride, void *dst, size_t dst_stride, size_t cap, void *info)
+{
+    const char *who = "vp8hip_frames_pack_key_async";
+    if (!c || n < 1 || !p || !modes || !coef || !dst || !info || !c->width) return fail(c, -2, "%s: bad arguments", who);
+    if (!pack_key_params_ok(p))
+        return fail(c, -2, "%s: version %d (0..3), flags %d %d %d %d (0, 1), filter level %d (0..63), sharpness %d (0..7), deltas %d %d %d %d %d "
+                    "(-15..15), log2_parts %d (0..3), prob_skip_false %d (1..255)", who, p->version, p->show_frame, p->color_space, p->clamping_type,
+                    p->filter_type, p->filter_level, p->sharpness, p->delta[0], p->delta[1], p->delta[2], p->delta[3], p->delta[4], p->log2_parts,
+                    p->prob_skip_false);
+    if (!p->job_qindex && (p->qindex < 0 || p->qindex > 127)) return fail(c, -2, "%s: qindex %d (0..127)", who, p->qindex);
+    if (p->job_qindex)
+        for (int i = 0; i < n; i++)
+            if (p->job_qindex[i] > 127) return fail(c, -2, "%s: job_qindex[%d] = %d (0..127)", who, i, p->job_qindex[i]);
+    if (cap < 16 || cap % 16 || cap > dst_stride) return fail(c, -2, "%s: cap %zu (a multiple of 16, 16 .. the stride %zu)", who, cap, dst_stride);
+    const size_t nmb = (size_t)c->dg.mb_cols * c->dg.mb_rows;
+    const struct { const void *p; size_t stride, size, align; const char *name; } t[4] = {
+        {dst, dst_stride, cap, 16, "dst"}, {info, 64, 64, 4, "info"}, {modes, modes_stride, 32 * nmb, 4, "modes"}, {coef, coef_stride, 800 * nmb, 16, "coef"}};
+    for (const auto &s : t)
+        if (int rc = vp8hip_check_named_dst(c, who, s.name, s.p, s.stride, s.size, s.align, n)) return rc;
+    for (int i = 0; i < 2; i++)                              // the outputs against each other and against the inputs
+        for (int j = i + 1; j < 4; j++)
+            if (vp8hip_spans_overlap(t[i].p, t[i].stride, n, t[j].p, t[j].stride, n)) return fail(c, -2, "%s: %s and %s overlap", who, t[i].name, t[j].name);
+    HIPCHK(c, hipSetDevice(c->device));
+
+    PackLaunch L;
+    memset(&L, 0, sizeof(L));
+    const int parts = 1 << p->log2_parts;
+    L.mb_cols = c->dg.mb_cols; L.mb_rows = c->dg.mb_rows;
+    L.log2_parts = p->log2_parts;
+    L.prob_skip = p->prob_skip_false;
+    L.version = p->version; L.show_frame = p->show_frame;
+    const size_t bound = vp8hip_pack_key_bound(c, p->log2_parts), frame_limit = PACK_KEY_HEADER_BYTES + PACK_FIRST_LIMIT + 24 + 8 * PACK_PART_LIMIT;
+    const size_t eff = cap < bound ? cap : bound;
+    const size_t part_rows = ((size_t)c->dg.mb_rows + parts - 1) / parts;
+    const size_t part_bound = PACK_MB_TOKEN_BYTES * part_rows * c->dg.mb_cols + PACK_FLUSH_BYTES;
+    auto least = [](size_t a, size_t b, size_t d) { a = a < b ? a : b; return a < d ? a : d; };
+    L.cap = (uint32_t)(eff < frame_limit ? eff : frame_limit);
+    L.first_cap = (uint32_t)align_up(least(pack_key_first_bound(nmb), eff, PACK_FIRST_LIMIT), 16);
+    L.part_cap = (uint32_t)align_up(least(part_bound, eff, PACK_PART_LIMIT), 16);
+    L.job_bytes = PACK_RECORD_BYTES * nmb + L.first_cap + (size_t)parts * L.part_cap;
+    size_t chunk = n < PACK_MAX_JOBS ? n : PACK_MAX_JOBS;
+    const size_t fit = PACK_SCRATCH_MAX / (L.job_bytes + 4 * PACK_CTR_DWORDS);
+    if (chunk > fit) chunk = fit < 1 ? 1 : fit;
+    L.jobs_off = align_up(chunk * 4 * PACK_CTR_DWORDS, 256);
+    const size_t need = L.jobs_off + chunk * L.job_bytes;
+    if (c->d_rgb.grow(need) != hipSuccess) return fail(c, -1, "%s: no device memory for %zu bytes of scratch", who, need);
+    uint8_t *scratch = c->d_rgb;
+    PackKey K;
+    K.modes_stride = modes_stride;
+    K.width = c->width; K.height = c->height;
+
+    for (int i0 = 0; i0 < n;) {
+        int m = 0, heads = 0, qof[PACK_MAX_HEADS];
+        for (; i0 + m < n && m < (int)chunk; m++) {
+            const int q = p->job_qindex ? p->job_qindex[i0 + m] : p->qindex;
+            int k = 0;
+            while (k < heads && qof[k] != q) k++;
+            if (k == heads) {
+                if (heads == PACK_MAX_HEADS) break;
+                qof[heads] = q;
+                vp8hip_pack_head h;
+                if (vp8hip_pack_key_header(p, q, &h)) return fail(c, -1, "%s: the frame header does not fit %d bytes", who, VP8HIP_PACK_HEAD_MAX);
+                memcpy(&L.heads[heads++], &h, sizeof h);
+            }
+            L.head_of[m] = (uint8_t)k;
+        }
+        const uint8_t *coef_at = (const uint8_t *)coef + coef_stride * (size_t)i0;
+        K.modes = (const uint8_t *)modes + modes_stride * (size_t)i0;
+        const dim3 plan_grid((unsigned)((nmb + 7) / 8), (unsigned)m);
+        HIPCHK(c, hipMemsetAsync(scratch, 0, (size_t)m * 4 * PACK_CTR_DWORDS, c->stream));
+        hipLaunchKernelGGL(vp8_pack_key_plan_kernel, plan_grid, dim3(256), 0, c->stream, coef_at, coef_stride, scratch, L, K);
+        hipLaunchKernelGGL(vp8_pack_key_y2_kernel, dim3((unsigned)((m * c->dg.mb_cols + 63) / 64)), dim3(64), 0, c->stream, scratch, m, L);
+        hipLaunchKernelGGL(vp8_pack_key_first_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, c->stream, scratch, m, L);
+        hipLaunchKernelGGL(vp8_pack_key_tokens_kernel, dim3((unsigned)((m * parts + 63) / 64)), dim3(64), 0, c->stream, coef_at, coef_stride, scratch, m, L);
+        hipLaunchKernelGGL(vp8_pack_key_assemble_kernel, dim3((unsigned)m), dim3(256), 0, c->stream, (const uint8_t *)scratch,
+                           (uint8_t *)dst + dst_stride * (size_t)i0, dst_stride, (uint32_t *)info + 16 * (size_t)i0, L, K);
+        HIPCHK(c, hipGetLastError());
+        i0 += m;
+    }
+    return 0;
 }
