@@ -691,14 +691,26 @@ def _pack_params(who, qindex, deltas, fields, n=None, key=False):
     return p, jq
 
 
+def _pack_bound(w, h, log2_parts, header, first):
+    """the bound of a frame with `header` bytes before the first partition and at most `first` bytes a macroblock in it"""
+    if not (1 <= int(w) <= 16383 and 1 <= int(h) <= 16383 and 0 <= int(log2_parts) <= 3):
+        return 0
+    cells, parts = ((int(w) + 15) // 16) * ((int(h) + 15) // 16), 1 << int(log2_parts)
+    return (header + (64 + 8 + first * cells) + 3 * (parts - 1) + 6672 * cells + 4 * parts + 15) // 16 * 16
+
+
+def _pack_head_dict(h):
+    """a PackHead as the dict the three header functions return"""
+    out = {name: int(getattr(h, name)) for name in ("bottom", "range", "bit_count", "cache", "pending", "settled")}
+    out["bytes"] = bytes(h.bytes[:h.nbytes])
+    return out
+
+
 def pack_bound(w, h, log2_parts=0):
     """a `cap` that always suffices for a frame of Vp8Hip.frames_pack at the display size w x h: what vp8hip_pack_bound gives for a
     context of that size (include/vp8hip.h derives it: 7 bits a put, 32 puts a macroblock in the first partition, 7625 in the
     tokens); 0 for a size outside 1..16383 or log2_parts outside 0..3"""
-    if not (1 <= int(w) <= 16383 and 1 <= int(h) <= 16383 and 0 <= int(log2_parts) <= 3):
-        return 0
-    cells, parts = ((int(w) + 15) // 16) * ((int(h) + 15) // 16), 1 << int(log2_parts)
-    return (3 + (64 + 8 + 28 * cells) + 3 * (parts - 1) + 6672 * cells + 4 * parts + 15) // 16 * 16
+    return _pack_bound(w, h, log2_parts, 3, 28)
 
 
 def pack_header(qindex=40, deltas=(0, 0, 0, 0, 0), **fields):
@@ -710,9 +722,7 @@ def pack_header(qindex=40, deltas=(0, 0, 0, 0, 0), **fields):
     h = PackHead()
     if load_hip().vp8hip_pack_header(ctypes.byref(p), int(qindex), ctypes.byref(h)):
         raise ValueError(f"pack_header: qindex {qindex} (0..127), deltas {deltas!r} (-15..15) or {fields!r} out of range")
-    out = {name: int(getattr(h, name)) for name in ("bottom", "range", "bit_count", "cache", "pending", "settled")}
-    out["bytes"] = bytes(h.bytes[:h.nbytes])
-    return out
+    return _pack_head_dict(h)
 
 
 ADAPT_COEF, ADAPT_MV, ADAPT_SKIP, ADAPT_REF = 1, 2, 4, 8     # VP8HIP_ADAPT_*: what Vp8Hip.frames_pack_adapt fits to the frame's counts
@@ -744,9 +754,7 @@ def pack_header_prefix(qindex=40, deltas=(0, 0, 0, 0, 0), refresh_entropy_probs=
     if load_hip().vp8hip_pack_header_prefix(ctypes.byref(p), int(qindex), int(refresh_entropy_probs), ctypes.byref(h)):
         raise ValueError(f"pack_header_prefix: qindex {qindex} (0..127), deltas {deltas!r} (-15..15), refresh_entropy_probs "
                          f"{refresh_entropy_probs} (0, 1) or {fields!r} out of range")
-    out = {name: int(getattr(h, name)) for name in ("bottom", "range", "bit_count", "cache", "pending", "settled")}
-    out["bytes"] = bytes(h.bytes[:h.nbytes])
-    return out
+    return _pack_head_dict(h)
 
 
 def pack_frames(data, info):
@@ -767,10 +775,7 @@ def pack_key_bound(w, h, log2_parts=0):
     """a `cap` that always suffices for a frame of Vp8Hip.frames_pack_key at the display size w x h: what vp8hip_pack_key_bound gives
     for a context of that size (include/vp8hip.h derives it: 7 bits a put, 117 puts a macroblock in the first partition, 7625 in
     the tokens, ten bytes of frame header); 0 for a size outside 1..16383 or log2_parts outside 0..3"""
-    if not (1 <= int(w) <= 16383 and 1 <= int(h) <= 16383 and 0 <= int(log2_parts) <= 3):
-        return 0
-    cells, parts = ((int(w) + 15) // 16) * ((int(h) + 15) // 16), 1 << int(log2_parts)
-    return (10 + (64 + 8 + 103 * cells) + 3 * (parts - 1) + 6672 * cells + 4 * parts + 15) // 16 * 16
+    return _pack_bound(w, h, log2_parts, 10, 103)
 
 
 def pack_key_header(qindex=40, deltas=(0, 0, 0, 0, 0), **fields):
@@ -780,9 +785,7 @@ def pack_key_header(qindex=40, deltas=(0, 0, 0, 0, 0), **fields):
     h = PackHead()
     if load_hip().vp8hip_pack_key_header(ctypes.byref(p), int(qindex), ctypes.byref(h)):
         raise ValueError(f"pack_key_header: qindex {qindex} (0..127), deltas {deltas!r} (-15..15) or {fields!r} out of range")
-    out = {name: int(getattr(h, name)) for name in ("bottom", "range", "bit_count", "cache", "pending", "settled")}
-    out["bytes"] = bytes(h.bytes[:h.nbytes])
-    return out
+    return _pack_head_dict(h)
 
 
 def ssim_mean(scores):
@@ -2230,13 +2233,48 @@ class Vp8Hip:
         made = self._to_torch(who, outs, call, "vp8hip_frames_intra_async")
         return dict(zip(names, made))
 
+    def _pack_bound_of(self, name, log2_parts):
+        """vp8hip_<name>(log2_parts) for the context, ValueError where it gives 0"""
+        size = int(getattr(self.L, "vp8hip_" + name)(self.h, int(log2_parts)))
+        if not size:
+            raise ValueError(f"{name}: log2_parts {log2_parts} (0..3) of a configured context")
+        return size
+
+    def _pack_inputs(self, who, coef, side, qindex, deltas, fields, key=False):
+        """the inputs the three pack calls check alike, in their order: coef; a key frame's modes (`side`); the parameters; an inter
+        frame's mv (`side`, or None).  -> (torch, dev, n, p, jq -- to be kept alive --, side's pointer, side's stride in bytes)"""
+        torch, dev = self._torch_device(who)
+        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
+        if not hasattr(coef, "shape") or len(coef.shape) != 5 or not self._dense(coef, torch.int16, (coef.shape[0], rows, cols, 25, 16), dev) or not coef.shape[0]:
+            raise ValueError(f"{who}: coef must be an int16 tensor {['n', rows, cols, 25, 16]}, each job dense, on {dev}")
+        n = int(coef.shape[0])
+        if key and (not hasattr(side, "shape") or not self._dense(side, torch.uint8, (n, rows, cols, 32), dev)):
+            raise ValueError(f"{who}: modes must be a uint8 tensor {[n, rows, cols, 32]}, each job dense, on {dev}")
+        p, jq = _pack_params(who, qindex, deltas, fields, n, key=key)
+        if side is None:
+            return torch, dev, n, p, jq, None, 0
+        if not key and not self._dense(side, torch.int16, (n, 2, rows, cols), dev):
+            raise ValueError(f"{who}: mv must be an int16 tensor {[n, 2, rows, cols]}, each job dense, on {dev}")
+        return torch, dev, n, p, jq, c_void_p(side.data_ptr()), side.stride(0) * side.element_size()
+
+    def _pack_cap(self, who, cap, out_data, bound_fn, p):
+        """`cap` or its default -- out_data's second dimension, else the bound --, checked"""
+        if cap is None:
+            cap = int(out_data.shape[1]) if out_data is not None and len(out_data.shape) == 2 else int(bound_fn(self.h, p.log2_parts))
+        cap = int(cap)
+        if cap < 16 or cap % 16:
+            raise ValueError(f"{who}: cap {cap} (a multiple of 16; log2_parts 0..3)")
+        return cap
+
+    def _pack_info16(self, who, out_info, torch, dev, n):
+        """a given out_info of frames_pack and frames_pack_key, checked (after `cap`, as the wrappers always did)"""
+        if out_info is not None and not (self._dense(out_info, torch.int32, (n, 16), dev) and out_info.is_contiguous()):
+            raise ValueError(f"{who}: out_info must be a contiguous int32 tensor {[n, 16]} on {dev}")
+
     def pack_bound(self, log2_parts=0):
         """a `cap` that always suffices for a frame of frames_pack at the context's size (vp8hip_pack_bound): a multiple of 16, and
         loose -- real frames are a hundredth of it"""
-        size = int(self.L.vp8hip_pack_bound(self.h, int(log2_parts)))
-        if not size:
-            raise ValueError(f"pack_bound: log2_parts {log2_parts} (0..3) of a configured context")
-        return size
+        return self._pack_bound_of("pack_bound", log2_parts)
 
     def frames_pack(self, mv, coef, qindex=40, deltas=(0, 0, 0, 0, 0), cap=None, out_data=None, out_info=None, **fields):
         """Compressed VP8 inter frames from frames_quant's levels and vectors on the context's device (vp8hip_frames_pack_async;
@@ -2254,24 +2292,9 @@ class Vp8Hip:
         multiples of 16; out_info: int32 [n, 16], contiguous.  Stream ordering, the `import torch` first rule and the remark on
         record_stream: as frames_scaled."""
         who = "frames_pack"
-        torch, dev = self._torch_device(who)
-        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
-        if not hasattr(coef, "shape") or len(coef.shape) != 5 or not self._dense(coef, torch.int16, (coef.shape[0], rows, cols, 25, 16), dev) or not coef.shape[0]:
-            raise ValueError(f"{who}: coef must be an int16 tensor {['n', rows, cols, 25, 16]}, each job dense, on {dev}")
-        n = int(coef.shape[0])
-        p, jq = _pack_params(who, qindex, deltas, fields, n)
-        mptr, mstride = None, 0
-        if mv is not None:
-            if not self._dense(mv, torch.int16, (n, 2, rows, cols), dev):
-                raise ValueError(f"{who}: mv must be an int16 tensor {[n, 2, rows, cols]}, each job dense, on {dev}")
-            mptr, mstride = c_void_p(mv.data_ptr()), mv.stride(0) * 2
-        if cap is None:
-            cap = int(out_data.shape[1]) if out_data is not None and len(out_data.shape) == 2 else int(self.L.vp8hip_pack_bound(self.h, p.log2_parts))
-        cap = int(cap)
-        if cap < 16 or cap % 16:
-            raise ValueError(f"{who}: cap {cap} (a multiple of 16; log2_parts 0..3)")
-        if out_info is not None and not (self._dense(out_info, torch.int32, (n, 16), dev) and out_info.is_contiguous()):
-            raise ValueError(f"{who}: out_info must be a contiguous int32 tensor {[n, 16]} on {dev}")
+        torch, dev, n, p, jq, mptr, mstride = self._pack_inputs(who, coef, mv, qindex, deltas, fields)
+        cap = self._pack_cap(who, cap, out_data, self.L.vp8hip_pack_bound, p)
+        self._pack_info16(who, out_info, torch, dev, n)
         outs = [("out_data", out_data, "uint8", (n, cap)), ("out_info", out_info, "int32", (n, 16))]
         made = self._to_torch(who, outs, lambda dp, ds, ip, istride: self.L.vp8hip_frames_pack_async(
             self.h, n, ctypes.byref(p), mptr, mstride, c_void_p(coef.data_ptr()), coef.stride(0) * 2, dp, ds, cap, ip), "vp8hip_frames_pack_async")
@@ -2280,10 +2303,7 @@ class Vp8Hip:
 
     def pack_key_bound(self, log2_parts=0):
         """a `cap` that always suffices for a frame of frames_pack_key at the context's size (vp8hip_pack_key_bound)"""
-        size = int(self.L.vp8hip_pack_key_bound(self.h, int(log2_parts)))
-        if not size:
-            raise ValueError(f"pack_key_bound: log2_parts {log2_parts} (0..3) of a configured context")
-        return size
+        return self._pack_bound_of("pack_key_bound", log2_parts)
 
     def frames_pack_key(self, modes, coef, qindex=40, deltas=(0, 0, 0, 0, 0), cap=None, out_data=None, out_info=None, **fields):
         """Compressed VP8 key frames from frames_intra's modes and levels on the context's device (vp8hip_frames_pack_key_async;
@@ -2298,34 +2318,19 @@ class Vp8Hip:
         partition's, [3..10] the token partitions', [11] skipped macroblocks, [12] B_PRED macroblocks; pack_frames gives the frames
         as bytes.  Stream ordering, the `import torch` first rule and the remark on record_stream: as frames_scaled."""
         who = "frames_pack_key"
-        torch, dev = self._torch_device(who)
-        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
-        if not hasattr(coef, "shape") or len(coef.shape) != 5 or not self._dense(coef, torch.int16, (coef.shape[0], rows, cols, 25, 16), dev) or not coef.shape[0]:
-            raise ValueError(f"{who}: coef must be an int16 tensor {['n', rows, cols, 25, 16]}, each job dense, on {dev}")
-        n = int(coef.shape[0])
-        if not hasattr(modes, "shape") or not self._dense(modes, torch.uint8, (n, rows, cols, 32), dev):
-            raise ValueError(f"{who}: modes must be a uint8 tensor {[n, rows, cols, 32]}, each job dense, on {dev}")
-        p, jq = _pack_params(who, qindex, deltas, fields, n, key=True)
-        if cap is None:
-            cap = int(out_data.shape[1]) if out_data is not None and len(out_data.shape) == 2 else int(self.L.vp8hip_pack_key_bound(self.h, p.log2_parts))
-        cap = int(cap)
-        if cap < 16 or cap % 16:
-            raise ValueError(f"{who}: cap {cap} (a multiple of 16; log2_parts 0..3)")
-        if out_info is not None and not (self._dense(out_info, torch.int32, (n, 16), dev) and out_info.is_contiguous()):
-            raise ValueError(f"{who}: out_info must be a contiguous int32 tensor {[n, 16]} on {dev}")
+        torch, dev, n, p, jq, modes_ptr, modes_stride = self._pack_inputs(who, coef, modes, qindex, deltas, fields, key=True)
+        cap = self._pack_cap(who, cap, out_data, self.L.vp8hip_pack_key_bound, p)
+        self._pack_info16(who, out_info, torch, dev, n)
         outs = [("out_data", out_data, "uint8", (n, cap)), ("out_info", out_info, "int32", (n, 16))]
         made = self._to_torch(who, outs, lambda dp, ds, ip, istride: self.L.vp8hip_frames_pack_key_async(
-            self.h, n, ctypes.byref(p), c_void_p(modes.data_ptr()), modes.stride(0), c_void_p(coef.data_ptr()), coef.stride(0) * 2, dp, ds, cap, ip),
+            self.h, n, ctypes.byref(p), modes_ptr, modes_stride, c_void_p(coef.data_ptr()), coef.stride(0) * 2, dp, ds, cap, ip),
             "vp8hip_frames_pack_key_async")
         del jq
         return made[0], made[1]
 
     def pack_adapt_bound(self, log2_parts=0):
         """a `cap` that always suffices for a frame of frames_pack_adapt at the context's size (vp8hip_pack_adapt_bound)"""
-        size = int(self.L.vp8hip_pack_adapt_bound(self.h, int(log2_parts)))
-        if not size:
-            raise ValueError(f"pack_adapt_bound: log2_parts {log2_parts} (0..3) of a configured context")
-        return size
+        return self._pack_bound_of("pack_adapt_bound", log2_parts)
 
     def frames_pack_adapt(self, mv, coef, qindex=40, deltas=(0, 0, 0, 0, 0), cap=None, flags=ADAPT_ALL, refresh_entropy_probs=1, probs_in=None,
                           counts=False, probs=False, out_data=None, out_info=None, out_counts=None, out_probs=None, **fields):
@@ -2342,17 +2347,7 @@ class Vp8Hip:
         [n, 1104], contiguous, 16-byte aligned) the effective sets -- the next frame's probs_in where refresh_entropy_probs is 1
         --, else None."""
         who = "frames_pack_adapt"
-        torch, dev = self._torch_device(who)
-        rows, cols = self.g.aligned_h // 16, self.g.aligned_w // 16
-        if not hasattr(coef, "shape") or len(coef.shape) != 5 or not self._dense(coef, torch.int16, (coef.shape[0], rows, cols, 25, 16), dev) or not coef.shape[0]:
-            raise ValueError(f"{who}: coef must be an int16 tensor {['n', rows, cols, 25, 16]}, each job dense, on {dev}")
-        n = int(coef.shape[0])
-        p, jq = _pack_params(who, qindex, deltas, fields, n)
-        mptr, mstride = None, 0
-        if mv is not None:
-            if not self._dense(mv, torch.int16, (n, 2, rows, cols), dev):
-                raise ValueError(f"{who}: mv must be an int16 tensor {[n, 2, rows, cols]}, each job dense, on {dev}")
-            mptr, mstride = c_void_p(mv.data_ptr()), mv.stride(0) * 2
+        torch, dev, n, p, jq, mptr, mstride = self._pack_inputs(who, coef, mv, qindex, deltas, fields)
         a = PackAdapt(int(flags), int(refresh_entropy_probs), None, 0)
         if probs_in is not None:
             one = hasattr(probs_in, "shape") and len(probs_in.shape) == 1
@@ -2360,11 +2355,7 @@ class Vp8Hip:
             if not hasattr(probs_in, "shape") or tuple(probs_in.shape) != shape or probs_in.dtype != torch.uint8 or probs_in.device != dev or probs_in.stride(-1) != 1:
                 raise ValueError(f"{who}: probs_in must be a uint8 tensor [{PACK_PROBS_BYTES}] or {[n, PACK_PROBS_BYTES]}, each set dense, on {dev}")
             a.probs_in, a.probs_in_stride = probs_in.data_ptr(), 0 if one else probs_in.stride(0)
-        if cap is None:
-            cap = int(out_data.shape[1]) if out_data is not None and len(out_data.shape) == 2 else int(self.L.vp8hip_pack_adapt_bound(self.h, p.log2_parts))
-        cap = int(cap)
-        if cap < 16 or cap % 16:
-            raise ValueError(f"{who}: cap {cap} (a multiple of 16; log2_parts 0..3)")
+        cap = self._pack_cap(who, cap, out_data, self.L.vp8hip_pack_adapt_bound, p)
         outs = [("out_data", out_data, "uint8", (n, cap)), ("out_info", out_info, "int32", (n, 32))]
         if counts or out_counts is not None:
             outs.append(("out_counts", out_counts, "int32", (n, PACK_COUNTS)))

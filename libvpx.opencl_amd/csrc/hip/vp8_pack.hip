@@ -7,10 +7,11 @@
 //   vp8_pack_tokens_kernel    a lane a token partition: the tokens of macroblock rows part, part + parts, ...
 //   vp8_pack_assemble_kernel  a workgroup a job: tag, partitions and size table into the caller's memory, the job's info.
 // The two coder kernels are launches of their own because their lanes do very different amounts of work and the lanes of a wave go
-// through their loops together.  The bool coder is in vp8_pack_coder.hip.h and the two coder kernels in vp8_pack_coders.inc, both
-// shared with vp8_pack_adapt.hip: here the kernels are made for the default tables.
+// through their loops together.  The bool coder is in vp8_pack_coder.hip.h; the bodies of the coder kernels, the plan's scan and
+// record store and the assemble body are in vp8_pack_tokens.hip.h, shared with vp8_pack_adapt.hip and vp8_pack_key.hip: here the
+// kernels are made for the default tables.
 #include <hip/hip_runtime.h>
-#include "vp8_pack_coder.hip.h"
+#include "vp8_pack_tokens.hip.h"
 
 // ---- the plan -----------------------------------------------------------------------------------------------------------------
 struct PackMv { int r, c; };
@@ -21,32 +22,13 @@ extern "C" __global__ __launch_bounds__(256) void vp8_pack_plan_kernel(const uin
                                                                        uint8_t *scratch, PackLaunch L)
 {
     __shared__ uint8_t s_end[8][32];
-    constexpr int zz[16] = {0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15};
     const int job = blockIdx.y, g = threadIdx.x >> 5, l = threadIdx.x & 31;
     const int cols = L.mb_cols, nmb = L.mb_cols * L.mb_rows;
     const int mb = (int)blockIdx.x * 8 + g;
-    const bool live = mb < nmb && l < 25;
-    const int first = l < 16 ? 1 : 0;   // position 0 of a luma block is not coded: the Y2 block carries it
-    int end = 0;
-    bool bad = false;
-    if (live) {
-        const uint4 *b = (const uint4 *)(coef + coef_stride * (size_t)job + ((size_t)mb * 25 + l) * 32);
-        const uint4 lo = b[0], hi = b[1];
-        const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            const int v = (int16_t)(w[zz[i] >> 1] >> (16 * (zz[i] & 1)));
-            if (i >= first && v) {
-                end = i + 1;
-                bad |= v > PACK_MAX_LEVEL || v < -PACK_MAX_LEVEL;
-            }
-        }
-    }
-    s_end[g][l] = (uint8_t)end;
-    const int half = (threadIdx.x >> 5) & 1;
-    const uint32_t nz = (uint32_t)(__ballot(live && end > first) >> (32 * half)) & PACK_NZ_MASK;
-    const bool any_bad = ((uint32_t)(__ballot(bad) >> (32 * half))) != 0;
-    __syncthreads();
+    uint32_t nz;
+    bool any_bad;
+    // position 0 of a luma block is not coded: the Y2 block carries it
+    pack_plan_scan(coef + coef_stride * (size_t)job, mb, l < 16 ? 1 : 0, mb < nmb && l < 25, s_end[g], nz, any_bad);
     if (l || mb >= nmb) return;
 
     const int r = mb / cols, c = mb - r * cols;
@@ -102,61 +84,33 @@ extern "C" __global__ __launch_bounds__(256) void vp8_pack_plan_kernel(const uin
         }
     }
     uint32_t rec[8] = {nz | (uint32_t)mode << 25, 0, 0, 0, 0, 0, probs, ((uint32_t)dr & 0xffffu) | (uint32_t)dc << 16};
-#pragma unroll
-    for (int b = 0; b < 25; b++) rec[1 + b / 6] |= (uint32_t)s_end[g][b] << (5 * (b % 6));
-    uint4 *out = (uint4 *)(pack_job(scratch, L, job) + (size_t)mb * PACK_RECORD_BYTES);
-    out[0] = make_uint4(rec[0], rec[1], rec[2], rec[3]);
-    out[1] = make_uint4(rec[4], rec[5], rec[6], rec[7]);
-    uint32_t *ctr = pack_counters(scratch, job);
-    if (status) atomicOr(&ctr[PACK_CTR_STATUS], status);
-    if (!nz) atomicAdd(&ctr[PACK_CTR_SKIPPED], 1u);
-    atomicAdd(&ctr[PACK_CTR_MODES + mode], 1u);
+    pack_record_store(scratch, L, job, mb, rec, s_end[g], status);
+    atomicAdd(&pack_counters(scratch, job)[PACK_CTR_MODES + mode], 1u);
 }
 
-// ---- vp8_pack_first_kernel and vp8_pack_tokens_kernel: the two coders with the default tables -----------------------------------------
-#define PACK_ADAPT 0
-#include "vp8_pack_coders.inc"
-#undef PACK_ADAPT
+// ---- the two coders with the default tables -----------------------------------------------------------------------------------
+extern "C" __global__ __launch_bounds__(PACK_CODER_THREADS) void vp8_pack_first_kernel(uint8_t *scratch, int jobs, PackLaunch L)
+{
+    pack_first<false>(scratch, jobs, L);
+}
+
+extern "C" __global__ __launch_bounds__(PACK_CODER_THREADS) void vp8_pack_tokens_kernel(const uint8_t *coef, size_t coef_stride, uint8_t *scratch, int jobs,
+                                                                                       PackLaunch L)
+{
+    pack_tokens<PACK_TOKENS_DEFAULT>(coef, coef_stride, scratch, jobs, L);
+}
 
 // ---- the frame ----------------------------------------------------------------------------------------------------------------
+// three bytes in front: the tag with bit 0 set
 extern "C" __global__ __launch_bounds__(256) void vp8_pack_assemble_kernel(const uint8_t *scratch, uint8_t *dst, size_t dst_stride, uint32_t *info, PackLaunch L)
 {
-    const int job = blockIdx.x, nparts = 1 << L.log2_parts;
-    const uint32_t *ctr = (const uint32_t *)scratch + (size_t)job * PACK_CTR_DWORDS;
-    const uint8_t *area = scratch + L.jobs_off + L.job_bytes * (size_t)job;
-    const uint8_t *first_region = area + (size_t)L.mb_cols * L.mb_rows * PACK_RECORD_BYTES;
-    uint8_t *out = dst + dst_stride * (size_t)job;
-    const uint32_t first = ctr[PACK_CTR_FIRST];
-    uint32_t status = ctr[PACK_CTR_STATUS];
-    unsigned long long total = 3ull + first + 3ull * (nparts - 1);
-    for (int k = 0; k < nparts; k++) total += ctr[PACK_CTR_PARTS + k];
-    if (total > L.cap) status |= PACK_OVERFLOW;
-    const bool failed = status & (PACK_OVERFLOW | PACK_BAD_VECTOR | PACK_BAD_LEVEL);
-    if (threadIdx.x == 0) {
-        uint32_t *o = info + (size_t)job * 16;
-        o[0] = status;
-        o[1] = failed ? 0 : (uint32_t)total;
-        o[2] = first;
-        for (int k = 0; k < 8; k++) o[3 + k] = k < nparts ? ctr[PACK_CTR_PARTS + k] : 0;
-        o[11] = ctr[PACK_CTR_SKIPPED];
-        for (int k = 0; k < 4; k++) o[12 + k] = ctr[PACK_CTR_MODES + k];
-    }
-    if (failed) return;
-    if (threadIdx.x == 0) {
-        const uint32_t tag = 1u | (uint32_t)L.version << 1 | (uint32_t)L.show_frame << 4 | first << 5;
-        out[0] = (uint8_t)tag; out[1] = (uint8_t)(tag >> 8); out[2] = (uint8_t)(tag >> 16);
-        for (int k = 0; k < nparts - 1; k++) {
-            const uint32_t s = ctr[PACK_CTR_PARTS + k];
-            uint8_t *t = out + 3 + first + 3 * k;
-            t[0] = (uint8_t)s; t[1] = (uint8_t)(s >> 8); t[2] = (uint8_t)(s >> 16);
-        }
-    }
-    for (uint32_t i = threadIdx.x; i < first; i += 256) out[3 + i] = first_region[i];
-    size_t at = 3 + (size_t)first + 3 * (size_t)(nparts - 1);
-    for (int k = 0; k < nparts; k++) {
-        const uint32_t s = ctr[PACK_CTR_PARTS + k];
-        const uint8_t *region = first_region + L.first_cap + (size_t)L.part_cap * k;
-        for (uint32_t i = threadIdx.x; i < s; i += 256) out[at + i] = region[i];
-        at += s;
-    }
+    pack_assemble<3>(
+        scratch, dst, dst_stride, info, L, PACK_OVERFLOW | PACK_BAD_VECTOR | PACK_BAD_LEVEL,
+        [](uint32_t *o, const uint32_t *ctr) {
+            for (int k = 0; k < 4; k++) o[12 + k] = ctr[PACK_CTR_MODES + k];
+        },
+        [&](uint8_t *out, uint32_t first) {
+            const uint32_t tag = 1u | (uint32_t)L.version << 1 | (uint32_t)L.show_frame << 4 | first << 5;
+            out[0] = (uint8_t)tag; out[1] = (uint8_t)(tag >> 8); out[2] = (uint8_t)(tag >> 16);
+        });
 }

@@ -8,14 +8,14 @@
 //                                 vp8_hist.hip's shape.  blockIdx.y is the job: a workgroup never holds two jobs' counts.
 //   vp8_pack_choose_kernel        a workgroup a job, a lane a probability: branch counts, the fitted probability, the saving, the
 //                                 update flag and the effective byte; lane 0 the header probabilities and the sums of info[16..19].
-//   vp8_pack_first_adapt_kernel   \ vp8_pack_coders.inc with PACK_ADAPT: the probability section of the header on the device,
-//   vp8_pack_tokens_adapt_kernel  / the job's own vector and coefficient tables.
+//   vp8_pack_first_adapt_kernel   \ vp8_pack_tokens.hip.h's pack_first<true> and pack_tokens<PACK_TOKENS_OWN>: the probability section
+//   vp8_pack_tokens_adapt_kernel  / of the header on the device, the job's own vector and coefficient tables.
 //   vp8_pack_adapt_info_kernel    the call's 32 uint32 a job from the assemble kernel's 16 and the choose kernel's 4.
 // Integer adds commute: the same bits in every run.  Levels and vector differences are data here, never addresses: a level of any
 // size counts as DCT_CAT6 and a difference by its low ten magnitude bits (the plan kernel's status says where either is refused).
 #include <hip/hip_runtime.h>
 #define PACK_CODER_INLINE __forceinline__
-#include "vp8_pack_coder.hip.h"
+#include "vp8_pack_tokens.hip.h"
 
 namespace pack_tables {
 #include "../host/vp8_enc_tables.c"
@@ -46,8 +46,6 @@ static __device__ __forceinline__ void count_component(uint32_t *h, int v)
 extern "C" __global__ __launch_bounds__(256) void vp8_pack_count_kernel(const uint8_t *coef, size_t coef_stride, uint8_t *scratch, PackLaunch L, PackAdapt A)
 {
     __shared__ uint32_t s_hist[4][PACK_ADAPT_COUNT_DWORDS];
-    constexpr int zz[16] = {0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15};
-    constexpr int bands[16] = {0, 1, 2, 3, 6, 4, 5, 6, 6, 6, 6, 6, 6, 6, 6, 7};
 #pragma unroll 1
     for (int t = threadIdx.x; t < 4 * PACK_ADAPT_COUNT_DWORDS; t += 256) (&s_hist[0][0])[t] = 0u;
     __syncthreads();
@@ -68,21 +66,9 @@ extern "C" __global__ __launch_bounds__(256) void vp8_pack_count_kernel(const ui
             const int r = mb / cols, c = mb - r * cols;
             const uint32_t up = r ? recs[2 * (mb - cols)].x & PACK_NZ_MASK : 0, left = c ? recs[2 * (mb - 1)].x & PACK_NZ_MASK : 0;
             const int blk = l, type = blk == 24 ? 1 : blk < 16 ? 0 : 2, first = blk < 16;
-            uint32_t a, b;              // the contexts above and to the left, as the token coder takes them
-            if (blk == 24) {
-                a = up >> 24; b = left >> 24;
-            } else if (blk < 16) {
-                a = blk >> 2 ? own >> (blk - 4) : up >> (blk + 12);
-                b = blk & 3 ? own >> (blk - 1) : left >> (blk + 3);
-            } else {
-                const int q = (blk - 16) & 3;
-                a = q >> 1 ? own >> (blk - 2) : up >> (blk + 2);
-                b = q & 1 ? own >> (blk - 1) : left >> (blk + 1);
-            }
-            int ctx = (int)((a & 1) + (b & 1));
-            const int word = blk / 6;
-            const uint32_t ew = word == 0 ? lo.y : word == 1 ? lo.z : word == 2 ? lo.w : word == 3 ? hi.x : hi.y;
-            const int end = (int)(ew >> (5 * (blk - 6 * word))) & 31;
+            // the context and the end as the token coder takes them
+            int ctx = pack_block_ctx(blk, own, up, left);
+            const int end = pack_record_end(lo, hi.x, hi.y, blk);
             const uint4 *p = (const uint4 *)(coef + coef_stride * (size_t)job + ((size_t)mb * 25 + blk) * 32);
             const uint4 p0 = p[0], p1 = p[1];
             const uint32_t w[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
@@ -90,15 +76,15 @@ extern "C" __global__ __launch_bounds__(256) void vp8_pack_count_kernel(const ui
 #pragma unroll
             for (int i = 0; i < 16; i++) {
                 if (i >= first && i < end) {
-                    const int v = (int16_t)(w[zz[i] >> 1] >> (16 * (zz[i] & 1)));
+                    const int z = pack_zigzag(i), v = (int16_t)(w[z >> 1] >> (16 * (z & 1)));
                     const int x = v < 0 ? -v : v;
-                    const int tok = x < 5 ? x : x < 7 ? 5 : x < 11 ? 6 : x < 19 ? 7 : x < 35 ? 8 : x < 67 ? 9 : 10;
-                    count_add(row, (bands[i] * 3 + ctx) * 12 + tok);
+                    const int tok = x < 5 ? x : 5 + pack_category(x);
+                    count_add(row, (pack_band(i) * 3 + ctx) * 12 + tok);
                     ctx = x == 0 ? 0 : x == 1 ? 1 : 2;
                 }
             }
             const int at = end > first ? end : first;       // the end of block, unless the block ends at step 15
-            if (at < 16) count_add(row, (((int)(0x7666666665463210ull >> (4 * at)) & 15) * 3 + ctx) * 12 + 11);
+            if (at < 16) count_add(row, (pack_band(at) * 3 + ctx) * 12 + 11);
         }
     }
     __syncthreads();
@@ -230,10 +216,17 @@ extern "C" __global__ __launch_bounds__(256) void vp8_pack_choose_kernel(uint8_t
     hdr[7] = 0;
 }
 
-// ---- vp8_pack_first_adapt_kernel and vp8_pack_tokens_adapt_kernel: the two coders with every job's own tables ---------------------
-#define PACK_ADAPT 1
-#include "vp8_pack_coders.inc"
-#undef PACK_ADAPT
+// ---- the two coders with every job's own tables ------------------------------------------------------------------------------------
+extern "C" __global__ __launch_bounds__(PACK_CODER_THREADS) void vp8_pack_first_adapt_kernel(uint8_t *scratch, int jobs, PackLaunch L, PackAdapt A)
+{
+    pack_first<true>(scratch, jobs, L, A);
+}
+
+extern "C" __global__ __launch_bounds__(PACK_CODER_THREADS) void vp8_pack_tokens_adapt_kernel(const uint8_t *coef, size_t coef_stride, uint8_t *scratch,
+                                                                                             int jobs, PackLaunch L, PackAdapt A)
+{
+    pack_tokens<PACK_TOKENS_OWN>(coef, coef_stride, scratch, jobs, L, A);
+}
 
 // a lane an entry: [0..15] the assemble kernel's, [16..19] the choose kernel's (0 for a job the plan refuses), the rest 0
 extern "C" __global__ __launch_bounds__(256) void vp8_pack_adapt_info_kernel(const uint8_t *scratch, int jobs, PackAdapt A)

@@ -1,8 +1,7 @@
 // Internal to libvp8hip.so: the bool coder of the frame packer, shared by vp8_pack.hip (vp8hip_frames_pack_async: the default
-// tables, the header complete from the host) and vp8_pack_adapt.hip (vp8hip_frames_pack_adapt_async: every job its own tables, the
-// header's probability section coded on the device).  The two coder kernels themselves are vp8_pack_coders.inc, which each of the
-// two files includes once: a second translation unit over a shared body, so that vp8_pack.hip's kernels stay the device code they
-// were (profiles/pack_adapt_codegen.txt).
+// tables, the header complete from the host), vp8_pack_adapt.hip (vp8hip_frames_pack_adapt_async: every job its own tables, the
+// header's probability section coded on the device) and vp8_pack_key.hip (vp8hip_frames_pack_key_async: key frames).  What the
+// kernels of the three files share above the coder is vp8_pack_tokens.hip.h; each file stays a translation unit of its own.
 //
 // The bool coder is RFC 6386 section 7.3 with the carry deferred: the last byte that is not 0xFF is held back (cache) with the
 // count of 0xFF bytes behind it (pending), so a carry never walks back through stored bytes, and settled bytes leave in whole

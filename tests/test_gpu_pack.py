@@ -9,7 +9,7 @@ import torch  # noqa: F401  (first: the library then shares torch's HIP runtime)
 import numpy as np
 import pytest
 
-from handover_testlib import assert_destinations_refused, assert_guards_intact, guarded, picture_into
+from handover_testlib import assert_destinations_refused, assert_guards_intact, guarded, hip_range, picture_into
 import pack_reference as R
 import scale_reference as SC
 import tfilter_reference as TR
@@ -357,3 +357,146 @@ def test_the_wrapper_and_the_refusals(pkg, contexts):
     ctx.sync()
     assert torch.equal(dst, filled[0]) and torch.equal(inf, filled[1])         # nothing was enqueued by any of them
     assert b"vp8hip_frames_pack_async" in ctx.L.vp8hip_last_error(ctx.h)
+
+
+def test_pack_refusal_texts(pkg):
+    """What vp8hip_last_error says after each refusal of the three packer calls (vp8hip_frames_pack_async, _pack_adapt_async,
+    _pack_key_async), and, by two faults at once, which check comes first: the texts the library gave before the three calls shared
+    their host path.  48x32 -- 3 x 2 macroblocks, the smallest size at which every check is reachable --, one job (two where the
+    second job's qindex is the fault) and 16 KB of device memory; every call here is refused and nothing is enqueued.  A
+    destination too small is one that begins 16 bytes too near the end of its allocation.  (The alignment refusal prints a pointer
+    and is left out.)"""
+    P = pkg
+    ctx = P.Vp8Hip(0)
+    try:
+        ctx.configure(48, 32, 2, 1)
+        L, vp = ctx.L, ctypes.c_void_p
+        mem = torch.empty((16384,), dtype=torch.uint8, device="cuda:0")
+        d = mem.data_ptr()
+        base, asize = hip_range(d)
+        end = base + asize
+        assert d % 16 == 0 and end % 16 == 0 and ctx.pack_bound(0) == 40288
+        # a job's bytes: dst 64 (the cap), info 64 (128: the adapt call's), counts 4864, probs 1104, mv 24, coef 4800, modes 192
+        at = dict(dst=d, info=d + 256, counts=d + 512, probs_out=d + 5632, mv=d + 6784, coef=d + 6912, probs_in=d + 11776, modes=d + 12928)
+
+        def params(cls, defaults, qindex, job_qindex, fields):
+            p = cls()
+            for name, v in {**defaults, **{k: v for k, v in fields.items() if k != "delta"}}.items():
+                setattr(p, name, v)
+            p.delta = (ctypes.c_int * 5)(*fields.get("delta", (0, 0, 0, 0, 0)))
+            p.qindex = qindex
+            jq = (ctypes.c_uint8 * len(job_qindex))(*job_qindex) if job_qindex else None
+            if jq:
+                p.job_qindex = jq
+            return p, jq
+
+        def pack(n=1, qindex=40, job_qindex=None, cap=64, stride=64, mvs=24, cs=4800, null=(), **kw):
+            a = {k: None if k in null else kw.pop(k, v) for k, v in at.items()}
+            p, jq = params(P.PackParams, P.PACK_DEFAULTS, qindex, job_qindex, kw)
+            return L.vp8hip_frames_pack_async(ctx.h, n, None if "p" in null else ctypes.byref(p), a["mv"], mvs, a["coef"], cs, a["dst"], stride, cap, a["info"])
+
+        def adapt(n=1, qindex=40, job_qindex=None, cap=64, stride=64, mvs=24, cs=4800, flags=15, rep=1, ps=1104, null=(), **kw):
+            a = {k: None if k in null else kw.pop(k, v) for k, v in at.items()}
+            p, jq = params(P.PackParams, P.PACK_DEFAULTS, qindex, job_qindex, kw)
+            ad = P.PackAdapt(flags, rep, a["probs_in"], ps)
+            return L.vp8hip_frames_pack_adapt_async(ctx.h, n, None if "p" in null else ctypes.byref(p), None if "a" in null else ctypes.byref(ad), a["mv"],
+                                                    mvs, a["coef"], cs, a["dst"], stride, cap, a["info"], a["counts"], a["probs_out"])
+
+        def key(n=1, qindex=40, job_qindex=None, cap=64, stride=64, mos=192, cs=4800, null=(), **kw):
+            a = {k: None if k in null else kw.pop(k, v) for k, v in at.items()}
+            p, jq = params(P.PackKeyParams, P.PACK_KEY_DEFAULTS, qindex, job_qindex, kw)
+            return L.vp8hip_frames_pack_key_async(ctx.h, n, None if "p" in null else ctypes.byref(p), a["modes"], mos, a["coef"], cs, a["dst"], stride, cap,
+                                                  a["info"])
+
+        def inter(version=0, flags="1 0 1 0 0 0 0", level=0, sharp=0, deltas="0 0 0 0 0", ref=1, copies="0 0", parts=0, probs="200 150 140 100"):
+            return (f": version {version} (0..3), flags {flags} (0, 1), filter level {level} (0..63), sharpness {sharp} (0..7), deltas {deltas} (-15..15), "
+                    f"ref_frame {ref} (1..3), buffer copies {copies} (0..2), log2_parts {parts} (0..3), probabilities {probs} (1..255)")
+
+        def intra(version=0, flags="1 0 0 0", level=0, sharp=0, deltas="0 0 0 0 0", parts=0, skip=200):
+            return (f": version {version} (0..3), flags {flags} (0, 1), filter level {level} (0..63), sharpness {sharp} (0..7), deltas {deltas} (-15..15), "
+                    f"log2_parts {parts} (0..3), prob_skip_false {skip} (1..255)")
+        assert inter() == (": version 0 (0..3), flags 1 0 1 0 0 0 0 (0, 1), filter level 0 (0..63), sharpness 0 (0..7), deltas 0 0 0 0 0 (-15..15), ref_frame 1 "
+                           "(1..3), buffer copies 0 0 (0..2), log2_parts 0 (0..3), probabilities 200 150 140 100 (1..255)")
+        assert intra() == (": version 0 (0..3), flags 1 0 0 0 (0, 1), filter level 0 (0..63), sharpness 0 (0..7), deltas 0 0 0 0 0 (-15..15), log2_parts 0 (0..3), "
+                           "prob_skip_false 200 (1..255)")
+        fit = " frames of {} bytes, {} apart, do not fit in the destination's allocation"
+        inter_only = [
+            (dict(null=("p",)), ": bad arguments"),
+            (dict(version=-1), inter(version=-1)), (dict(show_frame=2), inter(flags="2 0 1 0 0 0 0")), (dict(filter_type=-1), inter(flags="1 -1 1 0 0 0 0")),
+            (dict(refresh_last=2), inter(flags="1 0 2 0 0 0 0")), (dict(refresh_golden=2), inter(flags="1 0 1 2 0 0 0")),
+            (dict(refresh_alt=-1), inter(flags="1 0 1 0 -1 0 0")), (dict(sign_bias_golden=2), inter(flags="1 0 1 0 0 2 0")),
+            (dict(sign_bias_alt=2), inter(flags="1 0 1 0 0 0 2")), (dict(filter_level=64), inter(level=64)), (dict(sharpness=8), inter(sharp=8)),
+            (dict(delta=(0, 0, 16, 0, 0)), inter(deltas="0 0 16 0 0")), (dict(delta=(0, 0, 0, 0, -16)), inter(deltas="0 0 0 0 -16")),
+            (dict(ref_frame=0), inter(ref=0)), (dict(ref_frame=4), inter(ref=4)), (dict(copy_buffer_to_gf=3), inter(copies="3 0")),
+            (dict(copy_buffer_to_arf=-1), inter(copies="0 -1")), (dict(log2_parts=4), inter(parts=4)), (dict(prob_skip_false=0), inter(probs="0 150 140 100")),
+            (dict(prob_intra=256), inter(probs="200 256 140 100")), (dict(prob_last=0), inter(probs="200 150 0 100")),
+            (dict(prob_gf=256), inter(probs="200 150 140 256")),
+            (dict(mvs=20), " (mv): stride 20 below the frame's 24 bytes"),
+            (dict(mv=at["dst"]), ": dst and mv overlap"), (dict(mv=at["info"]), ": info and mv overlap"),
+            # two faults: the parameters before the quantiser; of two inputs the vectors first; an input's stride before an overlap
+            (dict(version=4, qindex=128), inter(version=4)),
+            (dict(mvs=20, cs=4784), " (mv): stride 20 below the frame's 24 bytes"),
+            (dict(mvs=20, info=at["dst"]), " (mv): stride 20 below the frame's 24 bytes"),
+            (dict(coef=at["dst"], mv=at["info"]), ": dst and coef overlap")]
+        pack_only = [(dict(info=end - 64 + 16), " (info): 1" + fit.format(64, 64))]
+        adapt_only = [
+            (dict(null=("a",)), ": bad arguments"),
+            (dict(flags=16), ": flags 16 (VP8HIP_ADAPT_* bits), refresh_entropy_probs 1 (0, 1)"),
+            (dict(flags=-1), ": flags -1 (VP8HIP_ADAPT_* bits), refresh_entropy_probs 1 (0, 1)"),
+            (dict(rep=2), ": flags 15 (VP8HIP_ADAPT_* bits), refresh_entropy_probs 2 (0, 1)"),
+            (dict(info=end - 128 + 16), " (info): 1" + fit.format(128, 128)),
+            (dict(counts=end - 4864 + 16), " (counts): 1" + fit.format(4864, 4864)),
+            (dict(probs_out=end - 1104 + 16), " (probs_out): 1" + fit.format(1104, 1104)),
+            (dict(ps=1088), " (probs_in): stride 1088 below the frame's 1104 bytes"),
+            (dict(counts=at["dst"]), ": dst and counts overlap"), (dict(probs_out=at["dst"]), ": dst and probs_out overlap"),
+            (dict(probs_in=at["dst"]), ": dst and probs_in overlap"), (dict(counts=at["info"]), ": info and counts overlap"),
+            (dict(probs_out=at["info"]), ": info and probs_out overlap"), (dict(probs_in=at["info"]), ": info and probs_in overlap"),
+            (dict(probs_out=at["counts"]), ": counts and probs_out overlap"), (dict(mv=at["counts"]), ": counts and mv overlap"),
+            (dict(coef=at["counts"]), ": counts and coef overlap"), (dict(probs_in=at["counts"]), ": counts and probs_in overlap"),
+            (dict(mv=at["probs_out"]), ": probs_out and mv overlap"), (dict(coef=at["probs_out"]), ": probs_out and coef overlap"),
+            (dict(probs_in=at["probs_out"]), ": probs_out and probs_in overlap"),
+            # two faults: cap before the adapt call's own parameters, those before the memory; the outputs before the inputs
+            (dict(cap=24, flags=16), ": cap 24 (a multiple of 16, 16 .. the stride 64)"),
+            (dict(flags=16, mvs=20), ": flags 16 (VP8HIP_ADAPT_* bits), refresh_entropy_probs 1 (0, 1)"),
+            (dict(probs_out=end - 1104 + 16, mvs=20), " (probs_out): 1" + fit.format(1104, 1104)),
+            (dict(ps=1088, counts=at["dst"]), " (probs_in): stride 1088 below the frame's 1104 bytes")]
+        key_only = [
+            (dict(null=("p",)), ": bad arguments"), (dict(null=("modes",)), ": bad arguments"),
+            (dict(version=4), intra(version=4)), (dict(show_frame=-1), intra(flags="-1 0 0 0")), (dict(color_space=2), intra(flags="1 2 0 0")),
+            (dict(clamping_type=2), intra(flags="1 0 2 0")), (dict(filter_type=2), intra(flags="1 0 0 2")), (dict(filter_level=-1), intra(level=-1)),
+            (dict(sharpness=8), intra(sharp=8)), (dict(delta=(-16, 0, 0, 0, 0)), intra(deltas="-16 0 0 0 0")), (dict(log2_parts=-1), intra(parts=-1)),
+            (dict(prob_skip_false=256), intra(skip=256)),
+            (dict(info=end - 64 + 16), " (info): 1" + fit.format(64, 64)),
+            (dict(mos=188), " (modes): stride 188 below the frame's 192 bytes"),
+            (dict(modes=at["dst"]), ": dst and modes overlap"), (dict(modes=at["info"]), ": info and modes overlap"),
+            (dict(version=4, qindex=128), intra(version=4)),
+            (dict(mos=188, cs=4784), " (modes): stride 188 below the frame's 192 bytes"),
+            (dict(coef=at["dst"], modes=at["dst"]), ": dst and modes overlap")]
+        for call, who, own in ((pack, "vp8hip_frames_pack_async", inter_only + pack_only), (adapt, "vp8hip_frames_pack_adapt_async", inter_only + adapt_only),
+                               (key, "vp8hip_frames_pack_key_async", key_only)):
+            shared = [
+                (dict(n=0), ": bad arguments"), (dict(null=("coef",)), ": bad arguments"), (dict(null=("dst",)), ": bad arguments"),
+                (dict(null=("info",)), ": bad arguments"),
+                (dict(qindex=128), ": qindex 128 (0..127)"), (dict(qindex=-1), ": qindex -1 (0..127)"),
+                (dict(n=2, job_qindex=(5, 200)), ": job_qindex[1] = 200 (0..127)"),
+                (dict(cap=0), ": cap 0 (a multiple of 16, 16 .. the stride 64)"), (dict(cap=24), ": cap 24 (a multiple of 16, 16 .. the stride 64)"),
+                (dict(cap=80), ": cap 80 (a multiple of 16, 16 .. the stride 64)"),
+                (dict(dst=end - 64 + 16), " (dst): 1" + fit.format(64, 64)),
+                (dict(cs=4784), " (coef): stride 4784 below the frame's 4800 bytes"),
+                (dict(info=at["dst"]), ": dst and info overlap"), (dict(coef=at["dst"]), ": dst and coef overlap"),
+                (dict(coef=at["info"]), ": info and coef overlap"),
+                # two faults: the arguments first, then the quantiser -- job_qindex where it is given, whatever qindex is --, then cap,
+                # then the memory, a span's own fault before an overlap, the overlaps in the order of the outputs
+                (dict(n=0, version=4), ": bad arguments"), (dict(qindex=128, cap=0), ": qindex 128 (0..127)"),
+                (dict(qindex=128, job_qindex=(200,)), ": job_qindex[0] = 200 (0..127)"),
+                (dict(qindex=128, job_qindex=(5,), cap=24), ": cap 24 (a multiple of 16, 16 .. the stride 64)"),
+                (dict(n=2, job_qindex=(5, 200), cap=0), ": job_qindex[1] = 200 (0..127)"),
+                (dict(cap=80, cs=4784), ": cap 80 (a multiple of 16, 16 .. the stride 64)"),
+                (dict(dst=end - 64 + 16, cs=4784), " (dst): 1" + fit.format(64, 64)),
+                (dict(cs=4784, info=at["dst"]), " (coef): stride 4784 below the frame's 4800 bytes"),
+                (dict(info=at["dst"], coef=at["info"]), ": dst and info overlap")]
+            for kw, text in shared + own:
+                assert call(**kw) == -2, (who, kw)
+                assert L.vp8hip_last_error(ctx.h).decode() == (who + text)[:255], (who, kw)     # (the context keeps 255 characters)
+    finally:
+        ctx.close()
